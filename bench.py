@@ -39,6 +39,29 @@ NSLP0 = 2.0e-4             # amplitude of the frozen isopycnal slopes that drive
 
 FORCING = {"default": {}, "calm": {"ustarw0": 5.0e-5}}
 
+# --dump-outputs: the state blomgpu_step leaves to its caller, as the caller downloads it (both time levels, halos included)
+DUMP_FIELDS = ["u", "v", "dp", "temp", "saln", "sigma", "trc", "p", "pb", "ub", "vb", "uflx", "vflx"]
+DUMP_MAX_ELEMS = 1 << 19        # per field: a larger field is written as a fixed, seeded sample of this many elements (4 MiB)
+DUMP_SEED = 0
+
+
+def dump_outputs(gpu, outdir):
+    """Write DUMP_FIELDS as outdir/<name>.npy (float64, flattened).  A field of more than DUMP_MAX_ELEMS elements is written as
+    the elements at a sorted sample of flat indices drawn by a generator seeded with DUMP_SEED, so the sample depends only on the
+    field's size: two runs with the same arguments write the same elements.  13 fields x 4 MiB stay under 64 MB."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    total = 0
+    for nm in DUMP_FIELDS:
+        a = gpu.get(nm).astype(np.float64, copy=False).ravel()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        np.save(os.path.join(outdir, nm + ".npy"), a)
+        total += a.nbytes
+    assert total <= 64 * 10**6, total
+    return total
+
 
 def build_case(cfg, advmth="remap", tracers="default", forcing="default"):
     import numpy as np
@@ -796,7 +819,12 @@ def main():
     ap.add_argument("--rccl-self", action="store_true",
                     help="N=1 only: route the halo update through the RCCL transport (rank sends to itself) "
                          "to measure the exchange overhead of the N>1 path on one GPU")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state they left (DUMP_FIELDS, float64; a fixed seeded sample of each "
+                         "large field) as DIR/<name>.npy, for comparing the outputs of two builds; one tile on one GPU only")
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus != 1 or args.tiles or args.config in ("hor3map", "ale", "hybrid")):
+        raise SystemExit("bench.py: --dump-outputs writes the state of one tile on one GPU (--gpus 1, no --tiles, not hor3map/ale/hybrid)")
     if args.config == "hor3map":
         return bench_hor3map(args)
     if args.config == "ale":
@@ -956,6 +984,8 @@ def main():
     dt = time.perf_counter() - t0
     graph_steps_timed = int(gpu.get_real("graph_steps") - g0)     # how many of the timed steps were graph replays (0 unless --opt use_graph=1)
     dt = launch.max_over_ranks(dt, env, device="cuda" if on_gpu else "cpu")
+    if args.dump_outputs:
+        dump_outputs(gpu, args.dump_outputs)          # the state the last timed step left, before any further step
 
     # ---- dominant kernel class, timed with HIP events on the library's stream over K more steps
     gpu.set("timing", 1)

@@ -17,29 +17,44 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _BUILD_OF = {"fuk95_ref": "fuk95"}
 
 
+_LOADABLE = {}
+
+
 def ref_lib_path(cfg):
-    return os.path.join(_HERE, "_ref", _BUILD_OF.get(cfg, cfg), "libblomref.so")
+    """The loadable reference library of cfg, or None where it was not built.
 
-
-def _unpack(path):
-    """The channel- and tnx-sized libraries carry ~100 MB of the reference's initialised module arrays each (constant
-    patterns: 1.5 MB gzipped) and the snapshot that travels to the GPU box is limited to 512 MiB, so oracle/Makefile
-    leaves a libblomref.so.gz beside them and .gpurunignore keeps the unpacked files at home; unpack on first use."""
-    gz = path + ".gz"
-    if os.path.exists(path) or not os.path.exists(gz):
-        return
+    oracle/Makefile keeps every library gzipped (oracle/_ref/<cfg>/libblomref.so.gz): the module arrays of the channel- and
+    tnx-sized builds make a library of ~100 MB (1.5 MB packed), and oracle/_ref goes wherever the tree goes.  The first use
+    unpacks it into a per-user directory under the system's temporary directory, named by the archive's content, so that
+    oracle/_ref itself never grows and a rebuilt library is never shadowed by an old copy."""
+    if cfg in _LOADABLE:
+        return _LOADABLE[cfg]
+    lib = _BUILD_OF.get(cfg, cfg)
+    gz = os.path.join(_HERE, "_ref", lib, "libblomref.so.gz")
+    if not os.path.exists(gz):
+        plain = gz[:-3]                          # a library left unpacked by an earlier recipe
+        return plain if os.path.exists(plain) else None
     import gzip
+    import hashlib
     import shutil
-    tmp = f"{path}.{os.getpid()}.tmp"
-    with gzip.open(gz, "rb") as src, open(tmp, "wb") as dst:
-        shutil.copyfileobj(src, dst, 1 << 24)
-    os.chmod(tmp, 0o755)
-    os.replace(tmp, path)
+    import tempfile
+    with open(gz, "rb") as f:
+        key = hashlib.sha256(f.read()).hexdigest()[:16]
+    cache = os.path.join(tempfile.gettempdir(), f"blomref-{os.getuid()}")
+    os.makedirs(cache, exist_ok=True)
+    path = os.path.join(cache, f"{lib}-{key}.so")
+    if not os.path.exists(path):
+        tmp = f"{path}.{os.getpid()}.tmp"
+        with gzip.open(gz, "rb") as src, open(tmp, "wb") as dst:
+            shutil.copyfileobj(src, dst, 1 << 24)
+        os.chmod(tmp, 0o755)
+        os.replace(tmp, path)
+    _LOADABLE[cfg] = path
+    return path
 
 
 def have_ref(cfg):
-    _unpack(ref_lib_path(cfg))
-    return os.path.exists(ref_lib_path(cfg))
+    return ref_lib_path(cfg) is not None
 
 
 class RefBlom:
@@ -49,7 +64,6 @@ class RefBlom:
     def __init__(self, cfg):
         self.cfg = cfg
         # RTLD_LOCAL + distinct file => several configs can coexist in a process.
-        _unpack(ref_lib_path(cfg))
         self.lib = C.CDLL(ref_lib_path(cfg), mode=os.RTLD_LOCAL | os.RTLD_NOW)
         d = (C.c_int * 8)()
         self.lib.ref_dims(d)

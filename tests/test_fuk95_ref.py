@@ -4,6 +4,7 @@ against the reference's test input tests/fuk95/limits (kept as a data fixture: t
 modules themselves cannot be built here (mod_fuk95 uses mod_mxlayr -> netCDF; mod_inicon netCDF + GSW), so the state is
 checked against what the routines are meant to produce; what the reference's stages then make of it is pinned by
 tests/golden/fuk95_ref_crc.json (tests/test_oracle_golden.py, tests/test_gpu_golden.py)."""
+import hashlib
 import os
 
 import numpy as np
@@ -12,6 +13,7 @@ from blom_amd.cases import make_case, FUK95_LIMITS, _delphi, GRAV
 from blom_amd.namelist import read_namelist, options_from_namelists
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+FUK95_LIMITS_SHA256 = "c34958e8ffd43b4774aa9fd18d871ab0948c260ee171ddf6388999370d3f4c39"
 
 
 def test_limits_file_of_the_reference_test_gives_the_case_options():
@@ -25,9 +27,9 @@ def test_limits_file_of_the_reference_test_gives_the_case_options():
     for k, v in FUK95_LIMITS.items():
         assert o[k] == v, (k, o[k], v)
     assert (o["vcoord_type"], o["advmth"], o["pgfmth"]) == ("cntiso_hybrid", "cppm", "dynamic enthalpy")
-    ref = "/root/reference/tests/fuk95/limits"
-    if os.path.exists(ref):                              # the fixture is the reference's file
-        assert open(ref).read() == open(os.path.join(HERE, "golden", "fuk95_limits")).read()
+    # the fixture is the reference's tests/fuk95/limits byte for byte (its SHA-256, taken from the reference's file)
+    with open(os.path.join(HERE, "golden", "fuk95_limits"), "rb") as f:
+        assert hashlib.sha256(f.read()).hexdigest() == FUK95_LIMITS_SHA256
 
 
 def test_state_is_what_the_generator_describes():

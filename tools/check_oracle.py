@@ -1,7 +1,8 @@
 """Dev helper: step the reference through the dyncore sequence and, stage by stage, feed the
 same inputs to the C restatement and compare every field exactly."""
-import sys, numpy as np
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, numpy as np
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, 'tests'))
 from blom_amd.cases import make_case
 from blom_amd import hostinit
 from blom_amd.stepper import dyncore_step

@@ -1,7 +1,8 @@
 """Dev helper: free-running comparison -- reference and C restatement start from the same
 state and are stepped independently; report first divergence."""
-import sys, numpy as np, time
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests')
+import os, sys, numpy as np, time
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, _ROOT); sys.path.insert(0, os.path.join(_ROOT, 'tests'))
 from blom_amd.cases import make_case
 from blom_amd import hostinit
 from blom_amd.stepper import dyncore_step

@@ -1,6 +1,6 @@
 """Dev helper: run the reference dyncore sequence and report where NaN/Inf first appear."""
-import sys, numpy as np
-sys.path.insert(0,'/root/repo')
+import os, sys, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from blom_amd.cases import make_case
 from blom_amd import hostinit
 from blom_amd.stepper import dyncore_step, DYNCORE_STAGES
