@@ -6,6 +6,7 @@
 // strips over rows 1-nhl..jj+nhl, so the corners travel with it.  Messages: mhl*(jj+2*nhl)*nlev reals per
 // neighbour, packed/unpacked by small kernels on the context's stream; RCCL runs on the same
 // stream, so ordering with the stage kernels needs no events.
+#include "../../include/blomgpu.h"
 #include "blomgpu_internal.h"
 #include <rccl/rccl.h>
 #include <cstring>
@@ -413,6 +414,8 @@ int rccl_xctilr(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl) {
   return rccl_xctilr_multi(c, &a, 1, nlev, mhl, nhl);
 }
 
+unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init);     // halo.hip
+
 extern "C" {
 // 128-byte ncclUniqueId created on rank 0 and distributed by the launcher (torch.distributed in
 // bench.py); every rank then joins the communicator.  Tiles: npx = nranks along i, npy = 1.
@@ -510,6 +513,90 @@ int blomgpu_rccl_attach_barotp_global(blomgpu_ctx *c, blomgpu_ctx *G, const int 
   G->stream = c->stream;
   G->stream_borrowed = true;
   c->bt_global = B;
+  return 0;
+}
+// xccrc of the whole decomposed domain (phy/mod_xc.F90:2195-2322; chksum, phy/mod_checksum.F90:41-74): a collective, every
+// rank calls it and every rank gets the same value.  Each tile forms the CRCs of its own 9-column strips with the code behind
+// blomgpu_crc_strips (the halo update the reference performs there included); the strips travel to rank 0 as doubles (exact:
+// a CRC is below 2^53) behind a header (l0, ns, j0, jj), rank 0 chains a row's strips in global order, then the rows
+// (blom_amd/tiles.py: chain_crc), and sends the result back to every rank.  Rank 0's own block and result travel through
+// send/recv to itself like everyone else's, so one rank alone runs the whole path.  End-of-run diagnostics: off the hot path.
+int blomgpu_rccl_crc(blomgpu_ctx *c, const char *name, int lev0, int nlev, int itype, unsigned *crc) {
+  RcclComm *R = c->tiling.rccl;
+  if (!R) return blomgpu_crc(c, name, lev0, nlev, itype, crc);
+  const DevView &h = c->h;
+  const int W = 2 * NBDY + 1, ntot = (h.itdm + W - 1) / W;
+  std::vector<unsigned> mine((size_t)h.jj * ntot);
+  int l0 = 0, ns = 0;
+  if (int rc = blomgpu_crc_strips(c, name, lev0, nlev, itype, mine.data(), (int)mine.size(), &l0, &ns)) return rc;
+  const int me = R->rank, nr = R->nranks;
+  hipStream_t st = c->stream;
+  const size_t nmine = (size_t)ns * h.jj;
+  std::vector<double> hsend(4 + nmine), hhdr(4 * (size_t)nr);
+  hsend[0] = l0; hsend[1] = ns; hsend[2] = h.j0; hsend[3] = h.jj;
+  for (size_t x = 0; x < nmine; x++) hsend[4 + x] = mine[x];
+  double *dsend = nullptr, *dhdr = nullptr, *dblk = nullptr, *dres = nullptr;
+  struct Bufs {                                           // freed on every return
+    double **p[4];
+    ~Bufs() { for (double **q : p) if (*q) (void)hipFree(*q); }
+  } bufs{{&dsend, &dhdr, &dblk, &dres}};
+  HIPCHK(c, hipMalloc((void **)&dsend, hsend.size() * sizeof(double)));
+  HIPCHK(c, hipMalloc((void **)&dhdr, hhdr.size() * sizeof(double)));
+  HIPCHK(c, hipMalloc((void **)&dres, 2 * sizeof(double)));
+  HIPCHK(c, hipMemcpyAsync(dsend, hsend.data(), hsend.size() * sizeof(double), hipMemcpyHostToDevice, st));
+  // 1: the headers
+  ncclGroupStart();
+  if (me == 0)
+    for (int q = 0; q < nr; q++) ncclRecv(dhdr + 4 * q, 4, ncclDouble, q, R->comm, st);
+  ncclSend(dsend, 4, ncclDouble, 0, R->comm, st);
+  ncclResult_t rc = ncclGroupEnd();
+  if (rc != ncclSuccess) return ctx_fail(c, std::string("RCCL crc headers: ") + ncclGetErrorString(rc));
+  std::vector<size_t> off(nr + 1, 0);
+  if (me == 0) {
+    HIPCHK(c, hipMemcpyAsync(hhdr.data(), dhdr, hhdr.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    for (int q = 0; q < nr; q++) off[q + 1] = off[q] + (size_t)hhdr[4 * q + 1] * (size_t)hhdr[4 * q + 3];
+    HIPCHK(c, hipMalloc((void **)&dblk, (off[nr] + 1) * sizeof(double)));
+  }
+  // 2: the strips (a narrow tile may own none: then nothing travels)
+  ncclGroupStart();
+  if (me == 0)
+    for (int q = 0; q < nr; q++)
+      if (off[q + 1] > off[q]) ncclRecv(dblk + off[q], off[q + 1] - off[q], ncclDouble, q, R->comm, st);
+  if (nmine) ncclSend(dsend + 4, nmine, ncclDouble, 0, R->comm, st);
+  rc = ncclGroupEnd();
+  if (rc != ncclSuccess) return ctx_fail(c, std::string("RCCL crc strips: ") + ncclGetErrorString(rc));
+  double result = 0.;
+  if (me == 0) {
+    std::vector<double> blk(off[nr]);
+    HIPCHK(c, hipMemcpyAsync(blk.data(), dblk, blk.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    std::vector<unsigned> table((size_t)h.jtdm * ntot, 0u);          // [global row][global strip]
+    for (int q = 0; q < nr; q++) {
+      const int ql0 = (int)hhdr[4 * q], qns = (int)hhdr[4 * q + 1], qj0 = (int)hhdr[4 * q + 2], qjj = (int)hhdr[4 * q + 3];
+      for (int j = 0; j < qjj; j++)
+        for (int s = 0; s < qns; s++)
+          table[(size_t)(qj0 + j) * ntot + ql0 + s] = (unsigned)blk[off[q] + (size_t)j * qns + s];
+    }
+    std::vector<unsigned> rows(h.jtdm);
+    for (int j = 0; j < h.jtdm; j++) {
+      unsigned crc8 = 0;
+      for (int s = 0; s < ntot; s++) crc8 = host_crc_bytes((const unsigned char *)&table[(size_t)j * ntot + s], 4, crc8);
+      rows[j] = crc8;
+    }
+    result = host_crc_bytes((const unsigned char *)rows.data(), 4 * rows.size(), 0);
+    HIPCHK(c, hipMemcpyAsync(dres, &result, sizeof(double), hipMemcpyHostToDevice, st));
+  }
+  // 3: the result to every rank
+  ncclGroupStart();
+  if (me == 0)
+    for (int q = 0; q < nr; q++) ncclSend(dres, 1, ncclDouble, q, R->comm, st);
+  ncclRecv(dres + 1, 1, ncclDouble, 0, R->comm, st);
+  rc = ncclGroupEnd();
+  if (rc != ncclSuccess) return ctx_fail(c, std::string("RCCL crc result: ") + ncclGetErrorString(rc));
+  HIPCHK(c, hipMemcpyAsync(&result, dres + 1, sizeof(double), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  *crc = (unsigned)result;
   return 0;
 }
 int blomgpu_rccl_finalize(blomgpu_ctx *c) {

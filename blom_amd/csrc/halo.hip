@@ -647,7 +647,7 @@ __global__ void k_crc_strips(const DevView *__restrict__ Vp, const double *__res
   out[t] = crc8p;
 }
 
-static unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init) {
+unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init) {
   unsigned crc = ~init;
   for (size_t x = 0; x < n; x++) {
     unsigned k = (crc ^ p[x]) & 255u;

@@ -10,41 +10,97 @@
 !   record 1: idm jdm kdm ntr nreg nsteps  (int32 x6), baclin (real64)
 !   then per entry: name (16 chars), kind (int32: 0 real field, 1 int field, 2 real option,
 !                   3 int option, 4 string option), nlev (int32), payload
+!
+! As N ranks (INTEGRATION.md, "Running as N ranks"): every rank runs this program, as every rank of
+! the reference runs `program blom`.  The rank environment is torchrun's (RANK, WORLD_SIZE, LOCAL_RANK;
+! the device is LOCAL_RANK); a tile table `patch.input` in the working directory (read as xcspmd reads
+! it, mod_xcspmd_gpu) switches tiles on, a 1x1 table on one rank included.  Every rank reads the whole
+! state file and keeps its window; the RCCL id travels from rank 0 through the file $BLOM_RCCL_ID_FILE.
 ! ------------------------------------------------------------------------------
 program blom_dyncore
 
+  use iso_c_binding, only: c_char, c_int, c_null_char
   use mod_blomgpu
+  use mod_xcspmd_gpu, only: xcspmd_gpu
   use mod_rdlim_gpu, only: rdlim_gpu, hybrid_coordinate, advect_cppm
   implicit none
+
+  interface
+    integer(c_int) function c_rename(old, new) bind(C, name='rename')
+      import :: c_int, c_char
+      character(kind=c_char), intent(in) :: old(*), new(*)
+    end function
+    integer(c_int) function c_usleep(us) bind(C, name='usleep')
+      import :: c_int
+      integer(c_int), value :: us
+    end function
+    integer(c_int) function c_getppid() bind(C, name='getppid')
+      import :: c_int
+    end function
+  end interface
 
   character(len=256) :: fname
   character(len=16)  :: name
   character(len=32)  :: sval
+  character(len=512) :: idfile
+  character(kind=c_char) :: rccl_id(128)
   integer :: u, ios, kind, nlev, nsteps, nstep, nstep1, nstep2, i4(6), ival
+  integer :: rank, world, local_rank, npx, npy, px, py
   real(8) :: baclin, rval
-  logical :: have_limits, full_physics = .false.
+  logical :: have_limits, full_physics = .false., tiled, isint
+  integer, allocatable :: isizes(:), jsizes(:)
   real(8), allocatable :: buf(:,:,:)
   integer, allocatable :: ibuf(:,:,:)
 
+  rank = env_int('RANK', 0)
+  world = env_int('WORLD_SIZE', 1)
+  local_rank = env_int('LOCAL_RANK', 0)
+  if (world < 1 .or. rank < 0 .or. rank >= world) error stop '(blom_dyncore: RANK must lie in 0 .. WORLD_SIZE-1)'
   call get_command_argument(1, fname)
   if (len_trim(fname) == 0) fname = 'blom_state.bin'
   open (newunit=u, file=trim(fname), access='stream', form='unformatted', status='old', action='read')
   read (u) i4, baclin
   nsteps = i4(6)
-  call gpu_init(i4(1), i4(2), i4(3), i4(4), i4(5), 0)
+  ! xcspmd: the tile table decides the layout; everything is checked before any RCCL call, alike on every rank
+  inquire (file='patch.input', exist=tiled)
+  if (tiled) then
+    call xcspmd_gpu('patch.input', world, i4(1), i4(2), i4(5), nbdy, isizes, jsizes)
+    npx = size(isizes)
+    npy = size(jsizes)
+    px = mod(rank, npx)                            ! rank = px + npx*py (blomgpu_rccl_init_2d)
+    py = rank/npx
+    call gpu_init_tile(i4(1), i4(2), i4(3), i4(4), i4(5), sum(isizes(1:px)), sum(jsizes(1:py)), isizes(px+1), jsizes(py+1), &
+                       local_rank)
+    mnproc = rank+1
+    npes = world
+  else
+    if (world /= 1) then
+      write (*,'(a,i0,a)') ' blom_dyncore: WORLD_SIZE = ', world, ' but no patch.input in the working directory'
+      error stop '(xcspmd)'
+    end if
+    call gpu_init(i4(1), i4(2), i4(3), i4(4), i4(5), local_rank)
+  end if
+  ! each rank reads the whole state: a tile takes the window i0+1..i0+idm+2*nbdy, j0+1..j0+jdm+2*nbdy of every padded field
+  ! (its halo included, so that no halo update is needed before the first step; blom_amd/tiles.py: TileLayout.window); the
+  ! global context of the barotropic solve takes the whole masks and every real field of <= 3 levels it registers alike
   do
     read (u, iostat=ios) name, kind, nlev
     if (ios /= 0) exit
     select case (kind)
       case (0)
-        allocate (buf(idm+2*nbdy, jdm+2*nbdy, nlev))
+        allocate (buf(itdm+2*nbdy, jtdm+2*nbdy, nlev))
         read (u) buf
-        call gpu_upload(trim(name), buf, nlev)
+        call gpu_upload(trim(name), buf(i0+1:i0+idm+2*nbdy, j0+1:j0+jdm+2*nbdy, :), nlev)
+        if (tiled .and. nlev <= 3) then
+          if (gpu_nlev_global(trim(name), isint) == nlev .and. .not. isint) call gpu_upload_global(trim(name), buf, nlev)
+        end if
         deallocate (buf)
       case (1)
-        allocate (ibuf(idm+2*nbdy, jdm+2*nbdy, nlev))
+        allocate (ibuf(itdm+2*nbdy, jtdm+2*nbdy, nlev))
         read (u) ibuf
-        call gpu_upload_int(trim(name), ibuf, nlev)
+        call gpu_upload_int(trim(name), ibuf(i0+1:i0+idm+2*nbdy, j0+1:j0+jdm+2*nbdy, :), nlev)
+        if (tiled .and. (name == 'ip' .or. name == 'iu' .or. name == 'iv' .or. name == 'iq')) &
+          call gpu_upload_int_global(trim(name), ibuf, nlev)
         deallocate (ibuf)
       case (2)
         read (u) rval
@@ -71,6 +127,12 @@ program blom_dyncore
     read (sval, *) nsteps
     nstep2 = nstep1+nsteps
   end if
+  ! thermf's ocean area (mod_grid: area) is the option record of the state file: the whole domain's, the same on every rank
+  if (tiled) then
+    call share_rccl_id(rccl_id)
+    call gpu_rccl_init(rccl_id, rank, npx, npy)
+    call gpu_attach_barotp_global(isizes, jsizes)
+  end if
 
   ! the step counter starts at nstep1 = nday1*nstep_in_day (its parity decides the time levels and the order of cppm's sweeps)
   nstep = nstep1
@@ -85,16 +147,99 @@ program blom_dyncore
   end do
 
   call gpu_sync()
-  call gpu_chksum('dp', 2*kdm, 1, 'dp')          ! blom.F:56-57
+  ! collectives on tiles: every rank calls them, the first prints (blom.F:56-57)
+  call gpu_chksum('dp', 2*kdm, 1, 'dp')
   call gpu_chksum('temp', 2*kdm, 1, 'temp')
   call gpu_chksum('u', 2*kdm, 13, 'u')
   if (difest_estimates) call gpu_chksum('difint', kdm, 1, 'difint')     ! (the estimates ran: see mod_blomgpu)
-  open (newunit=u, file='run.status', status='unknown')
-  write (u,*) 'success'                          ! blom.F:59-61
-  close (u)
+  if (mnproc == 1) then
+    open (newunit=u, file='run.status', status='unknown')
+    write (u,*) 'success'                          ! blom.F:59-61
+    close (u)
+  end if
   call gpu_finalize()
+  if (tiled .and. world > 1 .and. rank == 0) then  ! every rank has read the id: the checksums needed all of them
+    open (newunit=u, file=trim(idfile), status='old', iostat=ios)
+    if (ios == 0) close (u, status='delete')
+  end if
 
 contains
+
+  integer function env_int(var, default)
+    character(len=*), intent(in) :: var
+    integer, intent(in) :: default
+    character(len=32) :: v
+    integer :: st
+    env_int = default
+    call get_environment_variable(var, v, status=st)
+    if (st /= 0 .or. len_trim(v) == 0) return
+    read (v, *, iostat=st) env_int
+    if (st /= 0) then
+      write (*,'(4a)') ' blom_dyncore: ', var, ' is not an integer: ', trim(v)
+      error stop '(blom_dyncore)'
+    end if
+  end function
+
+  ! The RCCL unique id, rank 0 -> every rank, without MPI: rank 0 writes the 128 bytes and a run token to $BLOM_RCCL_ID_FILE
+  ! (default ./blom_rccl_id) under a temporary name and renames it; the others wait for it (300 s at most) and take it only
+  ! when its token is theirs, so that a file an earlier run left behind is never joined.  The token is $BLOM_RUN_TOKEN, or
+  ! else the parent process and torchrun's restart count -- the ranks of one launch are children of one launcher.
+  subroutine share_rccl_id(id)
+    character(kind=c_char), intent(out) :: id(128)
+    character(len=128) :: token, got
+    character(len=32) :: v
+    integer :: f, st, waited
+    logical :: ex
+    call get_environment_variable('BLOM_RCCL_ID_FILE', idfile, status=st)
+    if (st /= 0 .or. len_trim(idfile) == 0) idfile = 'blom_rccl_id'
+    call get_environment_variable('BLOM_RUN_TOKEN', token, status=st)
+    if (st /= 0 .or. len_trim(token) == 0) then
+      call get_environment_variable('TORCHELASTIC_RESTART_COUNT', v, status=st)
+      if (st /= 0) v = '0'
+      write (token, '(a,i0,2a)') 'ppid ', c_getppid(), ' restart ', trim(v)
+    end if
+    if (world == 1) then
+      call gpu_rccl_unique_id(id)
+      return
+    end if
+    if (rank == 0) then
+      call gpu_rccl_unique_id(id)
+      open (newunit=f, file=trim(idfile)//'.tmp', access='stream', form='unformatted', status='replace', action='write', iostat=st)
+      if (st == 0) write (f, iostat=st) id, token
+      if (st == 0) close (f, iostat=st)
+      if (st /= 0) then
+        write (*,'(2a)') ' blom_dyncore: cannot write ', trim(idfile)//'.tmp'
+        error stop '(blom_dyncore)'
+      end if
+      if (c_rename(trim(idfile)//'.tmp'//c_null_char, trim(idfile)//c_null_char) /= 0) then
+        write (*,'(2a)') ' blom_dyncore: cannot rename the id file to ', trim(idfile)
+        error stop '(blom_dyncore)'
+      end if
+      return
+    end if
+    waited = 0
+    do
+      inquire (file=trim(idfile), exist=ex)
+      if (ex) then
+        open (newunit=f, file=trim(idfile), access='stream', form='unformatted', status='old', action='read', iostat=st)
+        if (st == 0) then
+          read (f, iostat=st) id, got
+          close (f)
+          if (st == 0 .and. got == token) return
+        end if
+      end if
+      if (waited >= 300000) then
+        if (ex) then
+          write (*,'(3a)') ' blom_dyncore: ', trim(idfile), ' is from another run (its token differs) and rank 0 wrote none in 300 s'
+        else
+          write (*,'(3a)') ' blom_dyncore: no RCCL id from rank 0 in ', trim(idfile), ' after 300 s'
+        end if
+        error stop '(blom_dyncore)'
+      end if
+      st = c_usleep(50000_c_int)
+      waited = waited+50
+    end do
+  end subroutine
 
   subroutine blom_step(nstep)
     ! stage sequence of phy/mod_blom_step.F90:89-253, dynamical core only

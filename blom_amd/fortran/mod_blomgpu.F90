@@ -9,6 +9,11 @@
 ! reference has no return codes (it prints and calls xchalt/xcstop, e.g.
 ! phy/mod_advect.F90:166-172); a non-zero C status is converted to that behaviour
 ! in gpu_check.
+!
+! One tile per process (gpu_init_tile): the tile's context, a second context of the
+! whole domain for the replicated barotropic solve, the RCCL transport between the
+! ranks and the checksum over all of them.  Module mod_xcspmd_gpu at the end of this
+! file reads and checks the reference's tile table patch.input (xcspmd).
 ! ------------------------------------------------------------------------------
 module mod_blomgpu
 
@@ -21,7 +26,11 @@ module mod_blomgpu
 
   integer, parameter, public :: nbdy = 4          ! phy/mod_xc.F90:45
   type(c_ptr), save :: ctx = c_null_ptr
-  integer, public :: idm, jdm, kdm, ntr, nreg
+  type(c_ptr), save :: gctx = c_null_ptr          ! whole domain, for the replicated barotropic solve (tiles only)
+  logical, save :: on_rccl = .false.
+  integer, public :: idm, jdm, kdm, ntr, nreg     ! idm, jdm: this tile's extents
+  ! the tile's place in the global itdm x jtdm grid (phy/mod_xc.F90: i0, j0, mnproc counts from 1, npes ranks)
+  integer, public :: itdm, jtdm, i0 = 0, j0 = 0, mnproc = 1, npes = 1
 
   type, bind(C) :: blomgpu_dims
     integer(c_int) :: idm, jdm, kdm, nbdy, itdm, jtdm, i0, j0, nreg, ntr, device
@@ -126,8 +135,36 @@ module mod_blomgpu
       real(c_double), intent(in) :: v(*)
       integer(c_int), value :: nv
     end function
+    integer(c_int) function blomgpu_rccl_unique_id(id128) bind(C, name='blomgpu_rccl_unique_id')
+      import :: c_int, c_char
+      character(kind=c_char) :: id128(128)
+    end function
+    integer(c_int) function blomgpu_rccl_init_2d(c, id128, rank, npx, npy) bind(C, name='blomgpu_rccl_init_2d')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: id128(128)
+      integer(c_int), value :: rank, npx, npy
+    end function
+    integer(c_int) function blomgpu_rccl_attach_barotp_global(c, g, isizes, jsizes) bind(C, name='blomgpu_rccl_attach_barotp_global')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, g
+      integer(c_int), intent(in) :: isizes(*), jsizes(*)
+    end function
+    integer(c_int) function blomgpu_rccl_finalize(c) bind(C, name='blomgpu_rccl_finalize')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_rccl_crc(c, name, lev0, nlev, itype, crc) bind(C, name='blomgpu_rccl_crc')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: name(*)
+      integer(c_int), value :: lev0, nlev, itype
+      integer(c_int), intent(out) :: crc
+    end function
   end interface
 
+  public :: gpu_init_tile, gpu_upload_global, gpu_upload_int_global, gpu_nlev_global, gpu_rccl_unique_id, gpu_rccl_init, &
+            gpu_attach_barotp_global
   public :: gpu_init, gpu_finalize, gpu_set, gpu_upload, gpu_upload_int, gpu_download, gpu_nlev, &
             gpu_halo, gpu_chksum, gpu_sync, gpu_xcsum, budget_sums, gpu_budget
   public :: stage6
@@ -149,14 +186,21 @@ contains
   end function
 
   subroutine gpu_check(rc, where)
+    integer(c_int), intent(in) :: rc
+    character(len=*), intent(in) :: where
+    call gpu_check_on(ctx, rc, where)
+  end subroutine
+
+  subroutine gpu_check_on(c, rc, where)
     ! the reference prints to lp and calls xchalt + stop '(name)' (phy/mod_xc.F90:516)
+    type(c_ptr), intent(in) :: c
     integer(c_int), intent(in) :: rc
     character(len=*), intent(in) :: where
     character(kind=c_char), pointer :: msg(:)
     type(c_ptr) :: p
     integer :: i
     if (rc == 0) return
-    p = blomgpu_last_error(ctx)
+    p = blomgpu_last_error(c)
     call c_f_pointer(p, msg, [512])
     i = 1
     do while (i < 512 .and. msg(i) /= c_null_char)
@@ -172,12 +216,55 @@ contains
     integer, intent(in) :: idm_, jdm_, kdm_, ntr_, nreg_, device
     type(blomgpu_dims) :: d
     idm = idm_; jdm = jdm_; kdm = kdm_; ntr = ntr_; nreg = nreg_
+    itdm = idm; jtdm = jdm; i0 = 0; j0 = 0
     d = blomgpu_dims(idm, jdm, kdm, nbdy, idm, jdm, 0, 0, nreg, ntr, device)
     call gpu_check(blomgpu_create(d, ctx), 'gpu_init')
   end subroutine
 
+  ! One tile of the itdm_ x jtdm_ grid (xcspmd, phy/mod_xc.F90:1332-2027): this process owns the points i0_+1..i0_+ii,
+  ! j0_+1..j0_+jj.  idm, jdm become the tile's extents, so that gpu_upload / gpu_download keep the reference's tile-local
+  ! shape a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,:).  Also creates the second context of the whole domain that the replicated
+  ! barotropic solve runs on: itdm_ x jtdm_, kdm = 3 (2-D fields only), no tracers (blom_amd/tiles.py: make_barotp_global).
+  subroutine gpu_init_tile(itdm_, jtdm_, kdm_, ntr_, nreg_, i0_, j0_, ii, jj, device)
+    integer, intent(in) :: itdm_, jtdm_, kdm_, ntr_, nreg_, i0_, j0_, ii, jj, device
+    type(blomgpu_dims) :: d
+    integer(c_int) :: rc
+    idm = ii; jdm = jj; kdm = kdm_; ntr = ntr_; nreg = nreg_
+    itdm = itdm_; jtdm = jtdm_; i0 = i0_; j0 = j0_
+    d = blomgpu_dims(idm, jdm, kdm, nbdy, itdm, jtdm, i0, j0, nreg, ntr, device)
+    call gpu_check(blomgpu_create(d, ctx), 'gpu_init_tile')
+    d = blomgpu_dims(itdm, jtdm, 3, nbdy, itdm, jtdm, 0, 0, nreg, 0, device)
+    rc = blomgpu_create(d, gctx)
+    call gpu_check_on(gctx, rc, 'gpu_init_tile (global context)')
+  end subroutine
+
+  ! 128-byte RCCL unique id (rank 0 creates it, the launcher hands it to the others)
+  subroutine gpu_rccl_unique_id(id)
+    character(kind=c_char), intent(out) :: id(128)
+    if (blomgpu_rccl_unique_id(id) /= 0) error stop '(gpu_rccl_unique_id: ncclGetUniqueId failed)'
+  end subroutine
+
+  ! join the communicator as tile (px, py) = (mod(rank,npx), rank/npx) of the npx x npy grid
+  subroutine gpu_rccl_init(id, rank, npx, npy)
+    character(kind=c_char), intent(in) :: id(128)
+    integer, intent(in) :: rank, npx, npy
+    call gpu_check(blomgpu_rccl_init_2d(ctx, id, rank, npx, npy), 'gpu_rccl_init')
+    on_rccl = .true.
+  end subroutine
+
+  ! from now on barotp (and thermf's global sums) run on the global context; isizes / jsizes: the tile columns' widths and
+  ! the tile rows' heights
+  subroutine gpu_attach_barotp_global(isizes, jsizes)
+    integer, intent(in) :: isizes(:), jsizes(:)
+    call gpu_check(blomgpu_rccl_attach_barotp_global(ctx, gctx, isizes, jsizes), 'gpu_attach_barotp_global')
+  end subroutine
+
   subroutine gpu_finalize()
     integer(c_int) :: rc
+    if (on_rccl) rc = blomgpu_rccl_finalize(ctx)
+    on_rccl = .false.
+    if (c_associated(gctx)) rc = blomgpu_destroy(gctx)    ! first: it runs on the tile's stream
+    gctx = c_null_ptr
     rc = blomgpu_destroy(ctx)
     ctx = c_null_ptr
   end subroutine
@@ -207,6 +294,30 @@ contains
     isint = ii_ /= 0
   end function
 
+  ! the global context: levels of a field, 0 when it does not register `name`
+  integer function gpu_nlev_global(name, isint)
+    character(len=*), intent(in) :: name
+    logical, intent(out) :: isint
+    integer(c_int) :: nl, ii_
+    gpu_nlev_global = 0
+    isint = .false.
+    if (blomgpu_field_info(gctx, cz(name), nl, ii_) /= 0) return
+    gpu_nlev_global = nl
+    isint = ii_ /= 0
+  end function
+  subroutine gpu_upload_global(name, a, nlev)
+    character(len=*), intent(in) :: name
+    integer, intent(in) :: nlev
+    real(8), intent(in) :: a(1-nbdy:itdm+nbdy,1-nbdy:jtdm+nbdy,nlev)
+    call gpu_check_on(gctx, blomgpu_upload(gctx, cz(name), a, nlev), 'gpu_upload_global')
+  end subroutine
+  subroutine gpu_upload_int_global(name, a, nlev)
+    character(len=*), intent(in) :: name
+    integer, intent(in) :: nlev
+    integer, intent(in) :: a(1-nbdy:itdm+nbdy,1-nbdy:jtdm+nbdy,nlev)
+    call gpu_check_on(gctx, blomgpu_upload(gctx, cz(name), a, nlev), 'gpu_upload_int_global')
+  end subroutine
+
   ! a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,nlev): the reference's module-array layout
   subroutine gpu_upload(name, a, nlev)
     character(len=*), intent(in) :: name
@@ -234,13 +345,18 @@ contains
     call gpu_check(blomgpu_xctilr(ctx, cz(name), lev0, l1, ld, mh, nh, itype), 'xctilr')
   end subroutine
 
-  ! chksum(a, kcsd, itype, text), phy/mod_checksum.F90:41-74
+  ! chksum(a, kcsd, itype, text), phy/mod_checksum.F90:41-74; on RCCL tiles a collective (every rank calls it) that gives
+  ! the whole domain's xccrc (phy/mod_xc.F90:2195-2322), printed by the first rank only
   subroutine gpu_chksum(name, kcsd, itype, text)
     character(len=*), intent(in) :: name, text
     integer, intent(in) :: kcsd, itype
     integer(c_int) :: crc
-    call gpu_check(blomgpu_crc(ctx, cz(name), 1, kcsd, itype, crc), 'chksum')
-    write (*,'(3a,z8.8)') ' chksum: ', trim(text), ': 0x', crc
+    if (on_rccl) then
+      call gpu_check(blomgpu_rccl_crc(ctx, cz(name), 1, kcsd, itype, crc), 'chksum')
+    else
+      call gpu_check(blomgpu_crc(ctx, cz(name), 1, kcsd, itype, crc), 'chksum')
+    end if
+    if (mnproc == 1) write (*,'(3a,z8.8)') ' chksum: ', trim(text), ': 0x', crc
   end subroutine
 
   subroutine gpu_xcsum(s, name, lev, itype)    ! phy/mod_xc.F90:4116 xcsum(sum, a, mask) on a device field
@@ -401,3 +517,126 @@ contains
   end subroutine
 
 end module mod_blomgpu
+
+! ------------------------------------------------------------------------------
+! mod_xcspmd_gpu -- the tile table of the reference, patch.input, as xcspmd reads
+! and checks it (phy/mod_xc.F90:1332-1540; format in the comment block :1405-1430):
+!
+!   npes   npe   mpe   idm   jdm  ibig  jbig  nreg ...
+!      8     4     2   180   193    45    97     2 ...
+!   ispt(  1) =      1    46    91   136          (first i-point of every tile of tile row 1)
+!   iipe(  1) =     45    45    45    45          (their i-extents)
+!   ...                                           (one ispt/iipe pair per tile row, mpe rows)
+!   jspt(  1) =      1    98                      (first j-point of every tile row)
+!   jjpe(  1) =     97    96                      (their j-extents)
+!
+! Only tensor-product layouts are carried (every tile row cut alike, no empty
+! tiles): land-tile elimination is not supported (blom_amd/tiles.py says the same).
+! A layout that does not fit is refused with the reason, before any RCCL call, and
+! every rank refuses it alike -- no rank is left waiting for a peer.
+! ------------------------------------------------------------------------------
+module mod_xcspmd_gpu
+
+  implicit none
+  private
+  public :: xcspmd_gpu
+
+contains
+
+  subroutine refuse(msg)
+    character(len=*), intent(in) :: msg
+    write (*,'(a)') ' xcspmd: '//trim(msg)
+    error stop '(xcspmd)'
+  end subroutine
+
+  ! reads `fname` and checks it against the rank count and the state's dimensions; isizes(npe) / jsizes(mpe): the widths
+  ! of the tile columns and the heights of the tile rows
+  subroutine xcspmd_gpu(fname, world, idm, jdm, nreg, nbdy, isizes, jsizes)
+    character(len=*), intent(in) :: fname
+    integer, intent(in) :: world, idm, jdm, nreg, nbdy
+    integer, allocatable, intent(out) :: isizes(:), jsizes(:)
+    integer, allocatable :: ispt(:,:), iipe(:,:), jspt(:), jjpe(:)
+    logical, allocatable :: seen(:,:)
+    character(len=1024) :: line
+    character(len=160) :: msg
+    character(len=4) :: key
+    integer :: u, ios, npes, npe, mpe, pidm, pjdm, ibig, jbig, pnreg, n, m, k, p, q
+    open (newunit=u, file=fname, status='old', action='read', iostat=ios)
+    if (ios /= 0) call refuse('cannot open '//trim(fname))
+    read (u, '(a)', iostat=ios) line                    ! the column names
+    read (u, *, iostat=ios) npes, npe, mpe, pidm, pjdm, ibig, jbig, pnreg
+    if (ios /= 0) call refuse(trim(fname)//': the second line must hold npes npe mpe idm jdm ibig jbig nreg')
+    write (msg, '(a,i0,a,i0)') 'patch.input is for npes = ', npes, ' ranks but WORLD_SIZE = ', world
+    if (npes /= world) call refuse(msg)
+    write (msg, '(a,i0,a,i0,a,i0)') 'npe x mpe = ', npe, ' x ', mpe, ' is not npes = ', npes
+    if (npe < 1 .or. mpe < 1 .or. npe*mpe /= npes) call refuse(msg)
+    allocate (ispt(npe,mpe), iipe(npe,mpe), jspt(mpe), jjpe(mpe), seen(2,mpe+1))
+    seen = .false.
+    do
+      read (u, '(a)', iostat=ios) line
+      if (ios /= 0) exit
+      line = adjustl(line)
+      if (len_trim(line) == 0) cycle
+      key = line(1:4)
+      p = index(line, '(')
+      q = index(line, ')')
+      k = index(line, '=')
+      if (p /= 5 .or. q < p .or. k < q) call refuse(trim(fname)//': cannot read the line "'//trim(line)//'"')
+      read (line(p+1:q-1), *, iostat=ios) n
+      if (ios /= 0) call refuse(trim(fname)//': cannot read the line "'//trim(line)//'"')
+      select case (key)
+        case ('ispt', 'iipe')
+          if (n < 1 .or. n > mpe) call refuse(trim(fname)//': tile row out of range in "'//trim(line)//'"')
+          if (key == 'ispt') then
+            read (line(k+1:), *, iostat=ios) ispt(:,n)
+          else
+            read (line(k+1:), *, iostat=ios) iipe(:,n)
+          end if
+          seen(merge(1, 2, key == 'ispt'), n) = ios == 0
+        case ('jspt', 'jjpe')
+          if (n /= 1) call refuse(trim(fname)//': only jspt(1) / jjpe(1) are read')
+          if (key == 'jspt') then
+            read (line(k+1:), *, iostat=ios) jspt
+          else
+            read (line(k+1:), *, iostat=ios) jjpe
+          end if
+          seen(merge(1, 2, key == 'jspt'), mpe+1) = ios == 0
+        case default
+          call refuse(trim(fname)//': unexpected line "'//trim(line)//'"')
+      end select
+      if (ios /= 0) call refuse(trim(fname)//': too few values in "'//trim(line)//'"')
+    end do
+    close (u)
+    if (.not. all(seen)) call refuse(trim(fname)//': an ispt/iipe line of a tile row or jspt/jjpe is missing')
+
+    if (any(iipe <= 0) .or. any(jjpe <= 0)) &
+      call refuse('empty tile (iipe or jjpe = 0): land-tile elimination is not supported')
+    do n = 2, mpe
+      if (any(iipe(:,n) /= iipe(:,1)) .or. any(ispt(:,n) /= ispt(:,1))) &
+        call refuse('the tile rows are cut differently (land-tile elimination / a non-tensor-product layout is not supported)')
+    end do
+    do m = 1, npe
+      if (ispt(m,1) /= 1+sum(iipe(1:m-1,1))) call refuse('decomposition is non-contiguous (ispt)')
+    end do
+    do n = 1, mpe
+      if (jspt(n) /= 1+sum(jjpe(1:n-1))) call refuse('decomposition is non-contiguous (jspt)')
+    end do
+    write (msg, '(a,i0,a,i0,a,i0,a,i0)') 'the tiles cover ', sum(iipe(:,1)), ' x ', sum(jjpe), &
+                                        ' points but the state is idm x jdm = ', idm, ' x ', jdm
+    if (sum(iipe(:,1)) /= idm .or. sum(jjpe) /= jdm) call refuse(msg)
+    write (msg, '(a,i0,a,i0,a,i0,a,i0)') 'patch.input has idm x jdm = ', pidm, ' x ', pjdm, ' but the state is ', idm, ' x ', jdm
+    if (pidm /= idm .or. pjdm /= jdm) call refuse(msg)
+    write (msg, '(a,i0,a,i0)') 'patch.input has nreg = ', pnreg, ' but the state has nreg = ', nreg
+    if (pnreg /= nreg) call refuse(msg)
+    ! arctic patch: every tile of the top row as wide as itdm/ipr (:1483-1505)
+    if (nreg == 2 .and. npe > 1) then
+      write (msg, '(a,i0)') 'arctic tiles are not the right size: they should have ii = itdm/npe = ', idm/npe
+      if (any(iipe(:,mpe) /= idm/npe) .or. mod(idm, npe) /= 0) call refuse(msg)
+    end if
+    write (msg, '(a,i0,a)') 'a tile is narrower than nbdy = ', nbdy, ' points'
+    if (any(iipe < nbdy) .or. any(jjpe < nbdy)) call refuse(msg)
+    isizes = iipe(:,1)
+    jsizes = jjpe
+  end subroutine
+
+end module mod_xcspmd_gpu

@@ -226,6 +226,13 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_rccl_attach_barotp_global(self.ctx, glob.ctx, a, b))
         self._bt_global = glob               # keep it alive as long as the tile
 
+    def rccl_crc(self, name, lev0, nlev, itype=1):
+        """xccrc of the whole decomposed domain over the RCCL ranks (a collective: every rank calls it, every rank gets the
+        value); on a context without RCCL, crc()"""
+        v = C.c_uint(0)
+        self._chk(self.lib.blomgpu_rccl_crc(self.ctx, name.encode(), lev0, nlev, itype, C.byref(v)))
+        return v.value
+
     def rccl_force_ns_exchange(self, on=True):
         self._chk(self.lib.blomgpu_rccl_force_ns_exchange(self.ctx, int(on)))
 

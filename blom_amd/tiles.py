@@ -69,6 +69,21 @@ class TileLayout:
             raise ValueError(f"{path}: tile rows are cut differently (land-tile elimination); not a tensor-product layout")
         return cls(ii[0], jj[0])
 
+    def write_patch_input(self, path, nreg):
+        """this layout as a reference patch.input file (the format xcspmd reads, phy/mod_xc.F90:1405-1430): the header line
+        npes npe mpe idm jdm ibig jbig nreg, then ispt / iipe of every tile row (all alike here), then jspt / jjpe"""
+        ispt = [1 + sum(self.isizes[:k]) for k in range(self.npx)]
+        jspt = [1 + sum(self.jsizes[:k]) for k in range(self.npy)]
+        head = (self.npx * self.npy, self.npx, self.npy, self.itdm, self.jtdm, max(self.isizes), max(self.jsizes), nreg)
+        lines = ["".join(f"{h:>6}" for h in ("npes", "npe", "mpe", "idm", "jdm", "ibig", "jbig", "nreg")),
+                 "".join(f"{int(v):6d}" for v in head), ""]
+        for n in range(self.npy):
+            lines.append(f"ispt({n + 1:3d}) = " + "".join(f"{v:6d}" for v in ispt))
+            lines.append(f"iipe({n + 1:3d}) = " + "".join(f"{int(v):6d}" for v in self.isizes))
+        lines += ["", "jspt(  1) = " + "".join(f"{v:6d}" for v in jspt), "jjpe(  1) = " + "".join(f"{int(v):6d}" for v in self.jsizes)]
+        with open(path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
 
 def tile_extents(case, npx, npy):
     assert case.idm % npx == 0 and case.jdm % npy == 0, "uniform tiles only"

@@ -218,6 +218,11 @@ int  blomgpu_rccl_force_ns_exchange(blomgpu_ctx *, int on);   /* test hook, see 
  * are the widths / heights of the tile columns / rows.  From then on blomgpu_barotp of the tile gathers the 2-D fields
  * the solver reads (one grouped exchange), solves on `global`, and takes its window of the results. */
 int  blomgpu_rccl_attach_barotp_global(blomgpu_ctx *tile, blomgpu_ctx *global, const int *isizes, const int *jsizes);
+/* xccrc of the whole decomposed domain (phy/mod_xc.F90:2195-2322, chksum phy/mod_checksum.F90:41-74) over the RCCL ranks: a
+ * collective -- every rank calls it with the same arguments and every rank gets the same value, the single tile's checksum of
+ * the whole itdm x jtdm domain.  Each tile's strips (blomgpu_crc_strips) travel to rank 0, which chains them in global order and
+ * sends the result back.  On a context without RCCL it is blomgpu_crc. */
+int  blomgpu_rccl_crc(blomgpu_ctx *, const char *name, int lev0, int nlev, int itype, unsigned *crc);
 int  blomgpu_rccl_finalize(blomgpu_ctx *);
 typedef struct TileGroup blomgpu_group;
 int  blomgpu_group_create(int npx, int npy, blomgpu_group **out);
