@@ -18,10 +18,15 @@ same for every N at equal --steps/--warmup.  --scaling weak keeps round 1's mode
 N times as long, one 208x512 tile per GPU).  Launched without torchrun (`python bench.py --gpus N`),
 the script starts the N ranks itself.
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel, algorithmic bytes /
-HIP-event duration vs 8 TB/s), `step_roofline` (SURVEY.md 8d A_step / step time), `stages`
-(ms per stage) and `cpu_baseline` (the reference's own compiled Fortran, or the C restatement,
-timed on a bounded number of steps on the host cores).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps, writes --dump-outputs
+and prints the headline (`value`, `ms_per_step`, ...) and nothing else.  With --full the run goes on
+after the timed steps with the measurements and checks that take runs of their own: `ms_per_step_median`
+over more blocks, `roofline` (dominant kernel, algorithmic bytes / HIP-event duration vs 8 TB/s),
+`step_roofline` (SURVEY.md 8d A_step / step time), `stages_ms` (ms per stage), the state's checksum,
+`spunup`, `dyncore_only` and `cpu_baseline` (the reference's own compiled Fortran, or the C restatement,
+timed on a bounded number of steps on the host cores).  --blocks, --spunup-steps, --no-cpu-baseline and
+--no-dyncore-compare shape what --full adds; a command line that names one of them runs it as if --full
+were given.
 """
 import argparse
 import json
@@ -449,6 +454,17 @@ def bench_hor3map(args):
     g.sync()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    out = {"metric": "hor3map PPM six-call sequences of a 106080 x 53 slab per second", "value": args.steps / dt,
+           "unit": "slab-sequences/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f64", "data": "synthetic",
+           "config": {"workload": "mod_hor3map API (phy/mod_hor3map.F90:3834-4559), PPM / non-oscillatory posdef limiting / boundary "
+                                  "orders 6, 4: prepare_reconstruction, reconstruct, extract_polycoeff, regrid (method 1, the default BLOM's ale_regrid_remap calls), "
+                                  "prepare_remapping, remap on 106080 columns x 53 layers (tests/h3m_cases.py: make_slab)"}}
+    if not args.full:
+        g.free()
+        print(json.dumps(out))
+        return
     kms = {}
     for nm, f, _ in calls:                     # per-kernel HIP-event times (the library's own events), median of 9
         v = []
@@ -459,20 +475,13 @@ def bench_hor3map(args):
         kms[nm] = float(np.median(v))
     dom = max(kms, key=kms.get)
     alg = {nm: nf * F for nm, _, nf in calls}
-    out = {"metric": "hor3map PPM six-call sequences of a 106080 x 53 slab per second", "value": args.steps / dt,
-           "unit": "slab-sequences/sec", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-           "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f64", "data": "synthetic",
-           "config": {"workload": "mod_hor3map API (phy/mod_hor3map.F90:3834-4559), PPM / non-oscillatory posdef limiting / boundary "
-                                  "orders 6, 4: prepare_reconstruction, reconstruct, extract_polycoeff, regrid (method 1, the default BLOM's ale_regrid_remap calls), "
-                                  "prepare_remapping, remap on 106080 columns x 53 layers (tests/h3m_cases.py: make_slab)"},
-           "roofline": {"bound": "hbm", "kernel": dom, "achieved": alg[dom] / (kms[dom] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+    out.update({"roofline": {"bound": "hbm", "kernel": dom, "achieved": alg[dom] / (kms[dom] * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
                         "unit": "GB/s", "frac": alg[dom] / (kms[dom] * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None,
                         "algorithmic_bytes": alg[dom], "avg_ms": kms[dom],
                         "note": "caller-visible arrays in + out; the kernels also move their work planes (DESIGN.md 3g: counted "
                                 "0.4-0.9 GB per kernel before the store cuts) -- with every walk's loads issued ahead they run at "
                                 "4-5 TB/s of counted traffic"},
-           "kernels_ms": {k: round(v, 4) for k, v in kms.items()}}
+           "kernels_ms": {k: round(v, 4) for k, v in kms.items()}})
     if not args.no_cpu_baseline and hc.have_ref():
         m = 6000
         t0 = time.perf_counter()
@@ -688,6 +697,18 @@ def bench_hybrid_step(args):
         assert gpu.lib.blomgpu_dbg_kprof(gpu.ctx, buf, nw) == 0
         np.save(prof_file, np.frombuffer(buf, dtype=np.int64).reshape(-1, 6).copy())
     dt = (time.perf_counter() - t0) / args.steps
+    baclin = case.params["baclin"]
+    out = {"metric": "simulated-days/sec", "value": baclin / 86400.0 / dt, "unit": "simulated-days/sec", "n_gpus": 1, "steps": args.steps,
+           "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f64", "data": "synthetic",
+           "config": {"workload": f"channel {case.idm}x{case.jdm}x{kk}, ntr={case.ntr}: the step of vcoord_type = cntiso_hybrid as far as built "
+                                  f"(ltedtp = '{args.ltedtp}'; ale_regrid_remap nudge/ppm 6/4" + (" with neutral diffusion" if neutral else "") + ", cmnfld2, eddtra_ale gm+fox08, advect remap, pbcor1, diffus, pgforc, momtum, cmnfld_bfsqi_ale, ale_forcing, "
+                                  "ale_vdifft, ale_vdiffm, barotp, pbcor2, tmsmt2, cmnfld1); diffusivities, non-local fractions, boundary layer depth, surface fluxes constant",
+                      "parity": "cross-checked stage sequence, also at this size (tests/test_xcheck_hybrid_step.py)"}}
+    if not args.full:
+        gpu.close()
+        print(json.dumps(out))
+        return
     # per-class HIP-event times over a few more steps
     gpu.set("timing", 1)
     gpu.timer_reset()
@@ -702,8 +723,7 @@ def bench_hybrid_step(args):
     gpu_timers = {kn: gpu.timer_get(kn) for kn in ("k_ndiff_prep", "k_ndiff_flux", "k_ndiff_eval", "k_ndiff_uvflx", "k_ndiff_apply")}
     gpu.set("timing", 0)
     u = gpu.get("u")[:, 4:-4, 4:-4]
-    finite = bool(np.isfinite(u[np.broadcast_to((masks["iu"][4:-4, 4:-4] > 0)[None], u.shape)]).all())
-    baclin = case.params["baclin"]
+    out["config"]["state_finite"] = bool(np.isfinite(u[np.broadcast_to((masks["iu"][4:-4, 4:-4] > 0)[None], u.shape)]).all())
     ntr = case.ntr
     F = case.idm * case.jdm * kk * 8.0
     # algorithmic bytes per class in units of F (every distinct 3-D array read or written once): the classes of the isopycnic step as
@@ -730,20 +750,14 @@ def bench_hybrid_step(args):
     dom = max(hbm, key=hbm.get)
     ach = cb[dom] * F / (live[dom] * 1e-3) / 1e9
     tot = sum(cb[k] for k in hbm) * F
-    out = {"metric": "simulated-days/sec", "value": baclin / 86400.0 / dt, "unit": "simulated-days/sec", "n_gpus": 1, "steps": args.steps,
-           "warmup": args.warmup, "ms_per_step": dt * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-           "dtype": "f64", "data": "synthetic",
-           "config": {"workload": f"channel {case.idm}x{case.jdm}x{kk}, ntr={case.ntr}: the step of vcoord_type = cntiso_hybrid as far as built "
-                                  f"(ltedtp = '{args.ltedtp}'; ale_regrid_remap nudge/ppm 6/4" + (" with neutral diffusion" if neutral else "") + ", cmnfld2, eddtra_ale gm+fox08, advect remap, pbcor1, diffus, pgforc, momtum, cmnfld_bfsqi_ale, ale_forcing, "
-                                  "ale_vdifft, ale_vdiffm, barotp, pbcor2, tmsmt2, cmnfld1); diffusivities, non-local fractions, boundary layer depth, surface fluxes constant",
-                      "parity": "cross-checked stage sequence, also at this size (tests/test_xcheck_hybrid_step.py)", "state_finite": finite},
+    out.update({
            "roofline": {"bound": "hbm", "kernel": dom, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
                         "traffic": None, "algorithmic_bytes": cb[dom] * F, "avg_ms": live[dom],
                         "note": "stage class (its kernels are launched back to back); HIP events on the library's stream" +
                                 ("; with ltedtp = 'neutral' the class contains the neutral diffusion, whose searches are bound by instruction issue and "
                                  "load latency, not by bytes (DESIGN.md 3j): its kernels run on a stream of their own beside the remapping" if neutral else ""),
                         "step_hbm_frac": tot / dt / 1e9 / HBM_PEAK_GBS},
-           "stages_ms": live}
+           "stages_ms": live})
     if nd_k:
         out["ndiff_kernels_ms"] = nd_k
     gpu.close()
@@ -795,13 +809,18 @@ def main():
     ap.add_argument("--spinup", type=int, default=0,
                     help="steps integrated before the warm-up (default 0: the timed window starts from rest, steps W+1..W+K); with N > 0 the "
                          "CPU baseline starts from the state the device holds at the end of the run, downloaded")
-    ap.add_argument("--blocks", type=int, default=5,
-                    help="the timed region is block 1 (the headline: `value`, `ms_per_step`); blocks 2..B of --steps steps each follow and "
-                         "ms_per_step_median / _min / _max over all B blocks are reported beside it")
-    ap.add_argument("--spunup-steps", type=int, default=1000,
-                    help="one tile, --physics full: after the measurement the run is continued to this step count and --steps steps are "
-                         "timed again (key `spunup`: a state a model run is in, not the transient from rest); 0: leave it out")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: more timed blocks, HIP-event "
+                         "times per stage class and kernel (stages_ms, roofline), the state's checksum, the spun-up state, the dynamical "
+                         "core alone and the CPU baseline; without it the run prints the headline only.  The four options below shape "
+                         "these measurements, and naming one of them asks for them as --full does")
+    ap.add_argument("--blocks", type=int, default=None,
+                    help="(default 5) the timed region is block 1 (the headline: `value`, `ms_per_step`); blocks 2..B of --steps steps each follow "
+                         "and ms_per_step_median / _min / _max over all B blocks are reported beside it")
+    ap.add_argument("--spunup-steps", type=int, default=None,
+                    help="(default 1000) one tile, --physics full: after the measurement the run is continued to this step count and --steps "
+                         "steps are timed again (key `spunup`: a state a model run is in, not the transient from rest); 0: leave it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="leave out the CPU baseline")
     ap.add_argument("--no-dyncore-compare", action="store_true",
                     help="leave out the extra steps of the dynamical core alone that follow the measurement (profiling runs)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=INT",
@@ -823,6 +842,11 @@ def main():
                     help="after the timed steps, write the state they left (DUMP_FIELDS, float64; a fixed seeded sample of each "
                          "large field) as DIR/<name>.npy, for comparing the outputs of two builds; one tile on one GPU only")
     args = ap.parse_args()
+    # a command line that shapes the measurements after the timed steps asks for them (so do the ones written before --full existed)
+    if args.blocks is not None or args.spunup_steps is not None or args.no_cpu_baseline or args.no_dyncore_compare:
+        args.full = True
+    args.blocks = 5 if args.blocks is None else args.blocks
+    args.spunup_steps = 1000 if args.spunup_steps is None else args.spunup_steps
     if args.dump_outputs and (args.gpus != 1 or args.tiles or args.config in ("hor3map", "ale", "hybrid")):
         raise SystemExit("bench.py: --dump-outputs writes the state of one tile on one GPU (--gpus 1, no --tiles, not hor3map/ale/hybrid)")
     if args.config == "hor3map":
@@ -987,7 +1011,56 @@ def main():
     if args.dump_outputs:
         dump_outputs(gpu, args.dump_outputs)          # the state the last timed step left, before any further step
 
-    # ---- dominant kernel class, timed with HIP events on the library's stream over K more steps
+    def finish():
+        if world > 1 or args.rccl_self or layout is not None:
+            gpu.rccl_finalize()
+        gpu.close()
+        if world > 1:
+            torch.distributed.destroy_process_group()
+
+    ms_per_step = dt / args.steps * 1e3
+    # model days per wall second of the domain that is integrated (for --scaling weak that domain is N times as long:
+    # tile_days_per_s = N x value is reported beside it, not as the value)
+    value = args.steps * baclin / 86400.0 / dt
+    out = {
+        "metric": "simulated-days/sec", "value": value, "unit": "simulated-days/sec", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
+        "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": (f"{args.config} {case.idm}x{case.jdm}x{case.kdm} as {world} tiles ({layout.npx}x{layout.npy}: columns "
+                                f"{'/'.join(map(str, layout.isizes))}, rows {'/'.join(map(str, layout.jsizes))}), 1 tile per GPU, "
+                                if layout is not None else
+                                f"{args.config} {case.idm * world}x{case.jdm}x{case.kdm} as {world} tile(s) of "
+                                f"{case.idm}x{case.jdm}x{case.kdm} along i, 1 tile per GPU, ") +
+                               f"isopyc_bulkml/{args.advmth}/geopotential/uc/enscon, ntr={case.ntr} "
+                               f"({'TKE, length-scale slot, ideal age: the reference default build' if case.ntr == 3 else 'ideal age' if case.ntr == 1 else f'the default three + {case.ntr - 3} passive tracers'}), "
+                               f"baclin={baclin:g}s batrop={case.params['batrop']:g}s lstep={case.params['lstep']}; " +
+                               (f"config 2's step (phy/mod_blom_step.F90:96-253: init_fluxes, tmsmt1, cmnfld2, difest_isobml "
+                                f"[{'the whole routine: diffusivities estimated every step (NorESM defaults incl. rhsctp; the topographic beta is a synthetic field)' if difest_live else 'halos, pressure, ustar3, niw_ke_tendency; diffusivities frozen'}], eddtra, advect, pbcor1, "
+                                f"diffus, pgforc, momtum, convec, diapfl, thermf, mxlayr, updtrc, barotp, pbcor2, tmsmt2, cmnfld1), the channel "
+                                f"experiment's own forcing (zero fluxes, ustarw = 0.005 m/s), (gm, " if full else
+                                f"full dyncore stage sequence incl. cmnfld2, eddtra and convec (gm, ") +
+                               (f"neutral slopes from cmnfld2 every step" if args.slopes == "live" else f"frozen slopes of amplitude {NSLP0:g}") + "); "
+                               "N>1: halos over RCCL send/recv" + (f", barotropic solve {args.barotp}" if layout is not None else "") + "; state_crc = xccrc(dp) ^ xccrc(u) of the whole domain, "
+                               "the same for every N at equal --steps/--warmup" + (" [halo via RCCL self-send]" if args.rccl_self else ""),
+                   "eddtra_parity": "unpinned (mod_eddtra needs CVMix: the reference build lacks it; checked against the C restatement)"},
+    }
+    out["config"]["physics"] = "full" if full else "dyncore"
+    out["config"]["forcing"] = args.forcing
+    out["config"]["spinup_steps"] = args.spinup
+    out["timed_steps_replayed_as_graphs"] = graph_steps_timed
+    if world > 1 and layout is None:
+        out["tile_days_per_s"] = world * value
+    if not args.full:
+        # a plain run ends here: the headline is all it prints.  From here on file descriptor 1 points to stderr, so that nothing the
+        # libraries print while they close follows the line on stdout
+        if rank == 0:
+            sys.stdout.write(json.dumps(out) + "\n")
+            sys.stdout.flush()
+            os.dup2(2, 1)
+        finish()
+        return
+
+    # ---- --full: dominant kernel class, timed with HIP events on the library's stream over K more steps
     gpu.set("timing", 1)
     gpu.timer_reset()
     ns = gpu.step(ns, min(args.steps, 5))
@@ -1069,10 +1142,6 @@ def main():
         # weak scaling: every tile integrates the same periodic pattern, so all ranks must hold the same bits
         crcs = launch.all_gather_ints(crc_state, env)
 
-    ms_per_step = dt / args.steps * 1e3
-    # model days per wall second of the domain that is integrated (for --scaling weak that domain is N times as long:
-    # tile_days_per_s = N x value is reported beside it, not as the value)
-    value = args.steps * baclin / 86400.0 / dt
     tile_i, tile_j = (layout.tile(*layout.rank_tile(rank))[2:] if layout is not None else (case.idm, case.jdm))
     F = tile_i * tile_j * case.kdm * 8.0
     cb = class_bytes_F(case.ntr, ntr_diffused(case))
@@ -1082,29 +1151,8 @@ def main():
     kb = kernel_bytes_F(case.ntr, sum(1 for nt in range(1, case.ntr + 1) if not (case.params.get("itrtke", -1) >= 1 and not case.params.get("tkeadv", 1)
                                                                                and nt in (case.params.get("itrtke"), case.params.get("itrgls")))))
     traffic, traffic_src = class_traffic(args.config, case.ntr)
-    out = {
-        "metric": "simulated-days/sec", "value": value, "unit": "simulated-days/sec", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
-        "scaling": scaling, "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": (f"{args.config} {case.idm}x{case.jdm}x{case.kdm} as {world} tiles ({layout.npx}x{layout.npy}: columns "
-                                f"{'/'.join(map(str, layout.isizes))}, rows {'/'.join(map(str, layout.jsizes))}), 1 tile per GPU, "
-                                if layout is not None else
-                                f"{args.config} {case.idm * world}x{case.jdm}x{case.kdm} as {world} tile(s) of "
-                                f"{case.idm}x{case.jdm}x{case.kdm} along i, 1 tile per GPU, ") +
-                               f"isopyc_bulkml/{args.advmth}/geopotential/uc/enscon, ntr={case.ntr} "
-                               f"({'TKE, length-scale slot, ideal age: the reference default build' if case.ntr == 3 else 'ideal age' if case.ntr == 1 else f'the default three + {case.ntr - 3} passive tracers'}), "
-                               f"baclin={baclin:g}s batrop={case.params['batrop']:g}s lstep={case.params['lstep']}; " +
-                               (f"config 2's step (phy/mod_blom_step.F90:96-253: init_fluxes, tmsmt1, cmnfld2, difest_isobml "
-                                f"[{'the whole routine: diffusivities estimated every step (NorESM defaults incl. rhsctp; the topographic beta is a synthetic field)' if difest_live else 'halos, pressure, ustar3, niw_ke_tendency; diffusivities frozen'}], eddtra, advect, pbcor1, "
-                                f"diffus, pgforc, momtum, convec, diapfl, thermf, mxlayr, updtrc, barotp, pbcor2, tmsmt2, cmnfld1), the channel "
-                                f"experiment's own forcing (zero fluxes, ustarw = 0.005 m/s), (gm, " if full else
-                                f"full dyncore stage sequence incl. cmnfld2, eddtra and convec (gm, ") +
-                               (f"neutral slopes from cmnfld2 every step" if args.slopes == "live" else f"frozen slopes of amplitude {NSLP0:g}") + "); "
-                               "N>1: halos over RCCL send/recv" + (f", barotropic solve {args.barotp}" if layout is not None else "") + "; state_crc = xccrc(dp) ^ xccrc(u) of the whole domain, "
-                               "the same for every N at equal --steps/--warmup" + (" [halo via RCCL self-send]" if args.rccl_self else ""),
-                   "eddtra_parity": "unpinned (mod_eddtra needs CVMix: the reference build lacks it; checked against the C restatement)",
-                   "state_finite": finite, "tiles_bit_identical": len(set(crcs)) == 1,
-                   "state_crc": f"{crcs[0]:08x}"},
+    out["config"].update({"state_finite": finite, "tiles_bit_identical": len(set(crcs)) == 1, "state_crc": f"{crcs[0]:08x}"})
+    out.update({
         "roofline": roofline_of_kernel(kern, kb, F, args.config) or
                     {"bound": "hbm", "kernel": dom, "achieved": cb[dom] * F / (live[dom] * 1e-3) / 1e9,
                      "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -1138,13 +1186,9 @@ def main():
         # counted HBM bytes (committed PMC profile of this workload: 2 x FETCH_SIZE + WRITE_SIZE) over the algorithmic bytes of SURVEY.md 8(d),
         # per stage class that has both
         "class_counted_over_alg": ({k: round(traffic[k] / (cb[k] * F), 2) for k in cb if traffic and k in traffic and k in live} or None),
-    }
-    out["config"]["physics"] = "full" if full else "dyncore"
-    out["config"]["forcing"] = args.forcing
-    out["config"]["spinup_steps"] = args.spinup
+    })
     srt = sorted(block_ms)
     out["ms_per_step_blocks"] = [round(x, 4) for x in block_ms]
-    out["timed_steps_replayed_as_graphs"] = graph_steps_timed
     out["ms_per_step_median"] = srt[len(srt) // 2] if len(srt) % 2 else 0.5 * (srt[len(srt) // 2 - 1] + srt[len(srt) // 2])
     out["ms_per_step_min"], out["ms_per_step_max"] = srt[0], srt[-1]
     if spunup is not None:
@@ -1152,8 +1196,6 @@ def main():
     if dyncore_ms is not None:
         out["dyncore_only"] = {"ms_per_step": dyncore_ms, "value": baclin / 86400.0 / (dyncore_ms * 1e-3),
                                "note": "the dynamical-core sequence of rounds 1-3 (no thermf, mxlayr, difest part, cmnfld1), timed in this run after the main measurement"}
-    if world > 1 and layout is None:
-        out["tile_days_per_s"] = world * value
     if layout is not None:
         # the Amdahl term of the strong-scaling design: with --barotp replicated every rank solves the WHOLE 2-D barotropic domain
         # (no exchange inside the substep loop), so this part of a step does not shrink with N; rank_share_ms is what does
@@ -1180,11 +1222,7 @@ def main():
                 out["cpu_baseline"] = {"error": repr(e)}
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
         os.close(real_stdout)
-    if world > 1 or args.rccl_self or layout is not None:
-        gpu.rccl_finalize()
-    gpu.close()
-    if world > 1:
-        torch.distributed.destroy_process_group()
+    finish()
 
 
 if __name__ == "__main__":

@@ -12,12 +12,12 @@ export TMPDIR=/tmp
 for nl in "${LIBS[@]}"; do
   n=${nl%%=*}; l=${nl#*=}
   export BLOMGPU_LIB=$GRAFT_REPO_ROOT/$l
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --blocks 1 --spunup-steps 0 --no-dyncore-compare $BOPT > $O/kt_$n.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -o run -- python3 "$OLDPWD/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --blocks 1 --spunup-steps 0 --no-dyncore-compare $BOPT > $O/kt_$n.log 2>&1)
 done
 for rep in 1 2; do
   for nl in "${LIBS[@]}"; do
     n=${nl%%=*}; l=${nl#*=}
-    BLOMGPU_LIB=$GRAFT_REPO_ROOT/$l python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --spunup-steps 0 --no-dyncore-compare $BOPT 2>/dev/null | grep "^{" | python3 -c "
+    BLOMGPU_LIB=$PWD/$l python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --spunup-steps 0 --no-dyncore-compare $BOPT 2>/dev/null | grep "^{" | python3 -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$n', round(d['ms_per_step'],4), d['ms_per_step_blocks'], d.get('state_crc'))"
   done

@@ -97,7 +97,7 @@ def bench(lib):
         env["BLOMGPU_LIB"] = lib
     else:
         env.pop("BLOMGPU_LIB", None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu-baseline"], env=env, capture_output=True, text=True).stdout
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline"], env=env, capture_output=True, text=True).stdout
     line = [x for x in out.splitlines() if x.startswith('{"metric')][-1]
     d = json.loads(line)
     return d["ms_per_step"], d["stages_ms"]

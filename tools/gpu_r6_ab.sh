@@ -10,7 +10,7 @@ tools/probes/copy_rate > $O/copy_rate.txt 2>&1
 export TMPDIR=/tmp
 trace() {   # trace <name> <bench opts...>
   n=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare "$@" > $O/kt_$n.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare "$@" > $O/kt_$n.log 2>&1
   python3 tools/kstats.py $O/kt_$n k_ > $O/kstats_$n.txt 2>&1
 }
 if [ -f tools/probes/libblomgpu_r05.so ]; then
@@ -22,11 +22,11 @@ trace new --opt overlap=0
 for v in 1 2 3 4; do trace ring$v --opt overlap=0 --opt pgf_uv_ring=$v; done
 for rep in 1 2; do
   if [ -f tools/probes/libblomgpu_r05.so ]; then
-    BLOMGPU_LIB=$GRAFT_REPO_ROOT/tools/probes/libblomgpu_r05.so python3 bench.py --steps 20 --no-cpu-baseline > $O/bench_r05_$rep.json 2>/dev/null
+    BLOMGPU_LIB=$PWD/tools/probes/libblomgpu_r05.so python3 bench.py --full --steps 20 --no-cpu-baseline > $O/bench_r05_$rep.json 2>/dev/null
   fi
-  python3 bench.py --steps 20 --no-cpu-baseline > $O/bench_new_$rep.json 2>/dev/null
-  python3 bench.py --steps 20 --no-cpu-baseline --opt pgf_uv_ring=3 > $O/bench_ring3_$rep.json 2>/dev/null
-  python3 bench.py --steps 20 --no-cpu-baseline --opt pgf_uv_ring=2 > $O/bench_ring2_$rep.json 2>/dev/null
+  python3 bench.py --full --steps 20 --no-cpu-baseline > $O/bench_new_$rep.json 2>/dev/null
+  python3 bench.py --full --steps 20 --no-cpu-baseline --opt pgf_uv_ring=3 > $O/bench_ring3_$rep.json 2>/dev/null
+  python3 bench.py --full --steps 20 --no-cpu-baseline --opt pgf_uv_ring=2 > $O/bench_ring2_$rep.json 2>/dev/null
 done
 for f in $O/bench_*.json; do python3 - "$f" <<'PY'
 import sys, json

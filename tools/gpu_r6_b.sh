@@ -7,7 +7,7 @@ tools/probes/copy_rate > $O/copy_rate.txt 2>&1
 export TMPDIR=/tmp
 trace() {
   n=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare --blocks 1 --spunup-steps 0 "$@" > $O/kt_$n.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare --blocks 1 --spunup-steps 0 "$@" > $O/kt_$n.log 2>&1
   python3 tools/kstats.py $O/kt_$n k_ > $O/kstats_$n.txt 2>&1
 }
 trace old --opt overlap=0
@@ -18,7 +18,7 @@ grep -h "k_pgf_uv\|k_pscan" $O/kstats_*.txt | awk '{print FILENAME, $0}'
 for f in $O/kstats_*.txt; do echo "$f: $(grep -h 'k_pgf_uv\|k_pscan' $f | awk '{printf "%s %s us x%s | ", $2, $6, $4}')"; done | tee $O/pgf_summary.txt
 timeout 900 python3 -m pytest tests/test_gpu_fortran_host.py tests/test_xcheck_difest.py -m gpu -x -q -k "difest_live or spun_up" > $O/newtests.txt 2>&1
 tail -3 $O/newtests.txt
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - $O/bench.json <<'PY'
 import sys, json
 for l in open(sys.argv[1]):

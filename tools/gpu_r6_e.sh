@@ -9,7 +9,7 @@ done
 cat $O/pmc_v*.txt
 trace() {
   n=$1; shift
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare --blocks 1 --spunup-steps 0 "$@" > $O/kt_$n.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_$n -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-dyncore-compare --blocks 1 --spunup-steps 0 "$@" > $O/kt_$n.log 2>&1
   python3 tools/kstats.py $O/kt_$n k_cmn_nslope > $O/kstats_$n.txt 2>&1
 }
 for v in 4 3 2; do trace nb$v --opt overlap=0 --opt cmn_nslope_nb=$v; trace sp_nb$v --spinup 600 --opt overlap=0 --opt cmn_nslope_nb=$v; done
@@ -17,9 +17,9 @@ grep -h "k_cmn_nslope" $O/kstats_*.txt
 python3 tools/longrun_full_physics.py --steps 1200 --every 200 --golden tests/golden/channel_tke_live_long_crc.json > $O/longrun_default.txt 2> $O/longrun.err
 python3 tools/longrun_full_physics.py --steps 1200 --every 200 --forcing calm > $O/longrun_calm.txt 2>> $O/longrun.err
 cat $O/longrun_default.txt $O/longrun_calm.txt
-python3 bench.py --forcing calm --no-cpu-baseline > $O/bench_calm.json 2> /dev/null
-python3 bench.py --no-cpu-baseline --opt pgf_uv_ring=5 > $O/bench_next.json 2> /dev/null
-python3 bench.py --no-cpu-baseline > $O/bench_old.json 2> /dev/null
+python3 bench.py --full --forcing calm --no-cpu-baseline > $O/bench_calm.json 2> /dev/null
+python3 bench.py --full --no-cpu-baseline --opt pgf_uv_ring=5 > $O/bench_next.json 2> /dev/null
+python3 bench.py --full --no-cpu-baseline > $O/bench_old.json 2> /dev/null
 for f in calm next old; do python3 - $O/bench_$f.json <<'PY'
 import sys, json
 for l in open(sys.argv[1]):

@@ -6,7 +6,7 @@ tools/probes/copy_rate > $O/copy_rate.txt 2>&1
 timeout 1500 python3 -m pytest tests -m gpu -x -q > $O/gpu_suite_full.txt 2>&1
 grep -aE "passed|failed" $O/gpu_suite_full.txt | tail -1 | tee $O/gpu_suite.txt
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; tail -2 $O/smoke.txt
-python3 bench.py > $O/bench.json 2> $O/bench.err
+python3 bench.py --full > $O/bench.json 2> $O/bench.err
 python3 - $O/bench.json <<'PY'
 import sys, json
 for l in open(sys.argv[1]):

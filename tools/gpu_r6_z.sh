@@ -6,7 +6,7 @@ T=${1:?tag}; K=${2:-}
 O=gpurun_out/$T; mkdir -p $O
 python -m pytest tests/test_gpu_golden.py -x -q > $O/t_golden.log 2>&1; tail -2 $O/t_golden.log
 if [ -n "$K" ]; then python -m pytest tests -m gpu -x -q -k "$K" > $O/t_k.log 2>&1; grep -a "passed\|failed" $O/t_k.log | tail -2; fi
-python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>$O/b.err | grep "^{" > $O/b.json
+python3 bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>$O/b.err | grep "^{" > $O/b.json
 python3 - <<PY
 import json
 d=json.loads(open("$O/b.json").read())
@@ -14,7 +14,7 @@ print(d["ms_per_step"], d["ms_per_step_blocks"], d["spunup"]["ms_per_step"])
 print({k: round(v,3) for k,v in d["stages_ms"].items()})
 PY
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/$O/kt -o run -- python3 $GRAFT_REPO_ROOT/bench.py --steps 5 --warmup 2 --no-cpu-baseline --blocks 1 --spunup-steps 0 --no-dyncore-compare > /dev/null 2>$GRAFT_REPO_ROOT/$O/kt.err
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OLDPWD/$O/kt" -o run -- python3 "$OLDPWD/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --blocks 1 --spunup-steps 0 --no-dyncore-compare > /dev/null 2>"$OLDPWD/$O/kt.err"
 cd $GRAFT_REPO_ROOT
 python3 - <<PY
 import csv,glob

@@ -10,7 +10,7 @@ bad=0
 tools/probes/copy_rate > "$O/copy_rate.txt" 2> "$O/copy_rate.err" || bad=1
 # the headline line first, as the driver runs it (its own invocation on a box that has not been under load for minutes: the pool's boxes slow down by 3 - 5 %
 # under sustained load -- the same library 6.37 -> 6.75 ms over an hour of A/B runs, back at 6.37 after a quarter of an hour's rest), then the suite
-bench() { n=$1; shift; python3 bench.py "$@" > "$O/bench_$n.json" 2> "$O/bench_$n.err"; grep -q '^{' "$O/bench_$n.json" || { echo "bench $n produced no line" >&2; bad=1; }; }
+bench() { n=$1; shift; python3 bench.py --full "$@" > "$O/bench_$n.json" 2> "$O/bench_$n.err"; grep -q '^{' "$O/bench_$n.json" || { echo "bench $n produced no line" >&2; bad=1; }; }
 bench default --steps 20
 timeout 1500 python3 -m pytest tests -m gpu -x -q > "$O/gpu_suite_full.txt" 2>&1 || bad=1
 grep -aE "passed|failed" "$O/gpu_suite_full.txt" | tail -1 > "$O/gpu_suite.txt"

@@ -68,7 +68,7 @@ for r, n, ins in zip(rows, names, inside):
 tot = sum(v[1] for v in acc.values())
 tot_out = sum(v[1] for v in out_acc.values())
 with open(f"{base}_kernel_stats.txt", "w") as f:
-    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline  ({config} {dims}, ntr = {ntr}, 1 GPU)\n")
+    f.write(f"# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline  ({config} {dims}, ntr = {ntr}, 1 GPU)\n")
     f.write(f"# {nst} baroclinic steps in the trace; kernel time per step {tot / 1e6 / nst:.3f} ms (launches inside the steps only;\n")
     f.write(f"# outside them -- initialisation, uploads, the bench's checksums -- {tot_out / 1e6:.3f} ms in total, not counted)\n")
     f.write(f"# {'kernel':42s} {'calls/step':>10s} {'avg_us':>10s} {'ms/step':>9s} {'%':>6s}\n")
@@ -96,7 +96,7 @@ if len(sys.argv) > 4:
         return a, len(fi)
     (fe, nst_f), (wr, nst_w) = per_kernel(sys.argv[3], "FETCH_SIZE"), per_kernel(sys.argv[4], "WRITE_SIZE")
     with open(f"{base}_pmc_hbm_traffic.txt", "w") as f:
-        f.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --steps 3 --warmup 2 ({config} {dims}, ntr = {ntr});\n")
+        f.write(f"# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes), bench.py --full --steps 3 --warmup 2 ({config} {dims}, ntr = {ntr});\n")
         f.write(f"# launches inside the {nst_f} baroclinic steps only.\n")
         f.write("# per-launch averages in MB (counters are in KB).  Per MI355X_MICROARCH.md (HBM section) FETCH_SIZE on gfx950 reports\n")
         f.write("# half the bytes of a coalesced stream, for the 8 B/lane loads of these fp64 kernels as for 16 B/lane ones (calibrated on known\n")
