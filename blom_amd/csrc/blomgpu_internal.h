@@ -239,9 +239,26 @@ struct blomgpu_ctx;
 struct TileGroup;            // in-process transport: several tiles (contexts) on one device, one host thread each
 struct RcclComm;             // one process per GPU, neighbour ncclSend/ncclRecv over xGMI
 struct BtGlobal;             // RCCL tiles: the barotropic solve replicated on every rank (comm_rccl.hip)
+// The general tile table of xcspmd (phy/mod_xc.F90:1332-1720), kept for ragged layouts only: tile rows cut differently,
+// tiles shrunk to their sea points, all-land tiles eliminated (ii = 0).  Tensor-product layouts never carry one.
+struct TileTable {
+  int npx = 0, npy = 0, itdm = 0, nranks = 0;
+  std::vector<int> i0, ii;   // [py*npx + px]
+  std::vector<int> j0, jj;   // [py]
+  std::vector<int> rank;     // [py*npx + px]: the non-empty tiles numbered m fastest, then n (:1545-1560); -1: eliminated
+  // previous / next non-empty tile of row py, -1 if there is none or it does not touch tile px (:1726-1745); the row wraps
+  // only if it starts at 0 and ends at itdm (:1591-1594)
+  void ew_neighbours(int px, int py, bool periodic, int *west, int *east) const;
+  bool tensor_product() const;
+};
+// fills `out` from the four tables (i0_pe / ii_pe: npy*npx entries, m fastest; j0_pe / jj_pe: npy entries) and checks them the
+// way xcspmd does; returns nullptr or the message of the check that failed
+const char *tiletable_build(int npx, int npy, int itdm, int jtdm, const int *i0_pe, const int *ii_pe, const int *j0_pe,
+                            const int *jj_pe, TileTable *out);
 struct Tiling {
-  int npx = 1, npy = 1;      // uniform tile grid (mproc x nproc)
+  int npx = 1, npy = 1;      // tile grid (mproc x nproc)
   int px = 0, py = 0;        // this tile
+  const TileTable *tab = nullptr;   // ragged layout: the table (owned by the transport); nullptr: tensor product
   TileGroup *group = nullptr;
   RcclComm *rccl = nullptr;
   bool multi() const { return npx * npy > 1 || rccl != nullptr; }

@@ -1,6 +1,10 @@
 // xctilr over RCCL: one process per GPU, neighbour ncclSend/ncclRecv (xGMI is point-to-point, a
-// halo exchange touches only the neighbouring GPUs).  Uniform npx x npy tile grid, rank = px + npx*py
-// (the reference's mproc/nproc numbering, bld/blom_dimensions:104-148).  The reference's two phases
+// halo exchange touches only the neighbouring GPUs).  Tensor-product npx x npy tile grid, rank = px + npx*py
+// (the reference's mproc/nproc numbering, bld/blom_dimensions:104-148) -- or, through blomgpu_rccl_init_table, the
+// general table of xcspmd (phy/mod_xc.F90:1332-1720): rows cut differently, tiles shrunk to their sea points, all-land
+// tiles eliminated and left out of the rank numbering.  Such a ragged tile has at most one E and one W neighbour, and only
+// if that tile touches it (:1726-1745), but several N and S neighbours, one per tile of the next row that shares columns
+// with it (:1747-1990); columns over no tile are vland.  See "ragged" below.  The reference's two phases
 // (phy/mod_xc.F90:3036-3106 N-S, :3131-3178 E-W): phase 1 exchanges rows of the columns 1..ii with the
 // south/north neighbours (tile-local when npy = 1: periodic wrap or vland), phase 2 exchanges the E/W
 // strips over rows 1-nhl..jj+nhl, so the corners travel with it.  Messages: mhl*(jj+2*nhl)*nlev reals per
@@ -21,7 +25,30 @@ struct RcclComm {
   double *arc_send = nullptr, *arc_gath = nullptr;   // arctic patch: my strip (self-send hook), the top row's strips
   size_t arc_cap = 0;
   int force_ns = 0;          // test hook: route a tile-local periodic N/S wrap through send/recv to itself
+  // ragged table (blomgpu_rccl_init_table): written once at init, nothing of it is rebuilt on the step path
+  TileTable *tab = nullptr;
+  int west = -1, east = -1;  // ranks of the touching E/W neighbours
+  int top0 = 0;              // rank of the first tile of the top row (arctic strips)
+  struct NsSegs *segs = nullptr;   // receive tables [0] the row below, [1] the row above; send tables [2], [3] likewise
 };
+
+// The tiles of the next row that cover my columns (the reference's m0_top, mm_top, i0_st, ii_st and their _bot twins):
+// segment s is my local columns a..a+w-1, shared with rank `rank`.  The send and the receive table of a side differ in one
+// thing: the u- and q-points on the east face of a tile whose east edge is open (column ii+1) belong to no tile but hold what
+// that tile computes there (barotp's coastal pvtrop), so such a tile sends its halo column ii+1 along, and the receiver takes
+// it as one more column of that segment (halo.hip: k_xctilr_tiles_ragged does the same).  A
+// side's staging buffer holds one block per segment, [field][level][row][i - a] with i fastest, so a segment is one
+// message and every row of it a contiguous run; block s starts at cum[s] * nhl * nlev * nf.
+#define NS_MAXSEG 17            // a row has at most XCT_MAXDIM = 16 tiles
+struct NsSegs {
+  int n;
+  int a[NS_MAXSEG], w[NS_MAXSEG], cum[NS_MAXSEG], rank[NS_MAXSEG];
+};
+__device__ inline int ns_seg_of(const NsSegs &S, int i) {
+  for (int s = 0; s < S.n; s++)
+    if (i >= S.a[s] && i < S.a[s] + S.w[s]) return s;
+  return -1;
+}
 
 // up to MAXF plane stacks (same nlev, same halo widths) travel in one message per neighbour
 #define MAXF 4
@@ -122,6 +149,67 @@ __global__ void k_unpack_ns(const DevView *__restrict__ Vp, FieldSet F, const do
   }
 }
 
+// ragged: phase 1 between a tile and the several tiles below / above it.  One pack and one unpack launch whatever the
+// number of neighbours: thread (row, i) walks the tile's full width, so the loads / stores of the array are coalesced as in
+// k_pack_ns / k_unpack_ns, finds its segment in the table (passed by value) and addresses that segment's block.  Columns
+// over no tile of the next row are left as they stand where a row of the domain lies there (keep_s / keep_n: land inside
+// the domain keeps the undivided domain's value, halo.hip: k_xctilr_tiles_ragged) and get vland beyond a closed edge.
+__global__ void k_pack_ns_seg(const DevView *__restrict__ Vp, FieldSet F, double *__restrict__ south, double *__restrict__ north,
+                              NsSegs Ss, NsSegs Sn, int nlev, int nhl) {
+  const DevView &V = *Vp;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nhl * (V.ii + 1)) return;                 // column ii+1: the east face of an open edge
+  const int i = t % (V.ii + 1) + 1, r = t / (V.ii + 1);
+  const int ss = ns_seg_of(Ss, i), sn = ns_seg_of(Sn, i);
+  const double *a = F.p[blockIdx.z];
+  const size_t blk = (size_t)nhl * nlev * gridDim.z;
+  for (int k = blockIdx.y; k < nlev; k += gridDim.y) {
+    const size_t o = (size_t)k * V.nplane, fk = ((size_t)blockIdx.z * nlev + k) * nhl + r;
+    if (ss >= 0) south[Ss.cum[ss] * blk + fk * Ss.w[ss] + (i - Ss.a[ss])] = a[IDX(V, i, 1 + r) + o];
+    if (sn >= 0) north[Sn.cum[sn] * blk + fk * Sn.w[sn] + (i - Sn.a[sn])] = a[IDX(V, i, V.jj - nhl + 1 + r) + o];
+  }
+}
+__global__ void k_unpack_ns_seg(const DevView *__restrict__ Vp, FieldSet F, const double *__restrict__ from_south,
+                                const double *__restrict__ from_north, NsSegs Ss, NsSegs Sn, int nlev, int nhl, int keep_s,
+                                int keep_n) {
+  const DevView &V = *Vp;
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= nhl * (V.ii + 1)) return;                 // column ii+1: the east face of an open edge, written only if delivered
+  const int i = t % (V.ii + 1) + 1, r = t / (V.ii + 1);
+  const int ss = ns_seg_of(Ss, i), sn = ns_seg_of(Sn, i);
+  if (i > V.ii) { keep_s = 1; keep_n = 1; }
+  double *a = F.p[blockIdx.z];
+  const size_t blk = (size_t)nhl * nlev * gridDim.z;
+  for (int k = blockIdx.y; k < nlev; k += gridDim.y) {
+    const size_t o = (size_t)k * V.nplane, fk = ((size_t)blockIdx.z * nlev + k) * nhl + r;
+    if (ss >= 0) a[IDX(V, i, 1 - nhl + r) + o] = from_south[Ss.cum[ss] * blk + fk * Ss.w[ss] + (i - Ss.a[ss])];
+    else if (!keep_s) a[IDX(V, i, 1 - nhl + r) + o] = V.P.vland;
+    if (sn >= 0) a[IDX(V, i, V.jj + 1 + r) + o] = from_north[Sn.cum[sn] * blk + fk * Sn.w[sn] + (i - Sn.a[sn])];
+    else if (!keep_n) a[IDX(V, i, V.jj + 1 + r) + o] = V.P.vland;
+  }
+}
+// k_unpack_ew for a ragged tile: a side without a touching neighbour is vland where the domain ends there, and is left as
+// it stands (keep_w / keep_e) where land of the domain lies beyond it
+__global__ void k_unpack_ew_keep(const DevView *__restrict__ Vp, FieldSet F, const double *__restrict__ from_west,
+                                 const double *__restrict__ from_east, int nlev, int mhl, int nhl, int has_w, int has_e,
+                                 int keep_w, int keep_e) {
+  const DevView &V = *Vp;
+  const int nrow = V.jj + 2 * nhl, per = mhl * nrow;
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= per) return;
+  const int q = t % mhl, r = t / mhl;
+  const int j = r + 1 - nhl;
+  double *a = F.p[blockIdx.z];
+  const size_t fo = (size_t)blockIdx.z * nlev * per;
+  for (int k = blockIdx.y; k < nlev; k += gridDim.y) {
+    const size_t o = (size_t)k * V.nplane;
+    if (has_w) a[IDX(V, 1 - mhl + q, j) + o] = from_west[fo + (size_t)k * per + t];
+    else if (!keep_w) a[IDX(V, 1 - mhl + q, j) + o] = V.P.vland;
+    if (has_e) a[IDX(V, V.ii + 1 + q, j) + o] = from_east[fo + (size_t)k * per + t];
+    else if (!keep_e) a[IDX(V, V.ii + 1 + q, j) + o] = V.P.vland;
+  }
+}
+
 // `landed` != nullptr: leave the received E/W strips in the receive buffers (no unpack launch) and report
 // them; the consumer reads its rim straight from there (barotp's substep-pair kernel).
 int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev, int mhl, int nhl, RcclLanded *landed);
@@ -145,7 +233,7 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
   // ---- phase 1 as an exchange: several tile rows, or the single-rank test hook -----------------------
   const bool ns_exchange = nhl > 0 && (T.npy > 1 || (R->force_ns && periodic_j));
   if (ns_exchange) {
-    const size_t per = (size_t)nhl * h.ii, need = per * nlev * nf;
+    const size_t per = (size_t)nhl * h.ii, need = (per + (R->tab ? nhl : 0)) * nlev * nf;    // ragged: one column more
     if (need > R->cap_ns) {
       HIPCHK(c, hipStreamSynchronize(st));
       for (int s = 0; s < 2; s++) {
@@ -156,9 +244,26 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
       }
       R->cap_ns = need;
     }
+    dim3 g((unsigned)((per + 255) / 256), ly, nf);
+    if (R->tab) {
+      // same matching rule as below: sends to the south, sends to the north, receives from the north, from the south
+      const NsSegs &Ss = R->segs[0], &Sn = R->segs[1];
+      const size_t blk = (size_t)nhl * nlev * nf;
+      const NsSegs &Ps = R->segs[2], &Pn = R->segs[3];
+      hipLaunchKernelGGL(k_pack_ns_seg, dim3((unsigned)((per + nhl + 255) / 256), ly, nf), dim3(256), 0, st, c->d, F, R->sbuf_ns[0],
+                         R->sbuf_ns[1], Ps, Pn, nlev, nhl);
+      ncclGroupStart();
+      for (int s = 0; s < Ps.n; s++) ncclSend(R->sbuf_ns[0] + Ps.cum[s] * blk, Ps.w[s] * blk, ncclDouble, Ps.rank[s], R->comm, st);
+      for (int s = 0; s < Pn.n; s++) ncclSend(R->sbuf_ns[1] + Pn.cum[s] * blk, Pn.w[s] * blk, ncclDouble, Pn.rank[s], R->comm, st);
+      for (int s = 0; s < Sn.n; s++) ncclRecv(R->rbuf_ns[1] + Sn.cum[s] * blk, Sn.w[s] * blk, ncclDouble, Sn.rank[s], R->comm, st);
+      for (int s = 0; s < Ss.n; s++) ncclRecv(R->rbuf_ns[0] + Ss.cum[s] * blk, Ss.w[s] * blk, ncclDouble, Ss.rank[s], R->comm, st);
+      ncclResult_t rc = ncclGroupEnd();
+      if (rc != ncclSuccess) return ctx_fail(c, std::string("RCCL halo exchange (N/S, ragged): ") + ncclGetErrorString(rc));
+      hipLaunchKernelGGL(k_unpack_ns_seg, dim3((unsigned)((per + nhl + 255) / 256), ly, nf), dim3(256), 0, st, c->d, F, R->rbuf_ns[0], R->rbuf_ns[1], Ss, Sn, nlev, nhl,
+                         (h.j0 > 0 || periodic_j) ? 1 : 0, (h.j0 + h.jj < h.jtdm || periodic_j) ? 1 : 0);
+    } else {
     const int south = T.py > 0 ? R->rank - T.npx : (periodic_j ? R->rank + T.npx * (T.npy - 1) : -1);
     const int north = T.py < T.npy - 1 ? R->rank + T.npx : (periodic_j ? R->rank - T.npx * (T.npy - 1) : -1);
-    dim3 g((unsigned)((per + 255) / 256), ly, nf);
     hipLaunchKernelGGL(k_pack_ns, g, dim3(256), 0, st, c->d, F, R->sbuf_ns[0], R->sbuf_ns[1], nlev, nhl);
     // same matching rule as E/W below: send south, send north, receive north, receive south
     ncclGroupStart();
@@ -170,6 +275,7 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
     if (rc != ncclSuccess) return ctx_fail(c, std::string("RCCL halo exchange (N/S): ") + ncclGetErrorString(rc));
     hipLaunchKernelGGL(k_unpack_ns, g, dim3(256), 0, st, c->d, F, R->rbuf_ns[0], R->rbuf_ns[1], nlev, nhl,
                        south >= 0 ? 1 : 0, north >= 0 ? 1 : 0);
+    }
   }
   const unsigned gns = nhl > 0 && !ns_exchange ? (unsigned)((2 * nhl * h.ii + 255) / 256) : 0u;
   if (mhl <= 0) {
@@ -191,8 +297,9 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
       R->cap = need;
     }
     const int row0 = R->rank - T.px;        // first rank of my tile row
-    const int west = T.px > 0 ? R->rank - 1 : (per_i ? row0 + T.npx - 1 : -1);
-    const int east = T.px < T.npx - 1 ? R->rank + 1 : (per_i ? row0 : -1);
+    // ragged: the touching neighbours found at init (phy/mod_xc.F90:1726-1745); a side without one is vland
+    const int west = R->tab ? R->west : T.px > 0 ? R->rank - 1 : (per_i ? row0 + T.npx - 1 : -1);
+    const int east = R->tab ? R->east : T.px < T.npx - 1 ? R->rank + 1 : (per_i ? row0 : -1);
     const unsigned gpack = (unsigned)((per + 255) / 256);
     dim3 g(gpack, ly, nf);
     if (!prepacked || regrown)
@@ -213,6 +320,9 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
       landed->has_w = west >= 0 ? 1 : 0; landed->has_e = east >= 0 ? 1 : 0;
       landed->per = (int)per; landed->mhl = mhl; landed->nhl = nhl; landed->nlev = nlev;
       landed->send_west = R->sbuf[0]; landed->send_east = R->sbuf[1];
+    } else if (R->tab) {
+      hipLaunchKernelGGL(k_unpack_ew_keep, g, dim3(256), 0, st, c->d, F, R->rbuf[0], R->rbuf[1], nlev, mhl, nhl,
+                         west >= 0 ? 1 : 0, east >= 0 ? 1 : 0, (h.i0 > 0 || per_i) ? 1 : 0, (h.i0 + h.ii < h.itdm || per_i) ? 1 : 0);
     } else {
       hipLaunchKernelGGL(k_unpack_ew, g, dim3(256), 0, st, c->d, F, R->rbuf[0], R->rbuf[1], nlev, mhl, nhl,
                          west >= 0 ? 1 : 0, east >= 0 ? 1 : 0);
@@ -250,7 +360,7 @@ int rccl_arctic_gather(blomgpu_ctx *c, double *const *fields, int nf, int nlev, 
   double *mine = self ? R->arc_send : R->arc_gath + (size_t)T.px * need;
   arctic_pack_launch(c, st, fields, nf, mine, nlev, nrows);
   if (T.npx > 1 || self) {
-    const int row0 = T.npx * (T.npy - 1);
+    const int row0 = R->tab ? R->top0 : T.npx * (T.npy - 1);
     ncclGroupStart();
     for (int q = 0; q < T.npx; q++)
       if (q != T.px || self) ncclSend(mine, need, ncclDouble, row0 + q, R->comm, st);
@@ -458,6 +568,99 @@ int blomgpu_rccl_init_2d(blomgpu_ctx *c, const void *id128, int rank, int npx, i
   c->tiling.npx = npx; c->tiling.npy = npy; c->tiling.px = px; c->tiling.py = py;
   return 0;
 }
+// The general tile table of xcspmd (phy/mod_xc.F90:1332-1720): i0_pe / ii_pe hold npy*npx entries, m fastest (ii_pe = 0: the
+// tile is eliminated), j0_pe / jj_pe npy entries; `rank` counts the non-empty tiles, m fastest, then n (:1545-1560).  A
+// tensor-product table is handed to blomgpu_rccl_init_2d and takes exactly its path.  Otherwise the neighbours are found
+// here once: the touching tile to the west / east (:1726-1745), the segments of the rows below / above (:1747-1990).
+int blomgpu_rccl_init_table(blomgpu_ctx *c, const void *id128, int rank, int npx, int npy, const int *i0_pe, const int *ii_pe,
+                            const int *j0_pe, const int *jj_pe) {
+  const DevView &h = c->h;
+  TileTable *tab = new TileTable();
+  if (const char *msg = tiletable_build(npx, npy, h.itdm, h.jtdm, i0_pe, ii_pe, j0_pe, jj_pe, tab)) {
+    delete tab;
+    return ctx_fail(c, std::string("rccl_init_table: ") + msg);
+  }
+  if (tab->tensor_product()) {
+    delete tab;
+    return blomgpu_rccl_init_2d(c, id128, rank, npx, npy);
+  }
+  int me = -1;
+  for (int q = 0; q < npx * npy; q++)
+    if (tab->rank[q] == rank) me = q;
+  if (me < 0) { delete tab; return ctx_fail(c, "rccl_init_table: the rank is not a tile of the table"); }
+  const int px = me % npx, py = me / npx;
+  if (h.i0 != tab->i0[me] || h.ii != tab->ii[me] || h.j0 != tab->j0[py] || h.jj != tab->jj[py]) {
+    delete tab;
+    return ctx_fail(c, "rccl_init_table: the context's window (i0, j0, idm, jdm) is not this rank's tile of the table");
+  }
+  if (h.nreg == 2) {        // :1480-1506, :1600-1603; the strips of the fold travel between ALL tiles of the top row
+    for (int m = 0; m < npx; m++) {
+      const int q = (npy - 1) * npx + m;
+      if (npx > 1 && (tab->ii[q] != h.itdm / npx || tab->i0[q] != m * (h.itdm / npx) || h.itdm % npx)) {
+        const bool empty = tab->ii[q] == 0;
+        delete tab;
+        return ctx_fail(c, empty ? "rccl_init_table: eliminated tiles in the arctic top row are not built"
+                                 : "xcspmd: arctic tiles are not the right size");
+      }
+    }
+    if (npx > 1 && npx % 2) { delete tab; return ctx_fail(c, "xcspmd (arctic) - ipr must be even"); }
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  RcclComm *R = new RcclComm();
+  ncclUniqueId id;
+  memcpy(&id, id128, sizeof(id) < 128 ? sizeof(id) : 128);
+  ncclResult_t rc = ncclCommInitRank(&R->comm, tab->nranks, id, rank);
+  if (rc != ncclSuccess) { delete R; delete tab; return ctx_fail(c, std::string("ncclCommInitRank: ") + ncclGetErrorString(rc)); }
+  R->rank = rank; R->nranks = tab->nranks;
+  R->tab = tab;
+  int w = -1, e = -1;
+  tab->ew_neighbours(px, py, !(h.nreg == 0 || h.nreg == 4), &w, &e);
+  R->west = w >= 0 ? tab->rank[py * npx + w] : -1;
+  R->east = e >= 0 ? tab->rank[py * npx + e] : -1;
+  R->top0 = tab->rank[(npy - 1) * npx];
+  R->segs = new NsSegs[4];
+  const bool per_i = !(h.nreg == 0 || h.nreg == 4);
+  for (int tabno = 0; tabno < 4; tabno++) {
+    const int side = tabno % 2;
+    const bool sending = tabno >= 2;
+    NsSegs &S = R->segs[tabno];
+    S.n = 0;
+    for (int s = 0; s < NS_MAXSEG; s++) S.a[s] = S.w[s] = S.cum[s] = 0, S.rank[s] = -1;
+    int qy = side == 0 ? py - 1 : py + 1;
+    if (qy < 0 || qy >= npy) {
+      if (h.nreg <= 2) continue;                     // closed (or the arctic fold, which has its own exchange)
+      qy = (qy + npy) % npy;
+    }
+    int cum = 0;
+    for (int m = 0; m < npx; m++) {
+      const int q = qy * npx + m;
+      if (tab->ii[q] <= 0) continue;
+      // Columns a tile can give: its own, and -- east edge open -- its east face (halo column ii+1, which nobody owns).
+      // Columns a tile needs in phase 1: its own, and -- east edge open -- its east face.  A segment is what one gives and
+      // the other needs; the same rule on both sides, so sender and receiver agree on every length.
+      int qw = -1, qe = -1;
+      tab->ew_neighbours(m, qy, per_i, &qw, &qe);
+      const int my_end = h.i0 + h.ii + (e < 0 && h.i0 + h.ii < h.itdm ? 1 : 0);
+      const int q_end = tab->i0[q] + tab->ii[q] + (qe < 0 && tab->i0[q] + tab->ii[q] < h.itdm ? 1 : 0);
+      const int lo = tab->i0[q] > h.i0 ? tab->i0[q] : h.i0;
+      const int hi = q_end < my_end ? q_end : my_end;
+      if (hi <= lo) continue;
+      const int wd = hi - lo;
+      S.a[S.n] = lo - h.i0 + 1; S.w[S.n] = wd; S.cum[S.n] = cum; S.rank[S.n] = tab->rank[q];
+      cum += wd;
+      S.n++;
+    }
+  }
+  c->tiling.rccl = R;
+  c->tiling.tab = tab;
+  if (!c->xstream) {
+    HIPCHK(c, hipStreamCreateWithFlags(&c->xstream, hipStreamNonBlocking));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+  }
+  c->tiling.npx = npx; c->tiling.npy = npy; c->tiling.px = px; c->tiling.py = py;
+  return 0;
+}
 int blomgpu_rccl_init(blomgpu_ctx *c, const void *id128, int rank, int nranks) {      // tiles along i
   return blomgpu_rccl_init_2d(c, id128, rank, nranks, 1);
 }
@@ -471,30 +674,54 @@ int blomgpu_rccl_force_ns_exchange(blomgpu_ctx *c, int on) {
 // Replicated barotropic solve: G is a context of the GLOBAL domain (itdm x jtdm, kdm >= 3, same nreg, global masks and grid
 // metrics uploaded by the caller) on the same device; isizes[npx], jsizes[npy] are the widths / heights of the tile columns
 // and rows (bld/blom_dimensions:104-148).  From then on the tile's barotp gathers, solves on G and takes its window.
+static int attach_barotp_windows(blomgpu_ctx *c, blomgpu_ctx *G, const std::vector<int> &win);
 int blomgpu_rccl_attach_barotp_global(blomgpu_ctx *c, blomgpu_ctx *G, const int *isizes, const int *jsizes) {
-  RcclComm *R = c->tiling.rccl;
   const Tiling &T = c->tiling;
-  if (!R) return ctx_fail(c, "attach_barotp_global: no RCCL transport");
+  if (!T.rccl) return ctx_fail(c, "attach_barotp_global: no RCCL transport");
+  if (T.tab) return ctx_fail(c, "attach_barotp_global: a ragged tile table needs blomgpu_rccl_attach_barotp_table");
+  std::vector<int> win;                     // (i0, j0, ii, jj) of every rank
+  for (int q = 0; q < T.npx * T.npy; q++) {
+    const int qx = q % T.npx, qy = q / T.npx;
+    int i0 = 0, j0 = 0;
+    for (int x = 0; x < qx; x++) i0 += isizes[x];
+    for (int y = 0; y < qy; y++) j0 += jsizes[y];
+    win.insert(win.end(), {i0, j0, isizes[qx], jsizes[qy]});
+  }
+  return attach_barotp_windows(c, G, win);
+}
+// The same with the general tile table (blomgpu_rccl_init_table's arguments): the windows of the non-empty tiles in rank
+// order.  Points of eliminated tiles and of the land between tiles are never written: they keep G's land values.
+int blomgpu_rccl_attach_barotp_table(blomgpu_ctx *c, blomgpu_ctx *G, int npx, int npy, const int *i0_pe, const int *ii_pe,
+                                     const int *j0_pe, const int *jj_pe) {
+  if (!c->tiling.rccl) return ctx_fail(c, "attach_barotp_table: no RCCL transport");
+  TileTable tab;
+  if (const char *msg = tiletable_build(npx, npy, c->h.itdm, c->h.jtdm, i0_pe, ii_pe, j0_pe, jj_pe, &tab))
+    return ctx_fail(c, std::string("attach_barotp_table: ") + msg);
+  std::vector<int> win;
+  for (int q = 0; q < npx * npy; q++)
+    if (tab.rank[q] >= 0) win.insert(win.end(), {tab.i0[q], tab.j0[q / npx], tab.ii[q], tab.jj[q / npx]});
+  return attach_barotp_windows(c, G, win);
+}
+static int attach_barotp_windows(blomgpu_ctx *c, blomgpu_ctx *G, const std::vector<int> &win) {
+  RcclComm *R = c->tiling.rccl;
+  if ((int)win.size() != 4 * R->nranks) return ctx_fail(c, "attach_barotp_global: the table does not list the communicator's ranks");
   if (!G || G->h.ii != c->h.itdm || G->h.jj != c->h.jtdm || G->h.nreg != c->h.nreg || G->tiling.multi() || G->device != c->device)
     return ctx_fail(c, "attach_barotp_global: the second context must span the global domain as a single tile on the same device");
   BtGlobal *B = new BtGlobal();
   B->G = G;
   for (int f : kBtFields) B->nplanes += c->nlev_real[f];
   if (B->nplanes > BT_MAXPLANES) { delete B; return ctx_fail(c, "attach_barotp_global: too many planes"); }
-  const int nr = T.npx * T.npy;
+  const int nr = R->nranks;
   size_t off = 0;
   std::vector<int> geo;
   std::vector<size_t> offs;
   for (int q = 0; q < nr; q++) {
-    const int qx = q % T.npx, qy = q / T.npx;
-    int i0 = 0, j0 = 0;
-    for (int x = 0; x < qx; x++) i0 += isizes[x];
-    for (int y = 0; y < qy; y++) j0 += jsizes[y];
-    B->i0.push_back(i0); B->j0.push_back(j0); B->ii.push_back(isizes[qx]); B->jj.push_back(jsizes[qy]);
+    const int i0 = win[4 * q], j0 = win[4 * q + 1], wi = win[4 * q + 2], wj = win[4 * q + 3];
+    B->i0.push_back(i0); B->j0.push_back(j0); B->ii.push_back(wi); B->jj.push_back(wj);
     B->off.push_back(off);
     offs.push_back(off);
-    geo.insert(geo.end(), {i0, j0, isizes[qx], jsizes[qy]});
-    const int pts = (isizes[qx] + 2 * NBDY) * (jsizes[qy] + 2 * NBDY);       // a tile's planes travel with their halos
+    geo.insert(geo.end(), {i0, j0, wi, wj});
+    const int pts = (wi + 2 * NBDY) * (wj + 2 * NBDY);       // a tile's planes travel with their halos
     off += (size_t)pts * B->nplanes;
     if (pts > B->maxpts) B->maxpts = pts;
   }
@@ -618,6 +845,9 @@ int blomgpu_rccl_finalize(blomgpu_ctx *c) {
   }
   if (R->arc_send) (void)hipFree(R->arc_send);
   if (R->arc_gath) (void)hipFree(R->arc_gath);
+  delete[] R->segs;
+  delete R->tab;
+  c->tiling.tab = nullptr;
   delete R;
   c->tiling.rccl = nullptr;
   return 0;

@@ -165,6 +165,113 @@ __global__ void k_xctilr_tiles(const DevView *__restrict__ Vp, double *__restric
   }
 }
 
+// The same gather over a RAGGED tile table (land-tile elimination, phy/mod_xc.F90:1332-1720: every tile row has its own
+// cut, tiles are shrunk to their sea points, all-land tiles are missing).  It follows the reference's two phases point for
+// point, so that it leaves what the RCCL transport leaves (comm_rccl.hip):
+//   E-W (:1726-1745, :3131-3178): columns beyond the tile come from the previous / next non-empty tile of the row only if
+//       that tile TOUCHES this one (has_w / has_e, the periodic wrap of a row that spans the domain included); otherwise
+//       nothing is delivered -- also where a gap is narrower than the halo and another tile's sea lies beyond it;
+//   N-S (:1743-1990, :3036-3106): a column is read from whichever tile of the row below / above covers it, nothing is
+//       delivered if none does; the corners are what the E/W neighbour holds there after its own phase 1, i.e. the same
+//       rule for its column.
+// "Nothing delivered": the reference writes vland; here the point keeps its value if it lies inside the domain (below).
+struct RagTab {
+  double *p[XCT_MAXTILES];      // the array being updated, in every tile (index py*npx + px; nullptr: eliminated)
+  int i0[XCT_MAXTILES], ii[XCT_MAXTILES];
+  int yoff[XCT_MAXDIM + 1];
+};
+__device__ inline int rag_owner(const int *__restrict__ i0, const int *__restrict__ ii, int row0, int npx, int ig) {
+  for (int q = row0; q < row0 + npx; q++)
+    if (ii[q] > 0 && ig > i0[q] && ig <= i0[q] + ii[q]) return q;
+  return -1;
+}
+__global__ void k_xctilr_tiles_ragged(const DevView *__restrict__ Vp, double *__restrict__ a, RagTab tab, int npx, int npy,
+                                      int px, int py, int nlev, int mhl, int nhl, int itype, int itdm, int wq, int eq,
+                                      int ew_per, int ns_per, int arctic) {
+  const DevView &V = *Vp;
+  const int has_w = wq >= 0, has_e = eq >= 0;            // wq / eq: the touching W / E neighbour (index in tab), -1: none
+  const int ii = V.ii, jj = V.jj, jtdm = tab.yoff[npy];
+  const int g = itype % 10;
+  const double sgn = itype > 10 ? -1. : 1.;
+  const int wrow = ii + 2 * mhl, nrow = jj + 2 * nhl;
+  int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= wrow * nrow) return;
+  const int i = t % wrow + 1 - mhl, j = t / wrow + 1 - nhl;
+  const int ig = tab.i0[py * npx + px] + i, jg = tab.yoff[py] + j;
+  bool land = false, flip = false;
+  int iw = ig;
+  if (i < 1) {
+    if (!has_w) land = true;
+    else if (ig < 1) iw = ig + itdm;
+  } else if (i > ii) {
+    // open east edge: the east face (column ii+1) in the halo rows is a column of phase 1 like 1..ii -- its coastal u- and
+    // q-points hold values of the rows below / above (comm_rccl.hip: the segment tables reach one column further there)
+    if (!has_e) land = !(i == ii + 1 && (j < 1 || j > jj) && ig <= itdm);
+    else if (ig > itdm) iw = ig - itdm;
+  }
+  int is = iw, js = jg;
+  if (jg < 1) {
+    if (ns_per) js = jg + jtdm;
+    else land = true;
+  } else if (arctic && jg >= jtdm) {
+    if (!land) {
+      const int d = jg - jtdm;
+      if (g == 1 || g == 3) {                                              // p-, u-grid
+        is = g == 1 ? itdm - (iw - 1) % itdm : (itdm - (iw - 1)) % itdm + 1;
+        js = jtdm - 1 - d;
+        flip = true;
+      } else if (d > 0 || iw > itdm / 2) {                                 // q-, v-grid
+        is = g == 2 ? (itdm - (iw - 1)) % itdm + 1 : itdm - (iw - 1) % itdm;
+        js = jtdm - d;
+        flip = true;
+      }
+    }
+  } else if (jg > jtdm) {
+    if (ns_per) js = jg - jtdm;
+    else land = true;
+  }
+  if (!land && !flip && i >= 1 && i <= ii && j >= 1 && j <= jj) return;  // interior point, not a target
+  int q = -1, qy = 0;
+  if (!land) {
+    while (qy + 1 < npy && js > tab.yoff[qy + 1]) qy++;
+    q = rag_owner(tab.i0, tab.ii, qy * npx, npx, is);
+    if (q < 0) {
+      // The u- and q-points on the east face of a tile whose east edge is open (column end+1) belong to no tile, yet hold
+      // what that tile computes there (barotp's coastal pvtrop): they are read from its halo column ii+1, which its own
+      // update leaves alone.
+      for (int t2 = qy * npx; t2 < qy * npx + npx; t2++)
+        if (tab.ii[t2] > 0 && tab.i0[t2] + tab.ii[t2] == is - 1) q = t2;
+      if (q < 0) land = true;                                              // over no tile of that row
+    }
+  }
+  // A corner over no tile of the next row: it travels with the E-W strip all the same (phy/mod_xc.F90:3131-3178), so it
+  // is what the E / W neighbour holds there after its own phase 1 -- the value that neighbour kept, read from its halo row
+  // (its update does not write that point, for the same reason).  Thus both transports leave the same value.
+  const int nb = i < 1 ? wq : (i > ii ? eq : -1);
+  if (land && !flip && nb >= 0 && (j < 1 || j > jj) && ((jg >= 1 && jg <= jtdm) || ns_per)) {
+    const int sni = tab.ii[nb] + 2 * NBDY;
+    const size_t snp = (size_t)sni * (jj + 2 * NBDY);
+    const double *src = tab.p[nb];
+    const size_t so = (size_t)(iw - tab.i0[nb] + NBDY - 1) + (size_t)sni * (j + NBDY - 1), dst = IDX(V, i, j);
+    for (int k = blockIdx.y; k < nlev; k += gridDim.y) a[dst + (size_t)k * V.nplane] = src[so + (size_t)k * snp];
+    return;
+  }
+  // Land inside the domain that no tile delivers: the reference writes vland there.  Here the point keeps what it holds
+  // ("Ragged tile tables"): on the east face of an open edge that is a value the tile computed itself --
+  // barotp's coastal pvtrop at column ii+1 -- and the single tile keeps it too.  vland stays for what lies beyond a closed
+  // edge of the domain, as on a single tile (and as comm_rccl.hip: k_unpack_ew_keep).
+  if (land && ((jg >= 1 && jg <= jtdm) || ns_per) && ((ig >= 1 && ig <= itdm) || ew_per)) return;
+  const double *src = land ? a : tab.p[q];
+  const int sni = land ? 0 : tab.ii[q] + 2 * NBDY, snj = tab.yoff[qy + 1] - tab.yoff[qy] + 2 * NBDY;
+  const size_t snp = (size_t)sni * snj;
+  const size_t dst = IDX(V, i, j);
+  const size_t so = land ? 0 : (size_t)(is - tab.i0[q] + NBDY - 1) + (size_t)sni * (js - tab.yoff[qy] + NBDY - 1);
+  for (int k = blockIdx.y; k < nlev; k += gridDim.y) {
+    const double v = land ? V.P.vland : (flip ? sgn * src[so + (size_t)k * snp] : src[so + (size_t)k * snp]);
+    a[dst + (size_t)k * V.nplane] = v;
+  }
+}
+
 // ---- the arctic rule for tiles that cannot read each other's memory (one process per GPU) ---------------------
 // Every tile of the top row packs its last `nrows` = nhl+2 interior rows (the only rows the fold reads: jtdm-1-nhl
 // .. jtdm) into a strip [level][row][i]; the strips of the whole row are brought together (RCCL send/recv between
@@ -235,9 +342,69 @@ void arctic_pack_launch(blomgpu_ctx *c, hipStream_t st, double *const *fields, i
 #include <pthread.h>
 struct TileGroup {
   int npx, npy;
-  std::vector<blomgpu_ctx *> tiles;      // index py*npx + px
+  std::vector<blomgpu_ctx *> tiles;      // index py*npx + px (nullptr: a tile the table eliminated)
   pthread_barrier_t bar;
+  TileTable tab;                         // blomgpu_group_create_table with a ragged table
+  bool ragged = false;
 };
+
+bool TileTable::tensor_product() const {
+  for (int n = 0; n < npy; n++)
+    for (int m = 0; m < npx; m++) {
+      const int q = n * npx + m;
+      if (ii[q] <= 0 || i0[q] != i0[m] || ii[q] != ii[m]) return false;
+      if (i0[q] != (m ? i0[q - 1] + ii[q - 1] : 0)) return false;
+    }
+  return i0[npx - 1] + ii[npx - 1] == itdm;
+}
+void TileTable::ew_neighbours(int px, int py, bool periodic, int *west, int *east) const {
+  const int r = py * npx;
+  int first = -1, last = -1, w = -1, e = -1;
+  for (int m = 0; m < npx; m++)
+    if (ii[r + m] > 0) {
+      if (first < 0) first = m;
+      last = m;
+      if (m < px) w = m;
+      if (m > px && e < 0) e = m;
+    }
+  const int me = r + px;
+  if (w >= 0 && i0[r + w] + ii[r + w] != i0[me]) w = -1;                 // is the left tile touching this one?
+  if (e >= 0 && i0[me] + ii[me] != i0[r + e]) e = -1;
+  const bool wraps = periodic && i0[r + first] == 0 && i0[r + last] + ii[r + last] == itdm;
+  if (px == first && wraps) w = last;
+  if (px == last && wraps) e = first;
+  *west = w; *east = e;
+}
+const char *tiletable_build(int npx, int npy, int itdm, int jtdm, const int *i0_pe, const int *ii_pe, const int *j0_pe,
+                            const int *jj_pe, TileTable *out) {
+  if (npx < 1 || npy < 1 || !i0_pe || !ii_pe || !j0_pe || !jj_pe) return "tile table: bad tile grid";
+  if (npx > XCT_MAXDIM || npy > XCT_MAXDIM || npx * npy > XCT_MAXTILES) return "tile table: too many tiles";
+  TileTable &T = *out;
+  T.npx = npx; T.npy = npy; T.itdm = itdm; T.nranks = 0;
+  T.i0.assign(i0_pe, i0_pe + npx * npy); T.ii.assign(ii_pe, ii_pe + npx * npy);
+  T.j0.assign(j0_pe, j0_pe + npy); T.jj.assign(jj_pe, jj_pe + npy);
+  T.rank.assign((size_t)npx * npy, -1);
+  if (T.j0[0] != 0) return "xcspmd: decomposition has wrong j0_pe";
+  for (int n = 0; n < npy; n++) {
+    if (n && T.j0[n] != T.j0[n - 1] + T.jj[n - 1]) return "xcspmd: decomposition is non-contiguous";
+    if (T.jj[n] < NBDY) return "xcspmd: a tile row must be at least nbdy points high";
+    int end = 0, any = 0;
+    for (int m = 0; m < npx; m++) {
+      const int q = n * npx + m;
+      if (T.ii[q] < 0) return "xcspmd: negative tile width";
+      if (T.ii[q] == 0) continue;
+      if (T.ii[q] < NBDY) return "xcspmd: a tile must be at least nbdy points wide";
+      if (T.i0[q] < end) return "xcspmd: the tiles of a row overlap or are out of order";
+      end = T.i0[q] + T.ii[q];
+      T.rank[q] = T.nranks++;
+      any = 1;
+    }
+    if (!any) return "xcspmd: decomposition has an empty row";
+    if (end > itdm) return "xcspmd: a tile row reaches beyond itdm";
+  }
+  if (T.j0[npy - 1] + T.jj[npy - 1] != jtdm) return "xcspmd: decomposition has wrong jj_pe";
+  return nullptr;
+}
 
 int ctx_locate_ptr(const blomgpu_ctx *c, const double *p, size_t *offset) {
   for (int f = 0; f < NF_REAL; f++) {
@@ -271,6 +438,32 @@ static int xctilr_group(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl, i
   // a level offset inside the owner's array: its planes have their own size
   const size_t lev = off / h.nplane;
   if (off % h.nplane) return ctx_fail(c, "xctilr: pointer is not the start of a plane");
+  if (T.tab) {                                      // ragged table: the reference's touching rule, owners looked up per tile row
+    const TileTable &R = *T.tab;
+    RagTab rt;
+    for (int q = 0; q < XCT_MAXTILES; q++) {
+      const blomgpu_ctx *o = q < T.npx * T.npy ? G->tiles[(size_t)q] : nullptr;
+      rt.p[q] = o ? located_base(o, fid) + lev * o->h.nplane : nullptr;
+      rt.i0[q] = o ? R.i0[q] : 0;
+      rt.ii[q] = o ? R.ii[q] : 0;
+    }
+    for (int q = 0; q <= XCT_MAXDIM; q++) rt.yoff[q] = q < T.npy ? R.j0[q] : h.jtdm;
+    int w = -1, e = -1;
+    R.ew_neighbours(T.px, T.py, ew_periodic(h.nreg), &w, &e);
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // every tile's interior must be complete before anyone gathers
+    pthread_barrier_wait(&G->bar);
+    const int nt = (h.ii + 2 * mhl) * (h.jj + 2 * nhl);
+    dim3 grid((nt + 255) / 256, nlev > 64 ? 64 : nlev);
+    {
+      TimeScope ts(c, "halo_gather");                // with the option "timing": tools/gpu_halo_ragged.py
+      hipLaunchKernelGGL(k_xctilr_tiles_ragged, grid, dim3(256), 0, c->stream, c->d, a, rt, T.npx, T.npy, T.px, T.py, nlev, mhl, nhl,
+                         itype, h.itdm, w >= 0 ? T.py * T.npx + w : -1, e >= 0 ? T.py * T.npx + e : -1, ew_periodic(h.nreg) ? 1 : 0, ns_periodic(h.nreg) ? 1 : 0, fold ? 1 : 0);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));      // ... and nobody may go on modifying its interior before all have read
+    pthread_barrier_wait(&G->bar);
+    return 0;
+  }
   TileTab tab;
   for (int q = 0; q < XCT_MAXTILES; q++) {
     if (q >= T.npx * T.npy) { tab.p[q] = nullptr; continue; }
@@ -285,8 +478,11 @@ static int xctilr_group(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl, i
   pthread_barrier_wait(&G->bar);
   const int nt = (h.ii + 2 * mhl) * (h.jj + 2 * nhl);
   dim3 grid((nt + 255) / 256, nlev > 64 ? 64 : nlev);
-  hipLaunchKernelGGL(k_xctilr_tiles, grid, dim3(256), 0, c->stream, c->d, a, tab, T.npx, T.npy, T.px, T.py, nlev, mhl, nhl, itype,
-                     ew_periodic(h.nreg) ? 1 : 0, ns_periodic(h.nreg) ? 1 : 0, fold ? 1 : 0);
+  {
+    TimeScope ts(c, "halo_gather");                  // records only with the option "timing"
+    hipLaunchKernelGGL(k_xctilr_tiles, grid, dim3(256), 0, c->stream, c->d, a, tab, T.npx, T.npy, T.px, T.py, nlev, mhl, nhl, itype,
+                       ew_periodic(h.nreg) ? 1 : 0, ns_periodic(h.nreg) ? 1 : 0, fold ? 1 : 0);
+  }
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipStreamSynchronize(c->stream));      // ... and nobody may go on modifying its interior before all have read
   pthread_barrier_wait(&G->bar);
@@ -324,6 +520,10 @@ static int xctilr_arctic_strips(blomgpu_ctx *c, double *a, int nlev, int mhl, in
   const DevView &h = c->h;
   const Tiling &T = c->tiling;
   if (T.npx > XCT_MAXTILES) return ctx_fail(c, "xctilr: too many tile columns for the arctic strips");
+  if (T.tab)
+    for (int q = 0; q < T.npx; q++)
+      if (T.tab->ii[(size_t)(T.npy - 1) * T.npx + q] <= 0)
+        return ctx_fail(c, "xctilr: the arctic strips are built for a complete top tile row (no eliminated twin tiles)");
   if (int rc = xctilr_plain(c, a, nlev, mhl, nhl)) return rc;
   const bool top = T.py == T.npy - 1;
   const int nrows = nhl + 2;
@@ -603,8 +803,36 @@ int blomgpu_group_create(int npx, int npy, TileGroup **out) {
   *out = G;
   return 0;
 }
+// The same with the general tile table of xcspmd (phy/mod_xc.F90:1332-1720; blomgpu.h).  A tensor-product table gives
+// exactly the group of blomgpu_group_create; a ragged one has a thread (and a barrier seat) per non-empty tile only.
+int blomgpu_group_create_table(int npx, int npy, int itdm, int jtdm, const int *i0_pe, const int *ii_pe, const int *j0_pe,
+                               const int *jj_pe, TileGroup **out) {
+  TileTable tab;
+  *out = nullptr;
+  if (const char *msg = tiletable_build(npx, npy, itdm, jtdm, i0_pe, ii_pe, j0_pe, jj_pe, &tab)) {
+    ctx_fail(nullptr, msg);
+    return 1;
+  }
+  if (tab.tensor_product()) return blomgpu_group_create(npx, npy, out);
+  TileGroup *G = new TileGroup();
+  G->npx = npx; G->npy = npy;
+  G->tiles.assign((size_t)npx * npy, nullptr);
+  G->tab = tab;
+  G->ragged = true;
+  pthread_barrier_init(&G->bar, nullptr, tab.nranks);
+  *out = G;
+  return 0;
+}
 int blomgpu_group_attach(TileGroup *G, blomgpu_ctx *c, int px, int py) {
   if (px < 0 || px >= G->npx || py < 0 || py >= G->npy) return ctx_fail(c, "group_attach: tile index out of range");
+  if (G->ragged) {
+    const int q = py * G->npx + px;
+    const DevView &h = c->h;
+    if (G->tab.ii[q] <= 0) return ctx_fail(c, "group_attach: the table has eliminated this tile");
+    if (h.i0 != G->tab.i0[q] || h.ii != G->tab.ii[q] || h.j0 != G->tab.j0[py] || h.jj != G->tab.jj[py] || h.itdm != G->tab.itdm)
+      return ctx_fail(c, "group_attach: the context's window (i0, j0, idm, jdm) is not tile (px,py) of the table");
+    c->tiling.tab = &G->tab;
+  }
   G->tiles[(size_t)py * G->npx + px] = c;
   c->tiling.npx = G->npx; c->tiling.npy = G->npy; c->tiling.px = px; c->tiling.py = py; c->tiling.group = G;
   return 0;
@@ -698,7 +926,8 @@ __global__ void k_crc_strips_tile(const DevView *__restrict__ Vp, const double *
   const int g2 = min(g1 + 2 * NBDY, V.itdm);
   unsigned crc8p = 0;
   for (int ig = g1; ig <= g2; ig++) {
-    const int i = ig - V.i0;                                     // 1-nbdy .. ii+nbdy by the ownership rule
+    const int i = ig - V.i0;                                     // 1-nbdy .. ii+nbdy by the ownership rule ...
+    if (i < 1 - NBDY || i > V.ii + NBDY) continue;               // ... but for a strip centred in the land beside a ragged tile
     if (mask[IDX(V, i, j)] != 1) continue;
     unsigned crc = ~crc8p;
     for (int k = 0; k < nlev; k++) {
@@ -716,10 +945,20 @@ int st_crc_strips(blomgpu_ctx *c, double *base, int nlev, int itype, unsigned *o
   const int *mask = g == 1 ? h.m[I_ip] : g == 2 ? h.m[I_iq] : g == 3 ? h.m[I_iu] : h.m[I_iv];
   // strips whose centre column (clipped to the domain) lies in i0+1 .. i0+ii
   const int ntot = (h.itdm + W - 1) / W;
+  // ragged table: a tile without a touching neighbour on a side also owns the strips centred within nbdy columns of
+  // that edge (phy/mod_xc.F90:1686-1710) -- their other columns are land, or nobody's
+  bool open_w = false, open_e = false;
+  if (c->tiling.tab) {
+    int w = -1, e = -1;
+    c->tiling.tab->ew_neighbours(c->tiling.px, c->tiling.py, false, &w, &e);
+    open_w = w < 0; open_e = e < 0;
+  }
   int l0 = -1, ns = 0;
   for (int l = 0; l < ntot; l++) {
     const int ctr = min(1 + l * W + NBDY, h.itdm);
-    if (ctr > h.i0 && ctr <= h.i0 + h.ii) { if (l0 < 0) l0 = l; ns++; }
+    const bool mine = (ctr > h.i0 && ctr <= h.i0 + h.ii) || (open_w && ctr > h.i0 - NBDY && ctr <= h.i0) ||
+                      (open_e && ctr > h.i0 + h.ii && ctr <= h.i0 + h.ii + NBDY);
+    if (mine) { if (l0 < 0) l0 = l; ns++; }
   }
   *l0_out = l0 < 0 ? 0 : l0;
   *ns_out = ns;
@@ -863,6 +1102,45 @@ __global__ __launch_bounds__(64) void k_xcsum_rows_tiles(XcsTab tab, int npx, in
   if (threadIdx.x == 0) rowsum[j - 1] = sum8;
 }
 
+// ragged table: a row's points are looked up in that row's own cut; points over no tile are land and add nothing
+struct XcsRag {
+  const double *a[XCT_MAXTILES];
+  const int *m[XCT_MAXTILES];
+  int i0[XCT_MAXTILES], ii[XCT_MAXTILES];
+  int yoff[XCT_MAXDIM + 1];
+};
+__global__ __launch_bounds__(64) void k_xcsum_rows_tiles_ragged(XcsRag tab, int npx, int npy, int itdm, int jtdm, int skip_seam,
+                                                               double *__restrict__ rowsum) {
+  __shared__ double strip[64];
+  const int j = blockIdx.x + 1, W = 2 * NBDY + 1;
+  const bool dead = skip_seam && j >= jtdm;
+  int py = 0;
+  while (py + 1 < npy && j > tab.yoff[py + 1]) py++;
+  const int nstrip = (itdm + W - 1) / W;
+  double sum8 = 0.;
+  for (int s0 = 0; s0 < nstrip; s0 += 64) {
+    const int sidx = s0 + (int)threadIdx.x;
+    double sum8p = 0.;
+    if (sidx < nstrip) {
+      const int i1 = 1 + sidx * W, ie = i1 + 2 * NBDY < itdm ? i1 + 2 * NBDY : itdm;
+      for (int i = i1; i <= ie; i++) {
+        const int q = rag_owner(tab.i0, tab.ii, py * npx, npx, i);
+        if (q < 0) continue;
+        const size_t x = (size_t)(j - tab.yoff[py] + NBDY - 1) * (tab.ii[q] + 2 * NBDY) + (size_t)(i - tab.i0[q] + NBDY - 1);
+        if (!dead && tab.m[q][x] == 1) sum8p = sum8p + tab.a[q][x];
+      }
+    }
+    strip[threadIdx.x] = sum8p;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int n = nstrip - s0 < 64 ? nstrip - s0 : 64;
+      for (int q = 0; q < n; q++) sum8 = sum8 + strip[q];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) rowsum[j - 1] = sum8;
+}
+
 int rccl_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot);      // comm_rccl.hip
 
 static int xcsum_group(blomgpu_ctx *c, const double *a, int itype, int slot) {
@@ -875,6 +1153,27 @@ static int xcsum_group(blomgpu_ctx *c, const double *a, int itype, int slot) {
   if (fid < 0 || off % h.nplane) return ctx_fail(c, "xcsum: pointer is not a plane of a registered field");
   const size_t lev = off / h.nplane;
   const int g = itype % 10, mid = g == 1 ? I_ip : g == 2 ? I_iq : g == 3 ? I_iu : I_iv;
+  if (T.tab) {
+    const TileTable &R = *T.tab;
+    XcsRag rt;
+    for (int q = 0; q < XCT_MAXTILES; q++) {
+      const blomgpu_ctx *o = q < T.npx * T.npy ? G->tiles[(size_t)q] : nullptr;
+      rt.a[q] = o ? located_base(o, fid) + lev * o->h.nplane : nullptr;
+      rt.m[q] = o ? o->h.m[mid] : nullptr;
+      rt.i0[q] = o ? R.i0[q] : 0;
+      rt.ii[q] = o ? R.ii[q] : 0;
+    }
+    for (int q = 0; q <= XCT_MAXDIM; q++) rt.yoff[q] = q < T.npy ? R.j0[q] : h.jtdm;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    pthread_barrier_wait(&G->bar);
+    hipLaunchKernelGGL(k_xcsum_rows_tiles_ragged, dim3(h.jtdm), dim3(64), 0, c->stream, rt, T.npx, T.npy, h.itdm, h.jtdm,
+                       (g == 1 && h.nreg == 2) ? 1 : 0, c->xcsum_buf + 1);
+    hipLaunchKernelGGL(k_xcsum_total, dim3(1), dim3(256), sizeof(double) * (size_t)h.jtdm, c->stream, c->xcsum_buf + 1, h.jtdm, c->xcsum_dev + slot);
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    pthread_barrier_wait(&G->bar);
+    return 0;
+  }
   XcsTab tab;
   for (int q = 0; q < XCT_MAXTILES; q++) {
     if (q >= T.npx * T.npy) { tab.a[q] = nullptr; tab.m[q] = nullptr; tab.ni[q] = 0; continue; }

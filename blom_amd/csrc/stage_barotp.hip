@@ -461,7 +461,7 @@ int st_barotp_on(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n,
         // single tile: the pair kernel applies the halo rule while loading; otherwise exchange first
         // RCCL tiles along i: the received strips stay in the transport's buffers and the kernel loads its
         // E/W rim from there (c->barotp_rimbuf), saving the unpack launch of every exchange
-        const bool rimbuf = c->tiling.rccl && c->barotp_rimbuf && c->tiling.npy == 1 && !ovl && h.nreg != 2;
+        const bool rimbuf = c->tiling.rccl && c->barotp_rimbuf && c->tiling.npy == 1 && !ovl && h.nreg != 2 && !c->tiling.tab;
         // (single tile with the arctic patch: the pair kernel applies xctilr's seam rule while loading, before odd substeps)
         if ((arctic1 ? odd && c->tiling.multi() : c->tiling.multi()) && !halo_done) {
           if (rimbuf) { if (int rc = bt_pair_halo_landed(c, set, &landed)) return rc; }

@@ -150,6 +150,29 @@ module mod_blomgpu
       type(c_ptr), value :: c, g
       integer(c_int), intent(in) :: isizes(*), jsizes(*)
     end function
+    ! the general tile table of xcspmd (phy/mod_xc.F90:1332-1720): i0_pe / ii_pe hold npx*npy entries, m fastest
+    integer(c_int) function blomgpu_rccl_init_table(c, id128, rank, npx, npy, i0_pe, ii_pe, j0_pe, jj_pe) &
+        bind(C, name='blomgpu_rccl_init_table')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: id128(128)
+      integer(c_int), value :: rank, npx, npy
+      integer(c_int), intent(in) :: i0_pe(*), ii_pe(*), j0_pe(*), jj_pe(*)
+    end function
+    integer(c_int) function blomgpu_rccl_attach_barotp_table(c, g, npx, npy, i0_pe, ii_pe, j0_pe, jj_pe) &
+        bind(C, name='blomgpu_rccl_attach_barotp_table')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, g
+      integer(c_int), value :: npx, npy
+      integer(c_int), intent(in) :: i0_pe(*), ii_pe(*), j0_pe(*), jj_pe(*)
+    end function
+    integer(c_int) function blomgpu_group_create_table(npx, npy, itdm, jtdm, i0_pe, ii_pe, j0_pe, jj_pe, grp) &
+        bind(C, name='blomgpu_group_create_table')
+      import :: c_ptr, c_int
+      integer(c_int), value :: npx, npy, itdm, jtdm
+      integer(c_int), intent(in) :: i0_pe(*), ii_pe(*), j0_pe(*), jj_pe(*)
+      type(c_ptr), intent(out) :: grp
+    end function
     integer(c_int) function blomgpu_rccl_finalize(c) bind(C, name='blomgpu_rccl_finalize')
       import :: c_ptr, c_int
       type(c_ptr), value :: c
@@ -164,7 +187,7 @@ module mod_blomgpu
   end interface
 
   public :: gpu_init_tile, gpu_upload_global, gpu_upload_int_global, gpu_nlev_global, gpu_rccl_unique_id, gpu_rccl_init, &
-            gpu_attach_barotp_global
+            gpu_attach_barotp_global, gpu_rccl_init_table, gpu_attach_barotp_table
   public :: gpu_init, gpu_finalize, gpu_set, gpu_upload, gpu_upload_int, gpu_download, gpu_nlev, &
             gpu_halo, gpu_chksum, gpu_sync, gpu_xcsum, budget_sums, gpu_budget
   public :: stage6
@@ -257,6 +280,22 @@ contains
   subroutine gpu_attach_barotp_global(isizes, jsizes)
     integer, intent(in) :: isizes(:), jsizes(:)
     call gpu_check(blomgpu_rccl_attach_barotp_global(ctx, gctx, isizes, jsizes), 'gpu_attach_barotp_global')
+  end subroutine
+
+  ! the same two with the general tile table of xcspmd (ragged rows, eliminated tiles): i0_pe(m,n), ii_pe(m,n) as the
+  ! reference holds them (phy/mod_xc.F90:1332-1720), j0_pe(n), jj_pe(n); rank counts the non-empty tiles, m fastest
+  subroutine gpu_rccl_init_table(id, rank, i0_pe, ii_pe, j0_pe, jj_pe)
+    character(kind=c_char), intent(in) :: id(128)
+    integer, intent(in) :: rank, i0_pe(:,:), ii_pe(:,:), j0_pe(:), jj_pe(:)
+    call gpu_check(blomgpu_rccl_init_table(ctx, id, rank, size(ii_pe, 1), size(ii_pe, 2), i0_pe, ii_pe, j0_pe, jj_pe), &
+                   'gpu_rccl_init_table')
+    on_rccl = .true.
+  end subroutine
+
+  subroutine gpu_attach_barotp_table(i0_pe, ii_pe, j0_pe, jj_pe)
+    integer, intent(in) :: i0_pe(:,:), ii_pe(:,:), j0_pe(:), jj_pe(:)
+    call gpu_check(blomgpu_rccl_attach_barotp_table(ctx, gctx, size(ii_pe, 1), size(ii_pe, 2), i0_pe, ii_pe, j0_pe, jj_pe), &
+                   'gpu_attach_barotp_table')
   end subroutine
 
   subroutine gpu_finalize()

@@ -226,6 +226,19 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_rccl_attach_barotp_global(self.ctx, glob.ctx, a, b))
         self._bt_global = glob               # keep it alive as long as the tile
 
+    def rccl_init_layout(self, id128, rank, layout):
+        """join the communicator as rank `rank` of a blom_amd.tiles.TileLayout, ragged tables included
+        (blomgpu_rccl_init_table; a tensor-product layout takes the path of rccl_init_2d)"""
+        buf = (C.c_char * 128).from_buffer_copy(bytes(id128))
+        t = [a.ctypes.data_as(C.c_void_p) for a in layout.tables()]
+        self._chk(self.lib.blomgpu_rccl_init_table(self.ctx, buf, rank, layout.npx, layout.npy, *t))
+
+    def rccl_attach_barotp_layout(self, glob, layout):
+        """rccl_attach_barotp_global for a TileLayout: the windows of its non-empty tiles, in rank order"""
+        t = [a.ctypes.data_as(C.c_void_p) for a in layout.tables()]
+        self._chk(self.lib.blomgpu_rccl_attach_barotp_table(self.ctx, glob.ctx, layout.npx, layout.npy, *t))
+        self._bt_global = glob
+
     def rccl_crc(self, name, lev0, nlev, itype=1):
         """xccrc of the whole decomposed domain over the RCCL ranks (a collective: every rank calls it, every rank gets the
         value); on a context without RCCL, crc()"""
@@ -260,11 +273,23 @@ class TileGroup:
     """Several tiles of one domain on ONE device in one process (one host thread per tile): the
     in-process halo transport used to check decomposition independence (tests)."""
 
-    def __init__(self, npx, npy):
+    def __init__(self, npx, npy, layout=None):
+        """layout: a blom_amd.tiles.TileLayout whose table the group follows (blomgpu_group_create_table) -- needed for a
+        ragged one, where only the non-empty tiles are attached and run a thread"""
         self.lib = load_library()
         self.h = C.c_void_p()
-        self.lib.blomgpu_group_create(npx, npy, C.byref(self.h))
+        if layout is None:
+            self.lib.blomgpu_group_create(npx, npy, C.byref(self.h))
+        else:
+            assert (layout.npx, layout.npy) == (npx, npy)
+            t = [a.ctypes.data_as(C.c_void_p) for a in layout.tables()]
+            if self.lib.blomgpu_group_create_table(npx, npy, layout.itdm, layout.jtdm, *t, C.byref(self.h)):
+                raise BlomGpuError(self.lib.blomgpu_last_error(None).decode())
         self.npx, self.npy = npx, npy
+
+    @classmethod
+    def for_layout(cls, layout):
+        return cls(layout.npx, layout.npy, layout)
 
     def attach(self, gpu, px, py):
         gpu._chk(self.lib.blomgpu_group_attach(self.h, gpu.ctx, px, py))

@@ -287,3 +287,48 @@ def exchange_arctic_host(a, idm, jdm, mhl, nhl, rank, npx, npy, itype):
             qx = (src - 1) // idm
             a[:, 3 + jdm + d, 3 + i] = sgn * strips[qx][:, nrows - 1 - back, src - qx * idm - 1]
     return a
+
+
+def tile_of_rank(layout, rank):
+    """window of rank `rank` in a blom_amd.tiles.TileLayout (ragged tables included: ranks number the non-empty tiles, m fastest,
+    phy/mod_xc.F90:1545-1560) -- what BlomGpu(...) and rccl_init_layout need"""
+    if not (0 <= rank < layout.nranks):
+        raise ValueError(f"rank {rank} outside a layout of {layout.nranks} tiles")
+    px, py = layout.rank_tile(rank)
+    i0, j0, ii, jj = layout.tile(px, py)
+    return dict(itdm=layout.itdm, jtdm=layout.jtdm, i0=i0, j0=j0, idm=ii, jdm=jj, px=px, py=py, npx=layout.npx, npy=layout.npy)
+
+
+def neighbours_table(layout, rank, periodic_i, periodic_j):
+    """Host statement of the neighbour rule of blomgpu_rccl_init_table (phy/mod_xc.F90:1726-1990): (west, east, south, north)
+    with west / east the rank of the previous / next non-empty tile of the row if it TOUCHES this one (a row wraps only if it
+    starts at 0 and ends at itdm), else -1, and south / north lists of (rank, first local column, width), one entry per tile of
+    the row below / above that shares columns with this one."""
+    px, py = layout.rank_tile(rank)
+    row = layout.rows[py]
+    i0, ii = row[px]
+    live = [m for m in range(layout.npx) if row[m][1] > 0]
+    k = live.index(px)
+    west = live[k - 1] if k > 0 else -1
+    east = live[k + 1] if k + 1 < len(live) else -1
+    if west >= 0 and row[west][0] + row[west][1] != i0:
+        west = -1
+    if east >= 0 and i0 + ii != row[east][0]:
+        east = -1
+    if periodic_i and row[live[0]][0] == 0 and row[live[-1]][0] + row[live[-1]][1] == layout.itdm:
+        west = live[-1] if k == 0 else west
+        east = live[0] if k == len(live) - 1 else east
+
+    def segments(qy):
+        if not (0 <= qy < layout.npy):
+            if not periodic_j:
+                return []
+            qy %= layout.npy
+        out = []
+        for m, (q0, qq) in enumerate(layout.rows[qy]):
+            lo, hi = max(q0, i0), min(q0 + qq, i0 + ii)
+            if qq > 0 and hi > lo:
+                out.append((layout.tile_rank(m, qy), lo - i0 + 1, hi - lo))
+        return out
+    return (layout.tile_rank(west, py) if west >= 0 else -1, layout.tile_rank(east, py) if east >= 0 else -1,
+            segments(py - 1), segments(py + 1))

@@ -226,6 +226,26 @@ int  blomgpu_rccl_crc(blomgpu_ctx *, const char *name, int lev0, int nlev, int i
 int  blomgpu_rccl_finalize(blomgpu_ctx *);
 typedef struct TileGroup blomgpu_group;
 int  blomgpu_group_create(int npx, int npy, blomgpu_group **out);
+/* Ragged tile layouts: the general table of xcspmd (phy/mod_xc.F90:1332-1720) as the reference's patch.input files give it --
+ * every tile row with its own cut, tiles shrunk to their sea points, all-land tiles eliminated.  i0_pe[npy*npx], ii_pe[npy*npx]
+ * (m fastest; 0-based first column minus one as i0_pe(m,n), ii_pe = 0: eliminated), j0_pe[npy], jj_pe[npy].  Ranks number the
+ * non-empty tiles only, m fastest, then n (:1545-1560).  The entries above are the tensor-product special case and keep their
+ * paths: a tensor-product table given here is passed on to them.  What a ragged table changes in xctilr:
+ *  - E-W (:1726-1745, :3131-3178): the neighbour is the previous / next non-empty tile of the row, and only if it touches this
+ *    one; otherwise the halo is vland.  A row wraps periodically only if it starts at 0 and ends at itdm (:1591-1594).
+ *  - N-S (:1747-1990, :3036-3106): a tile's columns are covered by several tiles of the row below / above, one segment each;
+ *    columns over no tile are vland.  With the arctic patch (nreg = 2) the top row consists of equal tiles (:1480-1506);
+ *    eliminated twin tiles there are refused by the RCCL transport.
+ *  - xcsum / xccrc: the 9-column strips are anchored in global columns; a tile without a touching neighbour also owns the
+ *    strips centred within nbdy columns beyond that edge (:1686-1710).
+ * Both transports apply the same rule point for point.  blomgpu_group_create_table needs the domain's itdm, jtdm (no context
+ * exists yet); the others take them from the context. */
+int  blomgpu_rccl_init_table(blomgpu_ctx *, const void *id128, int rank, int npx, int npy, const int *i0_pe, const int *ii_pe,
+                             const int *j0_pe, const int *jj_pe);
+int  blomgpu_rccl_attach_barotp_table(blomgpu_ctx *tile, blomgpu_ctx *global, int npx, int npy, const int *i0_pe,
+                                      const int *ii_pe, const int *j0_pe, const int *jj_pe);
+int  blomgpu_group_create_table(int npx, int npy, int itdm, int jtdm, const int *i0_pe, const int *ii_pe, const int *j0_pe,
+                                const int *jj_pe, blomgpu_group **out);
 int  blomgpu_group_attach(blomgpu_group *, blomgpu_ctx *, int px, int py);
 int  blomgpu_group_destroy(blomgpu_group *);
 
