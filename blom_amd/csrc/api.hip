@@ -6,6 +6,7 @@
 #include "sin_libm.h"
 #include "atan2_libm.h"
 #include <cstring>
+#include <string_view>
 
 static thread_local std::string g_err;
 
@@ -45,7 +46,7 @@ void ctx_sync_view(blomgpu_ctx *c) {
 bool ctx_overlap_on(const blomgpu_ctx *c) {
   // not while stage timers run (their HIP events bracket launches on the context's stream), not on the hybrid coordinates
   // (their sequence has its own second stream inside ale_regrid_remap)
-  return c->overlap && c->in_sequence && !c->timing && c->h.P.vcoord_tag == 1 && c->side != nullptr;
+  return c->overlap && c->seq.in_sequence && !c->timing && c->h.P.vcoord_tag == 1 && c->side != nullptr;
 }
 int ctx_side_fork(blomgpu_ctx *c, int ev) {
   HIPCHK(c, hipEventRecord(c->ev_side[ev], c->stream));
@@ -148,6 +149,176 @@ static int ale_reset(blomgpu_ctx *c) {
   const int rc = c->h.P.vcoord_tag != 1 ? ale_check_deferred(c) : 0;
   ale_free(c);
   return rc;
+}
+
+// ---- the option table ------------------------------------------------------------------------------------------------------
+// One row per name that blomgpu_set_real / blomgpu_set_int / blomgpu_set_str accept: its kind (which entry point knows it), where
+// the value lives, what setting it touches, and how it is checked.  The defaults and the comments of the values stand at the
+// members (blomgpu_internal.h: Params, blomgpu_ctx).  Every setter drops the captured graphs, for unknown names too (KEEP_GRAPHS:
+// the one exception).
+enum OptKind { O_REAL, O_INT, O_BOOL, O_STR };      // O_BOOL: set through blomgpu_set_int and stored as v != 0
+enum : unsigned {
+  DIRTY = 1,        // a member of Params: the device view is uploaded again (context members are read by host code only)
+  ALE_RESET = 2,    // the cached ALE structures depend on it
+  READABLE = 4,     // blomgpu_get_real returns it
+  KEEP_GRAPHS = 8,  // selects nothing a captured graph holds
+};
+struct Slot {       // the member a row names, with the member's own type
+  double *d = nullptr; int *i = nullptr; bool *b = nullptr; std::string *s = nullptr;
+  Slot(double &x) : d(&x) {}
+  Slot(int &x) : i(&x) {}
+  Slot(bool &x) : b(&x) {}
+  Slot(std::string &x) : s(&x) {}
+  void put(double v) const { if (d) *d = v; else if (i) *i = (int)v; else *b = v != 0; }
+};
+struct Opt {
+  const char *name;
+  OptKind kind;
+  Slot (*at)(blomgpu_ctx *);          // nullptr: the value is checked and nothing is stored
+  unsigned flags;
+  const char *(*check)(double &v);    // clamps or scales v, or returns the refusal
+  void (*after)(blomgpu_ctx *);       // what else follows from the new value
+  // O_STR: what the refusal says in front of the value, and the accepted words with their codes (none: the string itself is stored)
+  const char *refuse;
+  struct { const char *word; int code; } words[3];
+};
+#define IN_P(m) [](blomgpu_ctx *c) { return Slot(c->h.P.m); }
+#define IN_C(m) [](blomgpu_ctx *c) { return Slot(c->m); }
+#define PR(nm) {#nm, O_REAL, IN_P(nm), DIRTY}
+#define PRR(nm) {#nm, O_REAL, IN_P(nm), DIRTY | READABLE}
+#define PI(nm) {#nm, O_INT, IN_P(nm), DIRTY}
+#define CR(nm) {#nm, O_REAL, IN_C(nm), 0}
+#define CI(nm) {#nm, O_INT, IN_C(nm), 0}
+#define CB(nm) {#nm, O_BOOL, IN_C(nm), 0}
+#define ONE_OR_TWO(msg) [](double &v) -> const char * { return v != 1 && v != 2 ? msg : nullptr; }
+#define LMI(n) {"l" #n "mi", O_INT, [](blomgpu_ctx *c) { return Slot(c->lmi[n - 1]); }, 0, \
+                [](double &v) -> const char * { return v < 1 || v > 12 ? "blomgpu_set_int: l" #n "mi is a month, 1..12" : nullptr; }}
+static const Opt g_opts[] = {
+  // ---- reals ----
+  PRR(baclin), PRR(batrop), PRR(delt1), PRR(dlt), PR(mdv2hi), PR(mdv2lo), PR(mdv4hi), PR(mdv4lo), PR(mdc2hi), PR(mdc2lo),
+  PR(vsc2hi), PR(vsc2lo), PR(vsc4hi), PR(vsc4lo), PR(cbar), PR(cb), PR(cwbdts), PR(cwbdls), PR(wuv1), PR(wuv2), PR(wts1), PR(wts2),
+  PRR(wbaro), PR(bdmc1), PR(bdmc2), PR(iwdfac), PR(nubmin), PR(vland),
+  {"pref", O_REAL, IN_P(pref), DIRTY | READABLE, nullptr, [](blomgpu_ctx *c) { set_eos(c->h.P); }},
+  CR(swamxd), CR(brine_mlbase_frac),                      // phy/mod_swabs.F90:179-183, phy/mod_forcing.F90:63
+  // &DIFFUSION, as far as phy/mod_difest.F90's isopycnic routines read it (phy/mod_diffusion.F90:45-110)
+  CR(egc), CR(eggam), CR(eglsmn), CR(egmndf), CR(egmxdf), CR(egidfq), CR(rhiscf), CR(ri0), CR(tkepf),
+  {"bdml_logc", O_REAL, IN_C(bdml_logc), READABLE},
+  // thermf: mod_forcing's namelist variables, mod_grid's area, mod_time's interpolation weight of the month
+  CR(trxday), CR(srxday), CR(trxdpt), CR(srxdpt), CR(trxlim), CR(srxlim), CR(sref), {"area", O_REAL, IN_C(area), READABLE}, CR(xmi),
+  // mod_mxlayr's and mod_niw's namelist variables (phy/mod_mxlayr.F90:58-68, phy/mod_niw.F90:38-45)
+  CR(rm0), CR(rm5), CR(niwgf), CR(niwbf), CR(niwlf),
+  // mixed layer restratification of eddtra_ale, phy/mod_eddtra.F90:53-94
+  {"ce", O_REAL, IN_C(eddtra_ce), 0}, {"cl", O_REAL, IN_C(eddtra_cl), 0}, CR(tau_mlr), CR(tau_growing_hbl), CR(tau_decaying_hbl),
+  CR(tau_growing_hml), CR(tau_decaying_hml), CR(lfmin), CR(mstar), CR(nstar), CR(wpup_min), CR(mlbl_max_ratio),
+  CR(ale_regrid_nudge_ts), CR(ale_stab_fac_limit), CR(ale_dpvar_fac), CR(ale_smooth_diff_max),
+  {"ale_dpmin_interior", O_REAL, IN_C(ale_dpmin_interior), 0,                        // [m], as in &ALE_REGRID_REMAP (:1352-1353)
+   [](double &v) -> const char * { v = v * 9806.; return nullptr; }},
+  // ---- integers ----
+  {"nstep", O_INT, IN_P(nstep), 0},                       // host-side only (stage_cppm.hip): the device view is not touched
+  PI(lstep), PI(nday_in_year), PI(itriag), PI(itrtke), PI(itrgls), PI(tkeadv), PI(tkeidf), PI(gls), PI(vcoord_tag), PI(ltedtp_opt),
+  PI(bdmtyp), PI(iwdflg), PI(bdmldp), PI(allwet),
+  CB(csdiag), CB(eddf2d), CB(edsprs), CB(edanis), CB(redi3d), CB(edfsmo), CB(rhsctp), CB(difest_live),
+  {"edritp_opt", O_INT, IN_C(edritp_opt), 0, ONE_OR_TWO(" readnml_diffusion: edritp is unsupported!")},   // phy/mod_diffusion.F90:113-116
+  {"edwmth_opt", O_INT, IN_C(edwmth_opt), 0, ONE_OR_TWO(" readnml_diffusion: edwmth is unsupported!")},
+  {"full_physics", O_BOOL, IN_C(full_physics), 0, nullptr, [](blomgpu_ctx *c) { if (c->full_physics) c->live_slopes = true; }},
+  // thermf: mod_forcing's switches (phy/mod_forcing.F90:43-47), mod_time's months of the interpolation, mod_ben02's ntda
+  CB(aptflx), CB(apsflx), CB(ditflx), CB(disflx), CB(srxbal), LMI(1), LMI(2), LMI(3), LMI(4), LMI(5), CI(ntda),
+  // (the stage timers select nothing: a step with them runs plain launches beside the graphs, which stay)
+  {"timing", O_BOOL, IN_C(timing), KEEP_GRAPHS},
+  CI(barotp_fused),
+  {"barotp_tile", O_INT, IN_C(barotp_tile), 0, [](double &v) -> const char * {
+     for (int ok : {0, 3216, 3208, 1608, 4016, 2616, 2615, 4015}) if (v == ok) return nullptr;
+     return "blomgpu_set_int: barotp_tile must be 0, 3216, 3208, 1608, 4016, 2616, 2615 or 4015"; }},
+  CI(barotp_persist), CI(barotp_block), CI(barotp_overlap), CI(barotp_rimbuf), CI(barotp_arctic_fused), CI(barotp_arctic_persist),
+  CI(eddtra_frozen), CI(pgf_uv_pair), CI(pgf_uv_ring), CI(pgf_reuse), CI(pgf_copy_fused), CI(kprof_sel), CI(mom_aw_split),
+  CI(mom_force_aw), CI(convec_nsingle), CI(cmn_nslope_nb), CI(scan_reassoc),
+  {"check_period", O_INT, IN_C(check_period), 0, [](double &v) -> const char * { if (v < 1) v = 1; return nullptr; }},
+  CI(cnsvdi), CI(arctic_strips), CI(use_graph), CI(overlap), CI(phys_dag), CI(mom_early_at), CI(lean_fluxes), CI(tmsmt_fold),
+  CI(tmsmt_ahead), CI(remap_fold), CI(remap_nfirst), CI(halo_overlap), CI(cmnfld1), CI(diapfl_du), CI(live_slopes),
+  CI(momtum_bs), CI(momtum_lds_pad), CI(momtum_order), CI(momtum_chunks_a), CI(momtum_chunks_b), CI(diffus_shfl),
+  {"ale_upper_bndr_ord", O_INT, IN_C(ale_upper_bndr_ord), ALE_RESET}, {"ale_lower_bndr_ord", O_INT, IN_C(ale_lower_bndr_ord), ALE_RESET},
+  CI(ale_k_range_plevel), CI(ale_dktzu), CI(ale_dktzl),
+  {"ale_density_pc_upper_bndr", O_BOOL, IN_C(ale_density_pc_upper), ALE_RESET},
+  {"ale_density_pc_lower_bndr", O_BOOL, IN_C(ale_density_pc_lower), ALE_RESET},
+  {"ale_tracer_pc_upper_bndr", O_BOOL, IN_C(ale_tracer_pc_upper), ALE_RESET},
+  {"ale_tracer_pc_lower_bndr", O_BOOL, IN_C(ale_tracer_pc_lower), ALE_RESET},
+  {"ale_velocity_pc_upper_bndr", O_BOOL, IN_C(ale_velocity_pc_upper), ALE_RESET},
+  {"ale_velocity_pc_lower_bndr", O_BOOL, IN_C(ale_velocity_pc_lower), ALE_RESET},
+  CB(ndiff_surface_align),
+  {"ndiff_rec_per_face", O_INT, IN_C(ndiff_rec_per_face), ALE_RESET, [](double &v) -> const char * { if (v < 0) v = 0; return nullptr; }},
+  // ---- strings: the reference's words, refused in the reference's words (blomgpu_set_str marks the view dirty for every name) ----
+  {"expcnf", O_STR, IN_C(expcnf), 0},
+  {"mlrttp", O_STR, IN_C(mlrttp), 0},                     // resolved (and refused) in mxlayr, phy/mod_mxlayr.F90:197-212
+  {"mommth", O_STR, IN_P(mommth), DIRTY, nullptr, nullptr, " mommth = ", {{"enscon", 0}, {"enecon", 1}, {"enedis", 2}}},   // phy/mod_momtum.F90:815-820
+  {"pgfmth", O_STR, IN_P(pgfmth), DIRTY, nullptr, nullptr, " pgfmth = ", {{"geopotential", 0}, {"dynamic enthalpy", 1}}},   // phy/mod_pgforc.F90:529-534
+  {"advmth", O_STR, IN_P(advmth), DIRTY, nullptr, nullptr, " advmth = ", {{"remap", 0}, {"cppm", 1}}},                      // phy/mod_advect.F90:166-171
+  {"bmcmth", O_STR, IN_P(bmcmth), DIRTY, nullptr, nullptr, " bmcmth = ", {{"uc", 0}, {"dluc", 1}}},                         // phy/mod_pbcor.F90:112-117
+  {"eitmth", O_STR, IN_P(eitmth), DIRTY, nullptr, nullptr, " eitmth = ", {{"intdif", 1}, {"gm", 2}}},                       // phy/mod_diffusion.F90:316-327
+  {"cppm_compatibility", O_STR, IN_C(cppm_compat), 0, nullptr, nullptr, " init_cppm: cppm_compatibility = ", {{"full", 1}, {"partial", 2}}},        // phy/mod_cppm.F90:2524-2535
+  {"cppm_limiting", O_STR, IN_C(cppm_limiting), 0, nullptr, nullptr, " init_cppm: cppm_limiting = ", {{"monotonic", 1}, {"non_oscillatory", 2}}},   // phy/mod_cppm.F90:2536-2548
+  // init_eddtra, phy/mod_eddtra.F90:1773-1806 (bod23: refused with isopyc_bulkml when the stage runs, :1787-1795)
+  {"mlrmth", O_STR, IN_C(mlrmth), 0, nullptr, nullptr, " init_eddtra: mlrmth = ", {{"none", 0}, {"fox08", 1}, {"bod23", 2}}},
+  {"vcoord_type", O_STR, IN_P(vcoord_tag), DIRTY, nullptr, nullptr, " readnml_vcoord: vcoord_type = ",                      // phy/mod_vcoord.F90:908-921
+   {{"isopyc_bulkml", 1}, {"cntiso_hybrid", 2}, {"plevel", 3}}},
+  // &ALE_REGRID_REMAP, phy/mod_ale_regrid_remap.F90:1185-1355 (readnml_ale_regrid_remap; same words, same refusals)
+  {"ale_reconstruction_method", O_STR, IN_C(ale_method), 0, nullptr, nullptr, " readnml_ale_regrid_remap: reconstruction_method = ",
+   {{"plm", 101}, {"ppm", 102}, {"pqm", 103}}},
+  {"ale_regrid_method", O_STR, IN_C(ale_regrid_method), 0, nullptr, nullptr, " readnml_ale_regrid_remap: regrid_method = ", {{"direct", 1}, {"nudge", 2}}},   // :1323-1337
+  {"ale_density_limiting", O_STR, nullptr, 0, nullptr, nullptr, " readnml_ale_regrid_remap: density_limiting = ", {{"monotonic", 0}}},
+  // (the cached reconstruction structures hold the limiter)
+  {"ale_tracer_limiting", O_STR, IN_C(ale_tracer_limiting), ALE_RESET, nullptr, nullptr, " readnml_ale_regrid_remap: tracer_limiting = ",
+   {{"monotonic", 201}, {"non_oscillatory", 203}}},
+  {"ale_velocity_limiting", O_STR, IN_C(ale_velocity_limiting), ALE_RESET, nullptr, nullptr, " readnml_ale_regrid_remap: velocity_limiting = ",
+   {{"monotonic", 201}, {"non_oscillatory", 203}}},
+};
+#undef IN_P
+#undef IN_C
+#undef PR
+#undef PRR
+#undef PI
+#undef CR
+#undef CI
+#undef CB
+#undef ONE_OR_TWO
+#undef LMI
+static const Opt *find_opt(std::string_view name, unsigned kinds) {      // kinds: bit per OptKind
+  for (const Opt &o : g_opts)
+    if (name == o.name && (kinds >> o.kind & 1)) return &o;
+  return nullptr;
+}
+// what the three setters share; `who` is the entry point's name in the messages
+static int opt_lookup(blomgpu_ctx *c, const char *who, const char *name, unsigned kinds, const Opt **o) {
+  if (!c || !name) return ctx_fail(c, std::string(who) + ": null argument");
+  *o = find_opt(name, kinds);
+  if (!*o || !((*o)->flags & KEEP_GRAPHS)) ctx_drop_graphs(c);
+  return *o ? 0 : ctx_fail(c, std::string(who) + ": unknown option " + name);
+}
+static int set_number(blomgpu_ctx *c, const char *who, const char *name, unsigned kinds, double v) {
+  const Opt *o;
+  if (int rc = opt_lookup(c, who, name, kinds, &o)) return rc;
+  if (o->kind == O_BOOL) v = v != 0;
+  if (o->check)
+    if (const char *refusal = o->check(v)) return ctx_fail(c, refusal);
+  o->at(c).put(v);
+  if (o->flags & DIRTY) c->dirty = true;
+  if (o->after) o->after(c);
+  return o->flags & ALE_RESET ? ale_reset(c) : 0;
+}
+
+// a (and b, unless nullptr) to the device, launch(grid, a, b, z) on the context's stream, z back
+template <class Launch>
+static int libm_probe(blomgpu_ctx *c, int n, const double *a, const double *b, double *z, const char *who, Launch launch) {
+  if (n <= 0) return 0;
+  double *d = nullptr;
+  HIPCHK(c, hipMalloc((void **)&d, sizeof(double) * 3 * (size_t)n));
+  int rc = 0;
+  if (hipMemcpyAsync(d, a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
+  if (b && hipMemcpyAsync(d + n, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
+  launch(dim3((n + 255) / 256), d, d + n, d + 2 * (size_t)n);
+  if (hipMemcpyAsync(z, d + 2 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
+  (void)hipFree(d);
+  return rc ? ctx_fail(c, std::string(who) + ": copy or launch failed") : 0;
 }
 
 int bt_block_mode(blomgpu_ctx *c);       // stage_barotp_pair.hip
@@ -282,74 +453,29 @@ int blomgpu_sync(blomgpu_ctx *c) {
   return 0;
 }
 
-int blomgpu_set_real(blomgpu_ctx *c, const char *name, double v) {
-  if (c) ctx_drop_graphs(c);
-  Params &P = c->h.P;
-  std::string s(name);
-#define R(nm) if (s == #nm) { P.nm = v; c->dirty = true; return 0; }
-  R(baclin) R(batrop) R(delt1) R(dlt) R(mdv2hi) R(mdv2lo) R(mdv4hi) R(mdv4lo) R(mdc2hi)
-  R(mdc2lo) R(vsc2hi) R(vsc2lo) R(vsc4hi) R(vsc4lo) R(cbar) R(cb) R(cwbdts) R(cwbdls)
-  R(wuv1) R(wuv2) R(wts1) R(wts2) R(wbaro) R(bdmc1) R(bdmc2) R(iwdfac) R(nubmin) R(vland)
-#undef R
-  if (s == "pref") { P.pref = v; set_eos(P); c->dirty = true; return 0; }
-  if (s == "swamxd") { c->swamxd = v; return 0; }
-  // &DIFFUSION, as far as phy/mod_difest.F90's isopycnic routines read it (phy/mod_diffusion.F90:45-110)
-  if (s == "egc") { c->egc = v; return 0; }
-  if (s == "eggam") { c->eggam = v; return 0; }
-  if (s == "eglsmn") { c->eglsmn = v; return 0; }
-  if (s == "egmndf") { c->egmndf = v; return 0; }
-  if (s == "egmxdf") { c->egmxdf = v; return 0; }
-  if (s == "egidfq") { c->egidfq = v; return 0; }
-  if (s == "rhiscf") { c->rhiscf = v; return 0; }
-  if (s == "ri0") { c->ri0 = v; return 0; }
-  if (s == "tkepf") { c->tkepf = v; return 0; }
-  if (s == "bdml_logc") { c->bdml_logc = v; return 0; }                           // phy/mod_swabs.F90:179-183
-  if (s == "brine_mlbase_frac") { c->brine_mlbase_frac = v; return 0; }     // phy/mod_forcing.F90:63
-  // mod_mxlayr's and mod_niw's namelist variables (phy/mod_mxlayr.F90:58-68, phy/mod_niw.F90:38-45)
-  // thermf: mod_forcing's namelist variables, mod_grid's area, mod_time's interpolation weight of the month
-  if (s == "trxday") { c->trxday = v; return 0; }
-  if (s == "srxday") { c->srxday = v; return 0; }
-  if (s == "trxdpt") { c->trxdpt = v; return 0; }
-  if (s == "srxdpt") { c->srxdpt = v; return 0; }
-  if (s == "trxlim") { c->trxlim = v; return 0; }
-  if (s == "srxlim") { c->srxlim = v; return 0; }
-  if (s == "sref") { c->sref = v; return 0; }
-  if (s == "area") { c->area = v; return 0; }
-  if (s == "xmi") { c->xmi = v; return 0; }
-  if (s == "rm0") { c->rm0 = v; return 0; }
-  if (s == "rm5") { c->rm5 = v; return 0; }
-  if (s == "niwgf") { c->niwgf = v; return 0; }
-  if (s == "niwbf") { c->niwbf = v; return 0; }
-  if (s == "niwlf") { c->niwlf = v; return 0; }
-  if (s == "ale_regrid_nudge_ts") { c->ale_regrid_nudge_ts = v; return 0; }
-  // mixed layer restratification of eddtra_ale, phy/mod_eddtra.F90:53-94
-  if (s == "ce") { c->eddtra_ce = v; return 0; }
-  if (s == "tau_mlr") { c->tau_mlr = v; return 0; }
-  if (s == "tau_growing_hbl") { c->tau_growing_hbl = v; return 0; }
-  if (s == "tau_decaying_hbl") { c->tau_decaying_hbl = v; return 0; }
-  if (s == "tau_growing_hml") { c->tau_growing_hml = v; return 0; }
-  if (s == "tau_decaying_hml") { c->tau_decaying_hml = v; return 0; }
-  if (s == "lfmin") { c->lfmin = v; return 0; }
-  if (s == "cl") { c->eddtra_cl = v; return 0; }
-  if (s == "mstar") { c->mstar = v; return 0; }
-  if (s == "nstar") { c->nstar = v; return 0; }
-  if (s == "wpup_min") { c->wpup_min = v; return 0; }
-  if (s == "mlbl_max_ratio") { c->mlbl_max_ratio = v; return 0; }
-  if (s == "ale_stab_fac_limit") { c->ale_stab_fac_limit = v; return 0; }
-  if (s == "ale_dpvar_fac") { c->ale_dpvar_fac = v; return 0; }
-  if (s == "ale_smooth_diff_max") { c->ale_smooth_diff_max = v; return 0; }
-  if (s == "ale_dpmin_interior") { c->ale_dpmin_interior = v * 9806.; return 0; }   // [m], as in &ALE_REGRID_REMAP (:1352-1353)
-  return ctx_fail(c, "blomgpu_set_real: unknown option " + s);
+int blomgpu_set_real(blomgpu_ctx *c, const char *name, double v) { return set_number(c, "blomgpu_set_real", name, 1u << O_REAL, v); }
+int blomgpu_set_int(blomgpu_ctx *c, const char *name, int v) { return set_number(c, "blomgpu_set_int", name, 1u << O_INT | 1u << O_BOOL, v); }
+
+int blomgpu_set_str(blomgpu_ctx *c, const char *name, const char *val) {
+  const Opt *o = nullptr;
+  const int rc = opt_lookup(c, "blomgpu_set_str", name, 1u << O_STR, &o);
+  if (c) c->dirty = true;              // for every name it is called with, known or not
+  if (rc) return rc;
+  if (!val) return ctx_fail(c, "blomgpu_set_str: null argument");
+  const std::string v(val);
+  if (!o->words[0].word) { *o->at(c).s = v; return 0; }
+  for (const auto &w : o->words)
+    if (w.word && v == w.word) {
+      if (o->at) o->at(c).put(w.code);
+      return o->flags & ALE_RESET ? ale_reset(c) : 0;
+    }
+  return ctx_fail(c, o->refuse + v + " is unsupported!");
 }
 
 int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
-  Params &P = c->h.P;
-  std::string s(name);
-#define R(nm) if (s == #nm) { *v = P.nm; return 0; }
-  R(baclin) R(batrop) R(delt1) R(dlt) R(pref) R(wbaro)
-#undef R
-  if (s == "area") { *v = c->area; return 0; }
-  if (s == "bdml_logc") { *v = c->bdml_logc; return 0; }
+  const std::string s(name);
+  if (const Opt *o = find_opt(s, 1u << O_REAL))
+    if (o->flags & READABLE) { *v = *o->at(c).d; return 0; }
   // which form of the barotropic substep kernel this context runs with its present options: 1 four substeps per hand-off
   // (k_bt_steps4, persistent), 2 the same kernel with a launch per four substeps, 0 the forms of stage_barotp_pair.hip's head
   if (s == "barotp_block_mode") { *v = bt_block_mode(c); return 0; }
@@ -375,190 +501,13 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   return ctx_fail(c, "blomgpu_get_real: unknown option " + s);
 }
 
-int blomgpu_set_int(blomgpu_ctx *c, const char *name, int v) {
-  std::string s(name);
-  // (the stage timers select nothing: a step with them runs plain launches beside the graphs, which stay)
-  if (c && s == "timing") { c->timing = v != 0; return 0; }
-  if (c) ctx_drop_graphs(c);
-  Params &P = c->h.P;
-#define R(nm) if (s == #nm) { P.nm = v; c->dirty = true; return 0; }
-  if (s == "nstep") { P.nstep = v; return 0; }      // host-side only (stage_cppm.hip): the device view is not touched
-  R(lstep) R(nday_in_year) R(itriag) R(itrtke) R(itrgls) R(tkeadv) R(tkeidf) R(gls) R(vcoord_tag) R(ltedtp_opt) R(bdmtyp) R(iwdflg) R(bdmldp) R(allwet)
-#undef R
-  if (s == "csdiag") { c->csdiag = v != 0; return 0; }
-  if (s == "eddf2d") { c->eddf2d = v != 0; return 0; }
-  if (s == "edsprs") { c->edsprs = v != 0; return 0; }
-  if (s == "edanis") { c->edanis = v != 0; return 0; }
-  if (s == "redi3d") { c->redi3d = v != 0; return 0; }
-  if (s == "edfsmo") { c->edfsmo = v != 0; return 0; }
-  if (s == "rhsctp") {
-    c->rhsctp = v != 0;          // topographic Rhines scale (round 6: sin_libm.h, atan2_libm.h)
-    return 0;
-  }
-  if (s == "edritp_opt") {                            // 1 'shear', 2 'large scale' (phy/mod_diffusion.F90:113-116)
-    if (v != 1 && v != 2) return ctx_fail(c, " readnml_diffusion: edritp is unsupported!");
-    c->edritp_opt = v;
-    return 0;
-  }
-  if (s == "edwmth_opt") {                            // 1 'smooth', 2 'step'
-    if (v != 1 && v != 2) return ctx_fail(c, " readnml_diffusion: edwmth is unsupported!");
-    c->edwmth_opt = v;
-    return 0;
-  }
-  if (s == "difest_live") { c->difest_live = v != 0; return 0; }
-  // thermf: mod_forcing's switches (phy/mod_forcing.F90:43-47), mod_time's months of the interpolation (l1mi..l5mi), mod_ben02's ntda
-  if (s == "full_physics") { c->full_physics = v != 0; if (v) c->live_slopes = true; return 0; }
-  if (s == "aptflx") { c->aptflx = v != 0; return 0; }
-  if (s == "apsflx") { c->apsflx = v != 0; return 0; }
-  if (s == "ditflx") { c->ditflx = v != 0; return 0; }
-  if (s == "disflx") { c->disflx = v != 0; return 0; }
-  if (s == "srxbal") { c->srxbal = v != 0; return 0; }
-  if (s.size() == 4 && s[0] == 'l' && s[2] == 'm' && s[3] == 'i' && s[1] >= '1' && s[1] <= '5') {
-    if (v < 1 || v > 12) return ctx_fail(c, "blomgpu_set_int: " + s + " is a month, 1..12");
-    c->lmi[s[1] - '1'] = v;
-    return 0;
-  }
-  if (s == "ntda") { c->ntda = v; return 0; }
-  if (s == "timing") { c->timing = v != 0; return 0; }
-  if (s == "barotp_fused") { c->barotp_fused = v; return 0; }
-  if (s == "barotp_tile") {
-    if (v != 0 && v != 3216 && v != 3208 && v != 1608 && v != 4016 && v != 2616 && v != 2615 && v != 4015)
-      return ctx_fail(c, "blomgpu_set_int: barotp_tile must be 0, 3216, 3208, 1608, 4016, 2616, 2615 or 4015");
-    c->barotp_tile = v;
-    return 0;
-  }
-  if (s == "eddtra_frozen") { c->eddtra_frozen = v; return 0; }
-  if (s == "pgf_uv_pair") { c->pgf_uv_pair = v; return 0; }
-  if (s == "pgf_uv_ring") { c->pgf_uv_ring = v; return 0; }
-  if (s == "kprof_sel") { c->kprof_sel = v; return 0; }
-  if (s == "mom_aw_split") { c->mom_aw_split = v; return 0; }
-  if (s == "mom_force_aw") { c->mom_force_aw = v; return 0; }
-  if (s == "convec_nsingle") { c->convec_nsingle = v; return 0; }
-  if (s == "cmn_nslope_nb") { c->cmn_nslope_nb = v; return 0; }
-  if (s == "pgf_reuse") { c->pgf_reuse = v; return 0; }
-  if (s == "scan_reassoc") { c->scan_reassoc = v; return 0; }
-  if (s == "pgf_copy_fused") { c->pgf_copy_fused = v; return 0; }
-  if (s == "check_period") { c->check_period = v < 1 ? 1 : v; return 0; }
-  if (s == "barotp_persist") { c->barotp_persist = v; return 0; }
-  if (s == "barotp_block") { c->barotp_block = v; return 0; }
-  if (s == "barotp_overlap") { c->barotp_overlap = v; return 0; }
-  if (s == "barotp_rimbuf") { c->barotp_rimbuf = v; return 0; }
-  if (s == "barotp_arctic_fused") { c->barotp_arctic_fused = v; return 0; }
-  if (s == "barotp_arctic_persist") { c->barotp_arctic_persist = v; return 0; }
-  if (s == "cnsvdi") { c->cnsvdi = v; return 0; }
-  if (s == "arctic_strips") { c->arctic_strips = v; return 0; }
-  if (s == "use_graph") { c->use_graph = v; return 0; }
-  if (s == "overlap") { c->overlap = v; return 0; }
-  if (s == "phys_dag") { c->phys_dag = v; return 0; }
-  if (s == "mom_early_at") { c->mom_early_at = v; return 0; }
-  if (s == "lean_fluxes") { c->lean_fluxes = v; return 0; }
-  if (s == "tmsmt_fold") { c->tmsmt_fold = v; return 0; }
-  if (s == "tmsmt_ahead") { c->tmsmt_ahead = v; return 0; }
-  if (s == "ale_upper_bndr_ord") { c->ale_upper_bndr_ord = v; return ale_reset(c); }
-  if (s == "ale_lower_bndr_ord") { c->ale_lower_bndr_ord = v; return ale_reset(c); }
-  if (s == "ale_k_range_plevel") { c->ale_k_range_plevel = v; return 0; }
-  if (s == "ale_dktzu") { c->ale_dktzu = v; return 0; }
-  if (s == "ale_dktzl") { c->ale_dktzl = v; return 0; }
-  if (s == "ale_density_pc_upper_bndr") { c->ale_density_pc_upper = v != 0; return ale_reset(c); }
-  if (s == "ale_density_pc_lower_bndr") { c->ale_density_pc_lower = v != 0; return ale_reset(c); }
-  if (s == "ale_tracer_pc_upper_bndr") { c->ale_tracer_pc_upper = v != 0; return ale_reset(c); }
-  if (s == "ale_tracer_pc_lower_bndr") { c->ale_tracer_pc_lower = v != 0; return ale_reset(c); }
-  if (s == "ale_velocity_pc_upper_bndr") { c->ale_velocity_pc_upper = v != 0; return ale_reset(c); }
-  if (s == "ale_velocity_pc_lower_bndr") { c->ale_velocity_pc_lower = v != 0; return ale_reset(c); }
-  if (s == "remap_fold") { c->remap_fold = v; return 0; }
-  if (s == "remap_nfirst") { c->remap_nfirst = v; return 0; }
-  if (s == "halo_overlap") { c->halo_overlap = v; return 0; }
-  if (s == "cmnfld1") { c->cmnfld1 = v; return 0; }
-  if (s == "diapfl_du") { c->diapfl_du = v; return 0; }
-  if (s == "live_slopes") { c->live_slopes = v; return 0; }
-  if (s == "ndiff_surface_align") { c->ndiff_surface_align = v != 0; return 0; }
-  if (s == "ndiff_rec_per_face") { c->ndiff_rec_per_face = v < 0 ? 0 : v; return ale_reset(c); }
-  if (s == "momtum_bs") { c->momtum_bs = v; return 0; }
-  if (s == "momtum_lds_pad") { c->momtum_lds_pad = v; return 0; }
-  if (s == "momtum_order") { c->momtum_order = v; return 0; }
-  if (s == "momtum_chunks_a") { c->momtum_chunks_a = v; return 0; }
-  if (s == "momtum_chunks_b") { c->momtum_chunks_b = v; return 0; }
-  if (s == "diffus_shfl") { c->diffus_shfl = v; return 0; }
-  return ctx_fail(c, "blomgpu_set_int: unknown option " + s);
-}
-
-int blomgpu_set_str(blomgpu_ctx *c, const char *name, const char *val) {
-  if (c) ctx_drop_graphs(c);
-  Params &P = c->h.P;
-  std::string s(name), v(val);
-  c->dirty = true;
-  if (s == "expcnf") { c->expcnf = v; return 0; }
-  if (s == "mommth") {
-    if (v == "enscon") P.mommth = 0; else if (v == "enecon") P.mommth = 1; else if (v == "enedis") P.mommth = 2;
-    else return ctx_fail(c, " mommth = " + v + " is unsupported!");   // phy/mod_momtum.F90:815-820
-    return 0;
-  }
-  if (s == "pgfmth") {
-    if (v == "geopotential") P.pgfmth = 0; else if (v == "dynamic enthalpy") P.pgfmth = 1;
-    else return ctx_fail(c, " pgfmth = " + v + " is unsupported!");   // phy/mod_pgforc.F90:529-534
-    return 0;
-  }
-  if (s == "advmth") {
-    if (v == "remap") P.advmth = 0; else if (v == "cppm") P.advmth = 1;
-    else return ctx_fail(c, " advmth = " + v + " is unsupported!");   // phy/mod_advect.F90:166-171
-    return 0;
-  }
-  if (s == "cppm_compatibility") {
-    if (v == "full") c->cppm_compat = 1; else if (v == "partial") c->cppm_compat = 2;
-    else return ctx_fail(c, " init_cppm: cppm_compatibility = " + v + " is unsupported!");   // phy/mod_cppm.F90:2524-2535
-    return 0;
-  }
-  if (s == "cppm_limiting") {
-    if (v == "monotonic") c->cppm_limiting = 1; else if (v == "non_oscillatory") c->cppm_limiting = 2;
-    else return ctx_fail(c, " init_cppm: cppm_limiting = " + v + " is unsupported!");        // phy/mod_cppm.F90:2536-2548
-    return 0;
-  }
-  if (s == "eitmth") {
-    if (v == "intdif") P.eitmth = 1; else if (v == "gm") P.eitmth = 2;
-    else return ctx_fail(c, " eitmth = " + v + " is unsupported!");   // phy/mod_diffusion.F90:316-327
-    c->dirty = true;
-    return 0;
-  }
-  if (s == "mlrttp") { c->mlrttp = v; return 0; }         // resolved (and refused) in mxlayr, phy/mod_mxlayr.F90:197-212
-  if (s == "mlrmth") {                                    // init_eddtra, phy/mod_eddtra.F90:1773-1806
-    if (v == "none") c->mlrmth = 0; else if (v == "fox08") c->mlrmth = 1;
-    else if (v == "bod23") c->mlrmth = 2;                 // refused with isopyc_bulkml when the stage runs (:1787-1795)
-    else return ctx_fail(c, " init_eddtra: mlrmth = " + v + " is unsupported!");
-    return 0;
-  }
-  // &ALE_REGRID_REMAP, phy/mod_ale_regrid_remap.F90:1185-1355 (readnml_ale_regrid_remap; same words, same refusals)
-  if (s == "vcoord_type") {                               // phy/mod_vcoord.F90:908-921
-    if (v == "isopyc_bulkml") P.vcoord_tag = 1; else if (v == "cntiso_hybrid") P.vcoord_tag = 2; else if (v == "plevel") P.vcoord_tag = 3;
-    else return ctx_fail(c, " readnml_vcoord: vcoord_type = " + v + " is unsupported!");
-    return 0;
-  }
-  if (s == "ale_reconstruction_method") {
-    if (v == "plm") c->ale_method = 101; else if (v == "ppm") c->ale_method = 102; else if (v == "pqm") c->ale_method = 103;
-    else return ctx_fail(c, " readnml_ale_regrid_remap: reconstruction_method = " + v + " is unsupported!");
-    return 0;
-  }
-  if (s == "ale_regrid_method") {                         // :1323-1337
-    if (v == "direct") c->ale_regrid_method = 1; else if (v == "nudge") c->ale_regrid_method = 2;
-    else return ctx_fail(c, " readnml_ale_regrid_remap: regrid_method = " + v + " is unsupported!");
-    return 0;
-  }
-  if (s == "ale_density_limiting") {
-    if (v != "monotonic") return ctx_fail(c, " readnml_ale_regrid_remap: density_limiting = " + v + " is unsupported!");
-    return 0;
-  }
-  if (s == "ale_tracer_limiting" || s == "ale_velocity_limiting") {
-    int lim;
-    if (v == "monotonic") lim = 201; else if (v == "non_oscillatory") lim = 203;
-    else return ctx_fail(c, " readnml_ale_regrid_remap: " + s.substr(4) + " = " + v + " is unsupported!");
-    (s == "ale_tracer_limiting" ? c->ale_tracer_limiting : c->ale_velocity_limiting) = lim;
-    return ale_reset(c);             // the cached reconstruction structures hold the limiter
-  }
-  if (s == "bmcmth") {
-    if (v == "uc") P.bmcmth = 0; else if (v == "dluc") P.bmcmth = 1;
-    else return ctx_fail(c, " bmcmth = " + v + " is unsupported!");   // phy/mod_pbcor.F90:112-117
-    return 0;
-  }
-  return ctx_fail(c, "blomgpu_set_str: unknown option " + s);
+// the names of the option table in its order, with the entry point that sets each: kind 0 blomgpu_set_real, 1 blomgpu_set_int,
+// 2 blomgpu_set_int (stored as v != 0), 3 blomgpu_set_str; non-zero past the end
+int blomgpu_option_name(int index, char *buf, int cap, int *kind) {
+  if (index < 0 || index >= (int)(sizeof(g_opts) / sizeof(g_opts[0])) || !buf || cap < 2) return 1;
+  snprintf(buf, cap, "%s", g_opts[index].name);
+  if (kind) *kind = g_opts[index].kind;
+  return 0;
 }
 
 int blomgpu_field_info(blomgpu_ctx *c, const char *name, int *nlev, int *is_int) {
@@ -686,42 +635,17 @@ int blomgpu_xcsum(blomgpu_ctx *c, const char *name, int lev, int itype, double *
   if (lev < 1 || lev > c->nlev_real[it->second]) return ctx_fail(c, "blomgpu_xcsum: level out of range");
   return st_xcsum(c, c->h.f[it->second] + (size_t)(lev - 1) * c->h.nplane, itype, sum);
 }
-// exp() as the kernels evaluate it (exp_libm.h), elementwise on host arrays: lets a caller check that the
-// device returns the bits of its own libm (tests/test_exp_libm.py)
+// exp(), pow(), sin() and atan2() as the kernels evaluate them (exp_libm.h, pow_libm.h, sin_libm.h, atan2_libm.h), elementwise on
+// host arrays: lets a caller check that the device returns the bits of its own libm (tests/test_exp_libm.py, test_pow_libm.py,
+// test_sin_atan2_libm.py)
 __global__ void k_exp_libm(int n, const double *x, double *y) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) y[t] = exp_libm(x[t]);
-}
-int blomgpu_exp(blomgpu_ctx *c, int n, const double *x, double *y) {
-  if (n <= 0) return 0;
-  double *d = nullptr;
-  HIPCHK(c, hipMalloc((void **)&d, sizeof(double) * 2 * (size_t)n));
-  int rc = 0;
-  if (hipMemcpyAsync(d, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
-  hipLaunchKernelGGL(k_exp_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d, d + n);
-  if (hipMemcpyAsync(y, d + n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
-  (void)hipFree(d);
-  return rc ? ctx_fail(c, "blomgpu_exp: copy or launch failed") : 0;
 }
 __global__ void k_pow_libm(int n, const double *x, const double *y, double *z) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) z[t] = pow_libm(x[t], y[t]);
 }
-int blomgpu_pow(blomgpu_ctx *c, int n, const double *x, const double *y, double *z) {
-  if (n <= 0) return 0;
-  double *d = nullptr;
-  HIPCHK(c, hipMalloc((void **)&d, sizeof(double) * 3 * (size_t)n));
-  int rc = 0;
-  if (hipMemcpyAsync(d, x, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
-  if (hipMemcpyAsync(d + n, y, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
-  hipLaunchKernelGGL(k_pow_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d, d + n, d + 2 * (size_t)n);
-  if (hipMemcpyAsync(z, d + 2 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
-  (void)hipFree(d);
-  return rc ? ctx_fail(c, "blomgpu_pow: copy or launch failed") : 0;
-}
-// sin() and atan2() as the kernels evaluate them (sin_libm.h, atan2_libm.h), elementwise on host arrays (tests/test_sin_atan2_libm.py)
 __global__ void k_sin_libm(int n, const double *x, double *z) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) z[t] = sin_libm(x[t]);
@@ -730,22 +654,18 @@ __global__ void k_atan2_libm(int n, const double *y, const double *x, double *z)
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t < n) z[t] = atan2_libm(y[t], x[t]);
 }
-static int unary_binary_libm(blomgpu_ctx *c, int n, const double *a, const double *b, double *z, const char *who) {
-  if (n <= 0) return 0;
-  double *d = nullptr;
-  HIPCHK(c, hipMalloc((void **)&d, sizeof(double) * 3 * (size_t)n));
-  int rc = 0;
-  if (hipMemcpyAsync(d, a, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
-  if (b && hipMemcpyAsync(d + n, b, sizeof(double) * n, hipMemcpyHostToDevice, c->stream) != hipSuccess) rc = 1;
-  if (b) hipLaunchKernelGGL(k_atan2_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d, d + n, d + 2 * (size_t)n);
-  else hipLaunchKernelGGL(k_sin_libm, dim3((n + 255) / 256), dim3(256), 0, c->stream, n, d, d + 2 * (size_t)n);
-  if (hipMemcpyAsync(z, d + 2 * (size_t)n, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
-  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
-  (void)hipFree(d);
-  return rc ? ctx_fail(c, std::string(who) + ": copy or launch failed") : 0;
+int blomgpu_exp(blomgpu_ctx *c, int n, const double *x, double *y) {
+  return libm_probe(c, n, x, nullptr, y, "blomgpu_exp", [&](dim3 g, double *a, double *, double *z) { hipLaunchKernelGGL(k_exp_libm, g, dim3(256), 0, c->stream, n, a, z); });
 }
-int blomgpu_sin(blomgpu_ctx *c, int n, const double *x, double *z) { return unary_binary_libm(c, n, x, nullptr, z, "blomgpu_sin"); }
-int blomgpu_atan2(blomgpu_ctx *c, int n, const double *y, const double *x, double *z) { return unary_binary_libm(c, n, y, x, z, "blomgpu_atan2"); }
+int blomgpu_pow(blomgpu_ctx *c, int n, const double *x, const double *y, double *z) {
+  return libm_probe(c, n, x, y, z, "blomgpu_pow", [&](dim3 g, double *a, double *b, double *r) { hipLaunchKernelGGL(k_pow_libm, g, dim3(256), 0, c->stream, n, a, b, r); });
+}
+int blomgpu_sin(blomgpu_ctx *c, int n, const double *x, double *z) {
+  return libm_probe(c, n, x, nullptr, z, "blomgpu_sin", [&](dim3 g, double *a, double *, double *r) { hipLaunchKernelGGL(k_sin_libm, g, dim3(256), 0, c->stream, n, a, r); });
+}
+int blomgpu_atan2(blomgpu_ctx *c, int n, const double *y, const double *x, double *z) {
+  return libm_probe(c, n, y, x, z, "blomgpu_atan2", [&](dim3 g, double *a, double *b, double *r) { hipLaunchKernelGGL(k_atan2_libm, g, dim3(256), 0, c->stream, n, a, b, r); });
+}
 int blomgpu_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   (void)k1m; (void)k1n;
   ctx_sync_view(c);
@@ -838,144 +758,125 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
     if (st_xctilr_multi(c, 6, ptrs, nl, 2, 2, it)) return 1;
   }
   // interface pressure out to ii+3 for remap (:761-772) -- unless st_cmnfld2 has done it in front of its kernels on the second stream
-  if (c->pscan_done_ahead) { c->pscan_done_ahead = false; return 0; }
+  if (c->seq.pscan_done_ahead) { c->seq.pscan_done_ahead = false; return 0; }
   return launch_pscan(c, nn, -2, 3);
 }
 
+// Everything blomgpu_stage accepts: X(name, the call of its entry point), the reference's stages and the pseudo-stages that stand for
+// parts of them.  (blom_amd/stepper.py keeps its own lists of these names.)
+#define STAGE_ARGS blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n
+#define ALL6 c, m, n, mm, nn, k1m, k1n
+#define BLOM_STAGES(X)                                                                                                          \
+  X(init_fluxes, blomgpu_init_fluxes(ALL6)) X(tmsmt1, blomgpu_tmsmt1(c, nn)) X(tmsmt2, blomgpu_tmsmt2(c, m, mm, nn, k1m))        \
+  X(initms, blomgpu_initms(c, mm)) X(advect, blomgpu_advect(ALL6)) X(pbcor1, blomgpu_pbcor1(ALL6)) X(pbcor2, blomgpu_pbcor2(ALL6)) \
+  X(diffus, blomgpu_diffus(ALL6)) X(pgforc, blomgpu_pgforc(ALL6)) X(momtum, blomgpu_momtum(ALL6)) X(convec, blomgpu_convec(ALL6))  \
+  X(sfcstr, blomgpu_sfcstr(ALL6)) X(updtrc, blomgpu_updtrc(ALL6)) X(diapfl, blomgpu_diapfl(c, n, nn, k1n))                        \
+  X(barotp, blomgpu_barotp(ALL6)) X(eddtra, blomgpu_eddtra(ALL6)) X(init_cppm, blomgpu_init_cppm(c))                              \
+  X(halo_cmnfld2, blomgpu_halo_cmnfld2(c, n)) X(cmnfld2, blomgpu_cmnfld2(ALL6)) X(cmnfld1, blomgpu_cmnfld1(ALL6))                 \
+  X(halo_difest, blomgpu_halo_difest(c, nn)) X(difest_isobml_pre, (ctx_sync_view(c), st_difest_isobml_pre(c, m, n, mm, nn)))      \
+  X(difest_isobml, blomgpu_difest_isobml(ALL6)) X(niw_ke_tendency, (ctx_sync_view(c), st_niw_ke_tendency(c, m, mm)))              \
+  X(halo_difest_hyb, blomgpu_halo_difest_hyb(c, 0, k1n)) X(halo_difest_vert, blomgpu_halo_difest_hyb(c, 1, k1n))                  \
+  X(mxlayr_tail, blomgpu_mxlayr_tail(c, nn, k1n)) X(mxlayr, blomgpu_mxlayr(ALL6)) X(thermf, blomgpu_thermf(ALL6))                 \
+  X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
+  X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6))
+enum StageId {
+#define X(nm, call) S_##nm,
+  BLOM_STAGES(X)
+#undef X
+  NSTAGE
+};
+static const struct Stage { const char *name; StageId id; int (*entry)(STAGE_ARGS); } g_stages[NSTAGE] = {
+#define X(nm, call) {#nm, S_##nm, [](STAGE_ARGS) -> int { return call; }},
+  BLOM_STAGES(X)
+#undef X
+};
+
 int blomgpu_stage(blomgpu_ctx *c, const char *stage, int m, int n, int mm, int nn, int k1m, int k1n) {
-  std::string s(stage);
-  if (s == "init_fluxes") return blomgpu_init_fluxes(c, m, n, mm, nn, k1m, k1n);
-  if (s == "tmsmt1") return blomgpu_tmsmt1(c, nn);
-  if (s == "tmsmt2") return blomgpu_tmsmt2(c, m, mm, nn, k1m);
-  if (s == "initms") return blomgpu_initms(c, mm);
-  if (s == "advect") return blomgpu_advect(c, m, n, mm, nn, k1m, k1n);
-  if (s == "pbcor1") return blomgpu_pbcor1(c, m, n, mm, nn, k1m, k1n);
-  if (s == "pbcor2") return blomgpu_pbcor2(c, m, n, mm, nn, k1m, k1n);
-  if (s == "diffus") return blomgpu_diffus(c, m, n, mm, nn, k1m, k1n);
-  if (s == "pgforc") return blomgpu_pgforc(c, m, n, mm, nn, k1m, k1n);
-  if (s == "momtum") return blomgpu_momtum(c, m, n, mm, nn, k1m, k1n);
-  if (s == "convec") return blomgpu_convec(c, m, n, mm, nn, k1m, k1n);
-  if (s == "sfcstr") return blomgpu_sfcstr(c, m, n, mm, nn, k1m, k1n);
-  if (s == "updtrc") return blomgpu_updtrc(c, m, n, mm, nn, k1m, k1n);
-  if (s == "diapfl") return blomgpu_diapfl(c, n, nn, k1n);
-  if (s == "barotp") return blomgpu_barotp(c, m, n, mm, nn, k1m, k1n);
-  if (s == "eddtra") return blomgpu_eddtra(c, m, n, mm, nn, k1m, k1n);
-  if (s == "init_cppm") return blomgpu_init_cppm(c);
-  if (s == "halo_cmnfld2") return blomgpu_halo_cmnfld2(c, n);
-  if (s == "cmnfld2") return blomgpu_cmnfld2(c, m, n, mm, nn, k1m, k1n);
-  if (s == "cmnfld1") return blomgpu_cmnfld1(c, m, n, mm, nn, k1m, k1n);
-  if (s == "halo_difest") return blomgpu_halo_difest(c, nn);
-  if (s == "difest_isobml_pre") { ctx_sync_view(c); return st_difest_isobml_pre(c, m, n, mm, nn); }
-  if (s == "difest_isobml") { ctx_sync_view(c); return st_difest_isobml(c, m, n, mm, nn); }
-  if (s == "niw_ke_tendency") { ctx_sync_view(c); return st_niw_ke_tendency(c, m, mm); }
-  if (s == "halo_difest_hyb") return blomgpu_halo_difest_hyb(c, 0, k1n);
-  if (s == "halo_difest_vert") return blomgpu_halo_difest_hyb(c, 1, k1n);
-  if (s == "mxlayr_tail") return blomgpu_mxlayr_tail(c, nn, k1n);
-  if (s == "mxlayr") return blomgpu_mxlayr(c, m, n, mm, nn, k1m, k1n);
-  if (s == "thermf") return blomgpu_thermf(c, m, n, mm, nn, k1m, k1n);
-  if (s == "ale_regrid_remap") return blomgpu_ale_regrid_remap(c, m, n, mm, nn, k1m, k1n);
-  if (s == "ale_forcing") return blomgpu_ale_forcing(c, m, n, mm, nn, k1m, k1n);
-  if (s == "cmnfld_bfsqi_ale") return blomgpu_cmnfld_bfsqi_ale(c, m, n, mm, nn, k1m, k1n);
-  if (s == "ale_vdifft") return blomgpu_ale_vdifft(c, m, n, mm, nn, k1m, k1n);
-  if (s == "ale_vdiffm") return blomgpu_ale_vdiffm(c, m, n, mm, nn, k1m, k1n);
-  return ctx_fail(c, "blomgpu_stage: unknown stage " + s);
+  const std::string_view s(stage);
+  for (const Stage &st : g_stages)
+    if (s == st.name) return st.entry(ALL6);
+  return ctx_fail(c, "blomgpu_stage: unknown stage " + std::string(s));
 }
 
 // Stage sequence of one baroclinic step, phy/mod_blom_step.F90:89-253 (hot path only).
-static int step_sequence(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
-  static const char *seq[] = {"init_fluxes", "tmsmt1", "halo_cmnfld2", "halo_difest", "eddtra", "advect",
-                              "pbcor1", "diffus", "pgforc", "momtum", "convec", "diapfl", "mxlayr_tail", "updtrc",
-                              "barotp", "pbcor2", "tmsmt2"};
+static int step_sequence(STAGE_ARGS) {
+  static const StageId seq[] = {S_init_fluxes, S_tmsmt1, S_halo_cmnfld2, S_halo_difest, S_eddtra, S_advect, S_pbcor1, S_diffus, S_pgforc,
+                                S_momtum, S_convec, S_diapfl, S_mxlayr_tail, S_updtrc, S_barotp, S_pbcor2, S_tmsmt2};
   // the other vertical coordinates (phy/mod_blom_step.F90:126-233 with vcoord_tag /= vcoord_isopyc_bulkml), as far as built:
   // blom_amd/stepper.py HYBRID_STAGES says what is left out and why
-  static const char *seq_ale[] = {"init_fluxes", "tmsmt1", "ale_regrid_remap", "cmnfld2", "halo_difest_hyb", "eddtra", "advect", "pbcor1",
-                                  "diffus", "pgforc", "momtum", "cmnfld_bfsqi_ale", "ale_forcing", "halo_difest_vert",
-                                  "ale_vdifft", "ale_vdiffm", "updtrc", "barotp", "pbcor2", "tmsmt2", "cmnfld1"};
-  c->defer_checks = true;
-  c->in_sequence = true;
-  c->pbcor1_handed_over = c->pbcor2_handed_over = c->pbcor2_dp_in_wk = false;
-  c->fluxes_zeroed = false;
-  c->fluxes_lean = false;
-  c->remap_handed_over = false;
-  c->mom_early_done = c->convec_col_ahead = c->cmn_on_side = false;
-  c->diapfl_mom_on_side = c->updtrc_on_side = c->pscan_done_ahead = false;
-  if (c->h.P.vcoord_tag != 1) {
-    for (const char *st : seq_ale) {
-      if (c->tmsmt1_done_ahead && !strcmp(st, "tmsmt1")) { c->tmsmt1_done_ahead = false; continue; }
-      if (c->eddtra_frozen && !strcmp(st, "eddtra")) continue;
-      if (int rc = blomgpu_stage(c, st, m, n, mm, nn, k1m, k1n)) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return rc;
+  static const StageId seq_ale[] = {S_init_fluxes, S_tmsmt1, S_ale_regrid_remap, S_cmnfld2, S_halo_difest_hyb, S_eddtra, S_advect,
+                                    S_pbcor1, S_diffus, S_pgforc, S_momtum, S_cmnfld_bfsqi_ale, S_ale_forcing, S_halo_difest_vert,
+                                    S_ale_vdifft, S_ale_vdiffm, S_updtrc, S_barotp, S_pbcor2, S_tmsmt2, S_cmnfld1};
+  const auto stage = [&](StageId id) { return g_stages[id].entry(ALL6); };
+  const bool ale = c->h.P.vcoord_tag != 1;
+  c->seq = StepState{};
+  c->seq.defer_checks = c->seq.in_sequence = true;
+  {
+    // the one way out of the sequence, whichever return takes it
+    struct Leave {
+      blomgpu_ctx *c;
+      bool failed = true;
+      ~Leave() {
+        c->seq.defer_checks = c->seq.in_sequence = false;
+        if (failed) c->tmsmt1_done_ahead = false;
       }
+    } leave{c};
+    if (ale) {
+      for (const StageId st : seq_ale) {
+        if (c->tmsmt1_done_ahead && st == S_tmsmt1) { c->tmsmt1_done_ahead = false; continue; }
+        if (c->eddtra_frozen && st == S_eddtra) continue;
+        if (int rc = stage(st)) return rc;
+      }
+    } else for (const StageId st : seq) {
+      // live_slopes: cmnfld2 (the halo updates plus buoyancy frequency and neutral slopes) in place of its halo part alone
+      StageId run = c->live_slopes && st == S_halo_cmnfld2 ? S_cmnfld2 : st;
+      // full_physics (blom_amd/stepper.py FULL_STAGES): the built part of difest_isobml, thermf and mxlayr in place of the two
+      // pseudo-stages that stood in for them
+      if (c->full_physics && st == S_halo_difest) run = c->difest_live ? S_difest_isobml : S_difest_isobml_pre;
+      if (c->full_physics && st == S_mxlayr_tail) {
+        if (int rc = stage(S_thermf)) return rc;
+        run = S_mxlayr;
+      }
+      // eddtra_frozen: the eddy-induced fluxes umfltd.. stay as uploaded (the reference build of the oracle has no mod_eddtra;
+      // tests pin advect/remap on non-zero fluxes this way)
+      if (c->eddtra_frozen && st == S_eddtra) continue;
+      // the step before this one, in the same call, has done this step's tmsmt1 in its tmsmt2
+      if (c->tmsmt1_done_ahead && st == S_tmsmt1) { c->tmsmt1_done_ahead = false; continue; }
+      // The lean init_fluxes zeroes only the ring the tile kernel of remap does not store (stage_simple.hip): until advect has run, every
+      // other plane of uflx .. vsflx (m) holds the PREVIOUS step's fluxes.  Only stages known not to touch them may run in between.
+      if (c->seq.fluxes_lean) {
+        bool allowed = false;
+        for (const StageId ok : {S_tmsmt1, S_halo_cmnfld2, S_cmnfld2, S_halo_difest, S_difest_isobml, S_difest_isobml_pre, S_eddtra, S_advect})
+          allowed = allowed || run == ok;
+        if (!allowed)
+          return ctx_fail(c, std::string("blomgpu_step: stage ") + g_stages[run].name + " between the lean init_fluxes and advect: the flux arrays of level m are not zeroed (set lean_fluxes = 0)");
+      }
+      // what an earlier stage left running on the second stream and this stage needs (st_mxlayr waits for diapfl's momentum mixing itself)
+      if ((c->seq.diapfl_mom_on_side && run != S_mxlayr) || (c->seq.updtrc_on_side && st == S_pbcor2)) {
+        const int ev = c->seq.diapfl_mom_on_side ? 7 : 9;
+        c->seq.diapfl_mom_on_side = c->seq.updtrc_on_side = false;
+        if (ctx_side_done(c, ev) || ctx_side_join(c, ev)) return 1;
+      }
+      if (int rc = stage(run)) return rc;
+      // cmnfld2's kernels still alone on the second stream (frozen diffusivities: difest_isobml did not wait for them): eddtra reads the slopes
+      if (st == S_halo_difest && c->seq.cmn_on_side) {
+        c->seq.cmn_on_side = false;
+        if (ctx_side_done(c, 4) || ctx_side_join(c, 4)) return 1;
+      }
+      // momtum's viscous chain starts here, on the second stream (stage_momtum.hip: st_momtum_early) -- or behind a later stage
+      // (option mom_early_at: nothing up to pgforc writes what the chain reads)
+      static const StageId early_at[] = {S_halo_difest, S_eddtra, S_advect, S_pbcor1, S_diffus};
+      if (st == early_at[c->mom_early_at < 0 || c->mom_early_at > 4 ? 0 : c->mom_early_at])
+        if (int rc = st_momtum_early(c, m, n, mm, nn)) return rc;
     }
-    c->defer_checks = false;
-    c->in_sequence = false;
-    return 0;
+    leave.failed = false;
   }
-  for (const char *st : seq) {
-    // live_slopes: cmnfld2 (the halo updates plus buoyancy frequency and neutral slopes) in place of its halo part alone
-    const char *run = c->live_slopes && !strcmp(st, "halo_cmnfld2") ? "cmnfld2" : st;
-    // full_physics (blom_amd/stepper.py FULL_STAGES): the built part of difest_isobml, thermf and mxlayr in place of the two
-    // pseudo-stages that stood in for them
-    if (c->full_physics && !strcmp(st, "halo_difest")) run = c->difest_live ? "difest_isobml" : "difest_isobml_pre";
-    if (c->full_physics && !strcmp(st, "mxlayr_tail")) {
-      if (int rc = blomgpu_stage(c, "thermf", m, n, mm, nn, k1m, k1n)) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return rc;
-      }
-      run = "mxlayr";
-    }
-    // eddtra_frozen: the eddy-induced fluxes umfltd.. stay as uploaded (the reference build of the oracle has no mod_eddtra;
-    // tests pin advect/remap on non-zero fluxes this way)
-    if (c->eddtra_frozen && !strcmp(st, "eddtra")) continue;
-    // the step before this one, in the same call, has done this step's tmsmt1 in its tmsmt2
-    if (c->tmsmt1_done_ahead && !strcmp(st, "tmsmt1")) { c->tmsmt1_done_ahead = false; continue; }
-    // The lean init_fluxes zeroes only the ring the tile kernel of remap does not store (stage_simple.hip): until advect has run, every
-    // other plane of uflx .. vsflx (m) holds the PREVIOUS step's fluxes.  Only stages known not to touch them may run in between.
-    if (c->fluxes_lean) {
-      static const char *ok[] = {"tmsmt1", "halo_cmnfld2", "cmnfld2", "halo_difest", "difest_isobml", "difest_isobml_pre", "eddtra", "advect"};
-      bool allowed = false;
-      for (const char *o : ok) allowed = allowed || !strcmp(run, o);
-      if (!allowed) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return ctx_fail(c, std::string("blomgpu_step: stage ") + run + " between the lean init_fluxes and advect: the flux arrays of level m are not zeroed (set lean_fluxes = 0)");
-      }
-    }
-    // what an earlier stage left running on the second stream and this stage needs (st_mxlayr waits for diapfl's momentum mixing itself)
-    if ((c->diapfl_mom_on_side && strcmp(run, "mxlayr")) || (c->updtrc_on_side && !strcmp(st, "pbcor2"))) {
-      const int ev = c->diapfl_mom_on_side ? 7 : 9;
-      c->diapfl_mom_on_side = c->updtrc_on_side = false;
-      if (ctx_side_done(c, ev) || ctx_side_join(c, ev)) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return 1;
-      }
-    }
-    if (int rc = blomgpu_stage(c, run, m, n, mm, nn, k1m, k1n)) {
-      c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-      return rc;
-    }
-    // cmnfld2's kernels still alone on the second stream (frozen diffusivities: difest_isobml did not wait for them): eddtra reads the slopes
-    if (!strcmp(st, "halo_difest") && c->cmn_on_side) {
-      c->cmn_on_side = false;
-      if (ctx_side_done(c, 4) || ctx_side_join(c, 4)) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return 1;
-      }
-    }
-    // momtum's viscous chain starts here, on the second stream (stage_momtum.hip: st_momtum_early) -- or behind a later stage
-    // (option mom_early_at: nothing up to pgforc writes what the chain reads)
-    static const char *early_at[] = {"halo_difest", "eddtra", "advect", "pbcor1", "diffus"};
-    if (!strcmp(st, early_at[c->mom_early_at < 0 || c->mom_early_at > 4 ? 0 : c->mom_early_at]))
-      if (int rc = st_momtum_early(c, m, n, mm, nn)) {
-        c->defer_checks = false; c->in_sequence = false; c->tmsmt1_done_ahead = false;
-        return rc;
-      }
-  }
-  c->defer_checks = false;
-  c->in_sequence = false;
-  if (c->cmnfld1 || c->full_physics) return blomgpu_stage(c, "cmnfld1", m, n, mm, nn, k1m, k1n);     // phy/mod_blom_step.F90:233
+  // (outside the sequence: nothing is handed to it and it defers nothing)
+  if (!ale && (c->cmnfld1 || c->full_physics)) return stage(S_cmnfld1);     // phy/mod_blom_step.F90:233
   return 0;
 }
+#undef ALL6
+#undef STAGE_ARGS
 
 // A step is ~100 kernel launches, and on the smaller grids most of them are shorter than the time it takes to launch
 // them.  The sequence depends on the step only through the parity of the time levels, so it is captured from the stream

@@ -264,81 +264,38 @@ struct Tiling {
   bool multi() const { return npx * npy > 1 || rccl != nullptr; }
 };
 
-struct blomgpu_ctx {
-  DevView h;                 // host copy (pointers are device pointers)
-  DevView *d = nullptr;      // device copy handed to kernels
-  bool dirty = true;         // host copy changed since last upload
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // second stream for halo exchanges that overlap with compute (RCCL tiles: barotp), its fork/join events,
-  // and the stream the RCCL transport enqueues on when set (otherwise `stream`)
-  hipStream_t xstream = nullptr, halo_stream = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  int barotp_rimbuf = 1;    // RCCL tiles: barotp's pair kernel reads its E/W rim from the receive buffers
-  int barotp_arctic_persist = 1; // arctic patch, single tile: the odd+even pairs of a phase in the persistent launch (stage_barotp.hip)
-  int barotp_arctic_fused = 1;   // decomposed arctic domain: fused pair kernel with the single tile's exchange schedule
-  int barotp_overlap = 0;   // measured slower (see stage_barotp_pair.hip: bt_overlap_usable)
-  int nlev_real[NF_REAL];
-  int nlev_int[NF_INT];
-  std::unordered_map<std::string, int> real_ids, int_ids;
-  std::unordered_map<std::string, KTimer> timers;
-  bool timing = false;
-  Tiling tiling;
-  bool cppm_ready = false;   // init_cppm has run (tables on the device)
-  int cppm_compat = 1;       // 1 full, 2 partial            (phy/mod_cppm.F90:55-58)
-  int cppm_limiting = 2;     // 1 monotonic, 2 non_oscillatory
-  // device error words: [0] diapfl, [1] eddtra, [2] barotp abort.  Stage entries read theirs back at once;
-  // blomgpu_step defers the read-back to the end of the step (one host sync per step instead of three)
-  int *err_dev = nullptr;
-  bool defer_checks = false;
-  // blomgpu_step replays the stage sequence of a step as a HIP graph (one per parity of the time levels), captured from
-  // the stream once the lazily allocated buffers exist; any option / parameter / mask change drops the graphs
-  int halo_overlap = 1;          // RCCL tiles: the halo exchange in front of remap runs on xstream while the inner tiles compute
-                                 // (bit-identical; ON by default since round 4, the arctic patch included -- in self-send on one GPU it
-                                 // costs 0.2 ms, 9.78 against 9.59 ms per step; what it buys over xGMI has not been measured)
-  int cmnfld1 = 0;               // blomgpu_step ends with cmnfld1 (z, dz of the new state; consumed by diagnostics and difest only)
-  int use_graph = 0;             // measured slower than plain launches on ROCm 7.2 (channel 8.25 vs 7.90 ms, tnx2v1s 5.44 vs 5.12): off by default
-  hipGraphExec_t step_graph[2] = {nullptr, nullptr};
-  int steps_done = 0;
-  BtGlobal *bt_global = nullptr; // RCCL tiles: barotp gathers its 2-D inputs and solves the global domain on a second context
-  bool stream_borrowed = false;  // this context runs on another context's stream (the global barotropic context of a tile)
-  bool in_sequence = false;      // blomgpu_step is running its stage sequence: a stage may hand data to the next one through the work space
+// What only means something between the stages of ONE step of blomgpu_step's sequence: a stage hands data or a running launch to a
+// later one.  step_sequence (api.hip) starts every step from StepState{} and leaves through one guard that clears the two switches, so a
+// flag added here cannot go stale.  A stage called on its own (blomgpu_stage) may still write its flag; nothing reads it then.
+struct StepState {
+  bool in_sequence = false;          // blomgpu_step is running its stage sequence: a stage may hand data to the next one through the work space
+  bool defer_checks = false;         // the stages leave their error words on the device: blomgpu_step reads them back (ctx_check_errors)
+  bool remap_handed_over = false;    // remap (remap_fold) has left dp, T, S, tracers of the new level in the work space for pbcor1
+  bool pbcor1_handed_over = false;   // pbcor1 left S, T, tracers of the new level in the work space (slots N_S, N_T, N_TR): diffus starts there
   bool pbcor2_handed_over = false;   // likewise pbcor2 (level m) for tmsmt2
   bool pbcor2_dp_in_wk = false;      // ... and its column pass (the rescaling of dp) is left to tmsmt2 as well
-  int tmsmt_fold = 1;                // option: 0 = pbcor2 always runs its column pass
-  bool pbcor1_handed_over = false;   // pbcor1 left S, T, tracers of the new level in the work space (slots N_S, N_T, N_TR): diffus starts there
-  int steps_warm = 0;            // plain steps since the last option change (graph capture waits for 2: both time levels' buffers exist)
-  long long graph_steps = 0;     // steps replayed as graphs (blomgpu_get_real "graph_steps")
-  int graph_failures = 0;        // captures that began and failed (tried again after two more plain steps, three times at most)
-  int pgf_uv_pair = 0;           // k_pgf_uv, A/B option: 1 = the u- and v-column wavefronts of 64 points in one workgroup with XCD-contiguous
-                                 // numbering: fetch 1.44 -> 0.92 GB per launch, but 0.388 against 0.369 ms for the stage (same box, two runs
-                                 // each): the kernel waits on its k-serial chain, not on bytes.  Off.
-  int scan_reassoc = 0;          // TOLERANCE-MODE EXPERIMENT (off): k_pscan with k on the lanes and a log-step shuffle prefix sum -- NOT bit-identical to the reference (stage_simple.hip)
-  hipStream_t side3 = nullptr;   // the viscous march's land-side pairs beside its all-wet pairs (mom_aw_split = 2)
-  hipEvent_t ev_side3[2] = {nullptr, nullptr};
-  int mom_aw_split = 0;          // the viscous march's all-wet (chunk, strip) pairs on a launch of their own with the mask-free kernel (round 6): 1 = one after the other, 2 = side by side on a third stream; measured, off
-  int mom_aw_key = -1, mom_aw_n[2] = {0, 0};
-  int *mom_aw_dev = nullptr;     // the two launch lists, device memory
-  int mom_force_aw = 0;          // TIMING EXPERIMENT ONLY: k_mom_visc_march with the mask-free body alone (wrong next to land)
-  int convec_nsingle = 2;        // k_convec_velocity: moves of a level walked singly before chunks of old layers are requested (A/B; 1000 = the kernel of rounds 1-5)
-  int cmn_nslope_nb = 4;         // k_cmn_nslope: interfaces in flight in the interior sweep (A/B: 2, 3, 4)
-  int pgf_reuse = 0;             // k_pgf_uv: skip the equation of state where a level repeats the previous level's inputs (wave-uniform; bit-identical)
-  int pgf_uv_ring = 7;           // k_pgf_uv_ring (round 6: every load of the level loop statically countable): 1 = separate u / v workgroups, 2 = paired + XCD-contiguous
-  int pgf_copy_fused = 1;        // pgforc: the pgfx_o/pgfy_o copy rides along in k_pgf_uv
-  int eddtra_frozen = 0;         // blomgpu_step leaves eddtra out: umfltd, vmfltd, umflsm, vmflsm stay as uploaded
-  int check_period = 8;          // steps between read-backs of the sticky stage error words in blomgpu_step
+  bool fluxes_lean = false;          // init_fluxes zeroed only the ring the storing tile kernel of remap leaves out; cleared by that kernel's launch
+  bool fluxes_zeroed = false;        // init_fluxes has run and remap has not yet (its u-faces then add to zero)
+  bool mom_early_done = false;       // momtum's viscous chain of this step is already running on `side` (st_momtum_early; momtum consumes)
+  bool convec_col_ahead = false;     // convec's column kernel of this step is already running on `side` (st_convec_column_ahead; convec consumes)
+  bool cmn_on_side = false;          // cmnfld2's kernels of this step are on `side`, nothing has waited for them yet (difest_isobml or step_sequence joins)
+  // small launches beside long ones (option phys_dag, bits 2, 4, 8): diapfl's momentum mixing beside thermf and mxlayr's first kernels
+  // (st_mxlayr or step_sequence joins), updtrc's ideal-age step / mxlayr's copy-back clamp beside barotp's first kernels (`updtrc_on_side`
+  // says that something on the second stream has to be waited for in front of pbcor2)
+  bool diapfl_mom_on_side = false, updtrc_on_side = false;
+  bool pscan_done_ahead = false;     // st_cmnfld2 has launched the pressure scan of difest_isobml's front part (blomgpu_halo_difest consumes)
+};
+
+struct blomgpu_ctx {
+  // ==== options: what blomgpu_set_real / _int / _str store outside Params (api.hip: g_opts names each of them once) ====================
+  // ---- namelist-type variables of the reference ----
+  std::string expcnf = "channel";   // experiment configuration (mod_config): selects the forcing branches
   bool csdiag = false;           // mod_checksum's switch: error words read back every step
-  bool bt_restart = true;        // the next persistent barotp launch zeroes the completion counts and starts at epoch 0
-  unsigned bt_epoch = 0;          // completion count every tile has reached after the launches so far
-  // blomgpu_step with more steps to come: tmsmt2 also writes what the next step's tmsmt1 would copy (stage_simple.hip)
-  // option: inside blomgpu_step k_remap_tile also does k_remap_update's work (stage_remap_tile.hip).  Off: measured equal
-  // (channel 6.41-6.45 against 6.43-6.45 ms per step, remap 0.910 against 0.906 ms) to slower (tnx2v1s 3.71 against 3.66 ms) -- the
-  // overlapping tiles cost the tile kernel what the update kernel took, though 1.1 GB less crosses HBM
-  int remap_fold = 0;
-  int remap_nfirst = 4;      // more than 4 advected tracers: how many of them ride with dp, T, S in k_remap_tile's first pass (0..4; 4 measured fastest)
-  bool remap_handed_over = false;   // ... and has left dp, T, S, tracers of the new level in the work space for pbcor1
+  int cnsvdi = 0;                // mod_budget: conservation diagnostics on/off
+  int cppm_compat = 1;           // 1 full, 2 partial            (phy/mod_cppm.F90:55-58)
+  int cppm_limiting = 2;         // 1 monotonic, 2 non_oscillatory
   // ale_regrid_remap (stage_ale.hip): the options of &ALE_REGRID_REMAP with the reference's defaults (mod_ale_regrid_remap.F90:69-95),
-  // as hor3map codes (include/blomgpu_hor3map.h); the engine's structures; the pressure levels of vcoord_type = 'plevel'
+  // as hor3map codes (include/blomgpu_hor3map.h)
   int ale_method = 102, ale_upper_bndr_ord = 6, ale_lower_bndr_ord = 4, ale_tracer_limiting = 203, ale_velocity_limiting = 203;
   bool ale_tracer_pc_upper = true, ale_tracer_pc_lower = false, ale_velocity_pc_upper = true, ale_velocity_pc_lower = false;
   bool ale_density_pc_upper = false, ale_density_pc_lower = false;
@@ -346,58 +303,40 @@ struct blomgpu_ctx {
   double ale_regrid_nudge_ts = 86400., ale_stab_fac_limit = .75, ale_dpvar_fac = .75, ale_smooth_diff_max = 50000.;   // :80-85
   int ale_dktzu = 4, ale_dktzl = 2;
   double ale_dpmin_interior = .1 * 9806.;                 // [m] in the namelist, times onem (:1352-1353)
+  int ndiff_rec_per_face = 0;    // neutral diffusion: records per face (0: 6 kk, the bound; stage_ale.hip)
+  int ndiff_surface_align = 1;   // phy/mod_diffusion.F90:84 (the namelist default of cime_config is .true.)
   // mod_mxlayr's namelist variables (cime_config/namelist_definition_blom.xml: rm0 = 1.2, rm5 = 0, mlrttp = 'constant'), mod_niw's
   double rm0 = 1.2, rm5 = 0., niwgf = 0., niwbf = .35, niwlf = .5;
-  std::string mlrttp = "constant";
+  std::string mlrttp = "constant";      // resolved (and refused) in mxlayr, phy/mod_mxlayr.F90:197-212
   // thermf (mod_forcing's namelist variables, phy/mod_forcing.F90:43-62, :84; mod_grid's area; mod_time's position in the year,
   // phy/mod_time.F90: xmi, l1mi..l5mi; mod_ben02's ntda)
   double trxday = 0., srxday = 0., trxdpt = 1., srxdpt = 1., trxlim = 1.5, srxlim = .5, sref = 34.65, area = 0., xmi = 0.;
   int lmi[5] = {11, 12, 1, 2, 3};
   bool aptflx = false, apsflx = false, ditflx = false, disflx = false, srxbal = false;
   int ntda = 0;
-  bool full_physics = false;  // blomgpu_step runs difest_isobml_pre, thermf, mxlayr (+ cmnfld2, cmnfld1): stepper.py FULL_STAGES
   double swamxd = 200., brine_mlbase_frac = 0.;           // phy/mod_swabs.F90:183 (default); phy/mod_forcing.F90:63 (namelist)
-  void *ale = nullptr;
-  double *ale_plevel = nullptr;
-  // eddtra_ale (stage_eddtra_ale.hip): the options of &DIFFUSION that phy/mod_eddtra.F90 owns, with its defaults (:53-94)
+  // eddtra_ale (stage_eddtra_ale.hip): the options of &DIFFUSION that phy/mod_eddtra.F90 owns, with its defaults (:53-94); the C-ABI
+  // names of eddtra_ce, eddtra_cl are "ce", "cl"
   int mlrmth = 1;                                         // 0 none, 1 fox08, 2 bod23 (hybrid coordinate only)
   double eddtra_ce = .06, tau_mlr = 86400., tau_growing_hbl = 300., tau_decaying_hbl = 86400., tau_growing_hml = 3600.,
          tau_decaying_hml = 259200., lfmin = 5.e3, mlbl_max_ratio = 3., eddtra_cl = .25, mstar = .5, nstar = .066, wpup_min = 1.e-3;
-  bool fluxes_lean = false;      // in sequence: init_fluxes zeroed only the ring the storing tile kernel of remap leaves out; cleared by that kernel's launch
-  bool fluxes_zeroed = false;    // in sequence: init_fluxes has run and remap has not yet (its u-faces then add to zero)
-  bool tmsmt1_ahead = false, tmsmt1_done_ahead = false;
-  int tmsmt_ahead = 1;           // option: 0 = every step launches its own tmsmt1
-  unsigned *bt_flags = nullptr;   // abort word + per-tile completion counts of the persistent barotp kernel
-  int num_cus = 0;
-  int bt4_blocks_per_cu[2] = {-1, -1};          // the same for the temporally blocked kernel (k_bt_steps4)
-  int bt_blocks_per_cu[4] = {-1, -1, -1, -1};   // occupancy query results for the persistent barotp kernel's shapes (-1: not asked yet)
-  int barotp_block = 1;      // 1: four substeps per hand-off where the persistent form runs (k_bt_steps4: no arctic patch, one process); 2: the same
-                             // kernel with one launch per four substeps (any number of tiles; the host emulation); 0: off
-  int barotp_persist = 1;    // 1: one launch per barotropic phase where all tiles are resident (stage_barotp_pair.hip)
-  long long *bt_prof = nullptr;   // debug: phase timestamps of k_bt_pair
-  long long *kprof = nullptr;     // debug (builds with -DBLOM_KPROF): per-wavefront phase timestamps of a column kernel, 8 words a wave (blomgpu_dbg_kprof)
-  int kprof_words = 0;
-  int kprof_sel = 1;              // which marked kernel writes: 1 k_pgf_uv*, 2 k_diapfl_column3, 3 k_mxl_column, 4 k_convec_column, 5 k_eddtra_gm, 6 k_mom_column_from, 7 k_diapfl_momentum, 9 k_remap_tile, 10 k_pbc_tile (these two: a word set per WORKGROUP of level 10)
-  int diffus_shfl = 0;       // A/B: west neighbours of diffus' flux kernel through wavefront shuffles
-  int ndiff_rec_per_face = 0;    // neutral diffusion: records per face (0: 6 kk, the bound; stage_ale.hip)
-  int ndiff_surface_align = 1;   // phy/mod_diffusion.F90:84 (the namelist default of cime_config is .true.)
-  int live_slopes = 0;       // blomgpu_step: 1 = cmnfld2 computes nslpx/nslpy every step (stage_cmnfld.hip); 0 = they stay as uploaded
-  int momtum_order = 0;      // A/B: 0 chunk-major work order of the fused kernels, 1 layer-major
-  int momtum_lds_pad = 0;    // experiment: extra bytes of LDS per workgroup of the one-wavefront marches (lowers the occupancy)
-  int momtum_bs = 0;         // lanes per workgroup of the fused kernels (0: 64, one wavefront)
-  int momtum_chunks_a = 0, momtum_chunks_b = 0;   // j-chunks per layer of the two fused kernels (0: one round of workgroups)
-  int diapfl_du = 8;         // levels whose loads k_diapfl_column3 keeps in flight (2, 4, 8)
-  int barotp_tile = 0;       // tile shape of the pair kernel, 100*TI + TJ (3216, 3208, 1608); 0: chosen from the tile count
-  int barotp_fused = 1;      // 1: LDS-tiled substep pairs (stage_barotp_pair.hip), 0: one kernel per equation
-  double *arc_strip = nullptr;                 // arctic patch, tiles of one process in strips mode: this tile's strip
-  size_t arc_cap = 0;
-  int arctic_strips = 0;                       // tiles of one process: arctic fold through packed strips (test of the RCCL path's kernels)
-  double *xcsum_dev = nullptr;                 // sums that stay on the device (thermf), 8 slots
-  double *xcsum_buf = nullptr;                 // [0] the sum, [1..jj] the row sums of xcsum
-  int cnsvdi = 0;                              // mod_budget: conservation diagnostics on/off
-  double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
-  std::string err;
-  std::string expcnf = "channel";   // experiment configuration (mod_config): selects the forcing branches
+  // difest_isobml's diffusivity estimates (stage_difest_iso.hip): the variables of &DIFFUSION that phy/mod_difest.F90 reads
+  // (phy/mod_diffusion.F90:45-110), with the values of the reference's own tests/fuk95/limits as defaults
+  double egc = 0., eggam = 200., eglsmn = 4000., egmndf = 0., egmxdf = 1500., egidfq = 1., rhiscf = 0., ri0 = 1.2, tkepf = 0.;
+  double bdml_logc = 0.;         // log(2 bvf0 / cori30) of the host's libm (set with the plane bdmlq when bdmldp is on)
+  int eddf2d = 0, edsprs = 1, edanis = 0, redi3d = 0, rhsctp = 0, edfsmo = 0;   // (rhsctp: topographic Rhines scale, sin_libm.h, atan2_libm.h)
+  int edritp_opt = 2, edwmth_opt = 1;   // 1 'shear', 2 'large scale'; 1 'smooth', 2 'step' (phy/mod_diffusion.F90:113-116)
+  // ---- what blomgpu_step's sequence consists of ----
+  bool full_physics = false;     // blomgpu_step runs difest_isobml_pre, thermf, mxlayr (+ cmnfld2, cmnfld1): stepper.py FULL_STAGES
+  int difest_live = 0;           // blomgpu_step: 1 = difest_isobml estimates difint, difiso, difdia, difwgt every step (full_physics)
+  int live_slopes = 0;           // blomgpu_step: 1 = cmnfld2 computes nslpx/nslpy every step (stage_cmnfld.hip); 0 = they stay as uploaded
+  int cmnfld1 = 0;               // blomgpu_step ends with cmnfld1 (z, dz of the new state; consumed by diagnostics and difest only)
+  int eddtra_frozen = 0;         // blomgpu_step leaves eddtra out: umfltd, vmfltd, umflsm, vmflsm stay as uploaded
+  int check_period = 8;          // steps between read-backs of the sticky stage error words in blomgpu_step
+  bool timing = false;           // stage timers (HIP events around kernel classes); a step with them runs plain launches
+  // blomgpu_step replays the stage sequence of a step as a HIP graph (one per parity of the time levels), captured from
+  // the stream once the lazily allocated buffers exist; any option / parameter / mask change drops the graphs
+  int use_graph = 0;             // measured slower than plain launches on ROCm 7.2 (channel 8.25 vs 7.90 ms, tnx2v1s 5.44 vs 5.12): off by default
   // ---- stage overlap inside blomgpu_step (round 5) ----------------------------------------------------------------
   // The column kernels of the step (one thread per column, 1.6 wavefronts per SIMD on the channel) wait on their k-serial
   // chains and leave the issue slots and the memory system idle; kernels of ANOTHER stage that do not depend on them run
@@ -407,33 +346,112 @@ struct blomgpu_ctx {
   // -- which reads nothing the stages between difest and momtum write -- can start right after difest's halo updates, and
   // convec's column kernel -- which writes p from dp(kn) -- can run beside momtum's Coriolis kernel, which reads p from dp(km).
   int overlap = 1;               // option: 0 = every stage on the context's stream, in order
+  // phys_dag: in sequence, cmnfld2's three column kernels run on `side` beside difest's common part and its vertical chain, and
+  // difest's lateral part (falign, lateral) follows them there (stage_cmnfld.hip: st_cmnfld2, stage_difest_iso.hip: st_difest_isobml);
+  // bits 2, 4, 8: StepState's diapfl_mom_on_side, updtrc_on_side.  (pgforc's p / dpu / dpv beside diffus' tile kernel: measured, dropped --
+  // a kernel that fills the chip leaves a second queue only its tail, whatever the queue's priority)
+  int phys_dag = 7;              // (bit 8 measured: 0.02 ms on the channel, inside the noise -- off)
+  int mom_early_at = 0;          // momtum's viscous chain forks behind: 0 difest (halo_difest), 1 eddtra, 2 advect, 3 pbcor1, 4 diffus
   // inside blomgpu_step (remap): init_fluxes only zeroes the faces remap does not store, the tile kernel's mass / heat / salt fluxes
   // go to uflx .. vsflx alone and k_remap_update reads them there (12 F of stores less per step); 0: the work planes of rounds 1-4
   int lean_fluxes = 1;
-  // difest_isobml's diffusivity estimates (stage_difest_iso.hip): the variables of &DIFFUSION that phy/mod_difest.F90 reads
-  // (phy/mod_diffusion.F90:45-110), with the values of the reference's own tests/fuk95/limits as defaults
-  double egc = 0., eggam = 200., eglsmn = 4000., egmndf = 0., egmxdf = 1500., egidfq = 1., rhiscf = 0., ri0 = 1.2, tkepf = 0.;
-  double bdml_logc = 0.;         // log(2 bvf0 / cori30) of the host's libm (set with the plane bdmlq when bdmldp is on)
-  int eddf2d = 0, edsprs = 1, edanis = 0, redi3d = 0, rhsctp = 0, edfsmo = 0, edritp_opt = 2, edwmth_opt = 1;
-  int difest_live = 0;           // blomgpu_step: 1 = difest_isobml estimates difint, difiso, difdia, difwgt every step (full_physics)
-  hipStream_t side = nullptr;    // the second stream
+  int tmsmt_fold = 1;            // 0 = pbcor2 always runs its column pass (StepState::pbcor2_dp_in_wk)
+  int tmsmt_ahead = 1;           // blomgpu_step with more steps to come: tmsmt2 also writes what the next step's tmsmt1 would copy
+                                 // (stage_simple.hip); 0 = every step launches its own tmsmt1
+  // inside blomgpu_step k_remap_tile also does k_remap_update's work (stage_remap_tile.hip).  Off: measured equal
+  // (channel 6.41-6.45 against 6.43-6.45 ms per step, remap 0.910 against 0.906 ms) to slower (tnx2v1s 3.71 against 3.66 ms) -- the
+  // overlapping tiles cost the tile kernel what the update kernel took, though 1.1 GB less crosses HBM
+  int remap_fold = 0;
+  // ---- kernel variants (A/B options; the measurement is why the default is what it is) ----
+  int remap_nfirst = 4;          // more than 4 advected tracers: how many of them ride with dp, T, S in k_remap_tile's first pass (0..4; 4 measured fastest)
+  int halo_overlap = 1;          // RCCL tiles: the halo exchange in front of remap runs on xstream while the inner tiles compute
+                                 // (bit-identical; ON by default since round 4, the arctic patch included -- in self-send on one GPU it
+                                 // costs 0.2 ms, 9.78 against 9.59 ms per step; what it buys over xGMI has not been measured)
+  int barotp_fused = 1;          // 1: LDS-tiled substep pairs (stage_barotp_pair.hip), 0: one kernel per equation
+  int barotp_tile = 0;           // tile shape of the pair kernel, 100*TI + TJ (3216, 3208, 1608); 0: chosen from the tile count
+  int barotp_persist = 1;        // 1: one launch per barotropic phase where all tiles are resident (stage_barotp_pair.hip)
+  int barotp_block = 1;          // 1: four substeps per hand-off where the persistent form runs (k_bt_steps4: no arctic patch, one process); 2: the same
+                                 // kernel with one launch per four substeps (any number of tiles; the host emulation); 0: off
+  int barotp_overlap = 0;        // measured slower (see stage_barotp_pair.hip: bt_overlap_usable)
+  int barotp_rimbuf = 1;         // RCCL tiles: barotp's pair kernel reads its E/W rim from the receive buffers
+  int barotp_arctic_persist = 1; // arctic patch, single tile: the odd+even pairs of a phase in the persistent launch (stage_barotp.hip)
+  int barotp_arctic_fused = 1;   // decomposed arctic domain: fused pair kernel with the single tile's exchange schedule
+  int arctic_strips = 0;         // tiles of one process: arctic fold through packed strips (test of the RCCL path's kernels)
+  int pgf_uv_pair = 0;           // k_pgf_uv, A/B option: 1 = the u- and v-column wavefronts of 64 points in one workgroup with XCD-contiguous
+                                 // numbering: fetch 1.44 -> 0.92 GB per launch, but 0.388 against 0.369 ms for the stage (same box, two runs
+                                 // each): the kernel waits on its k-serial chain, not on bytes.  Off.
+  int pgf_uv_ring = 7;           // k_pgf_uv_ring (round 6: every load of the level loop statically countable): 1 = separate u / v workgroups, 2 = paired + XCD-contiguous
+  int pgf_reuse = 0;             // k_pgf_uv: skip the equation of state where a level repeats the previous level's inputs (wave-uniform; bit-identical)
+  int pgf_copy_fused = 1;        // pgforc: the pgfx_o/pgfy_o copy rides along in k_pgf_uv
+  int scan_reassoc = 0;          // TOLERANCE-MODE EXPERIMENT (off): k_pscan with k on the lanes and a log-step shuffle prefix sum -- NOT bit-identical to the reference (stage_simple.hip)
+  int mom_aw_split = 0;          // the viscous march's all-wet (chunk, strip) pairs on a launch of their own with the mask-free kernel (round 6): 1 = one after the other, 2 = side by side on a third stream; measured, off
+  int mom_force_aw = 0;          // TIMING EXPERIMENT ONLY: k_mom_visc_march with the mask-free body alone (wrong next to land)
+  int momtum_order = 0;          // A/B: 0 chunk-major work order of the fused kernels, 1 layer-major
+  int momtum_lds_pad = 0;        // experiment: extra bytes of LDS per workgroup of the one-wavefront marches (lowers the occupancy)
+  int momtum_bs = 0;             // lanes per workgroup of the fused kernels (0: 64, one wavefront)
+  int momtum_chunks_a = 0, momtum_chunks_b = 0;   // j-chunks per layer of the two fused kernels (0: one round of workgroups)
+  int convec_nsingle = 2;        // k_convec_velocity: moves of a level walked singly before chunks of old layers are requested (A/B; 1000 = the kernel of rounds 1-5)
+  int cmn_nslope_nb = 4;         // k_cmn_nslope: interfaces in flight in the interior sweep (A/B: 2, 3, 4)
+  int diapfl_du = 8;             // levels whose loads k_diapfl_column3 keeps in flight (2, 4, 8)
+  int diffus_shfl = 0;           // A/B: west neighbours of diffus' flux kernel through wavefront shuffles
+  int kprof_sel = 1;             // which marked kernel writes: 1 k_pgf_uv*, 2 k_diapfl_column3, 3 k_mxl_column, 4 k_convec_column, 5 k_eddtra_gm, 6 k_mom_column_from, 7 k_diapfl_momentum, 9 k_remap_tile, 10 k_pbc_tile (these two: a word set per WORKGROUP of level 10)
+
+  // ==== runtime state: views, streams, events, buffers, counters =====================================================================
+  DevView h;                 // host copy (pointers are device pointers)
+  DevView *d = nullptr;      // device copy handed to kernels
+  bool dirty = true;         // host copy changed since last upload
+  int device = 0;
+  hipStream_t stream = nullptr;
+  bool stream_borrowed = false;  // this context runs on another context's stream (the global barotropic context of a tile)
+  // second stream for halo exchanges that overlap with compute (RCCL tiles: barotp), its fork/join events,
+  // and the stream the RCCL transport enqueues on when set (otherwise `stream`)
+  hipStream_t xstream = nullptr, halo_stream = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipStream_t side = nullptr;    // the second stream of the stage overlap (`overlap` above)
   hipEvent_t ev_side[10] = {};
   DevView hv[4];                 // host copies of the alternative views (hv[0] unused: the main view is h)
   DevView *dv[4] = {nullptr, nullptr, nullptr, nullptr};
   double *wk_mom = nullptr, *p_alt = nullptr, *pu_alt = nullptr, *pv_alt = nullptr;
-  bool mom_early_done = false;   // in sequence: momtum's viscous chain of this step is already running on `side`
-  bool convec_col_ahead = false; // in sequence: convec's column kernel of this step is already running on `side`
-  // phys_dag: in sequence, cmnfld2's three column kernels run on `side` beside difest's common part and its vertical chain, and
-  // difest's lateral part (falign, lateral) follows them there (stage_cmnfld.hip: st_cmnfld2, stage_difest_iso.hip: st_difest_isobml)
-  int phys_dag = 7;              // (bit 8 measured: 0.02 ms on the channel, inside the noise -- off)
-  int mom_early_at = 0;          // momtum's viscous chain forks behind: 0 difest (halo_difest), 1 eddtra, 2 advect, 3 pbcor1, 4 diffus
-  bool cmn_on_side = false;      // in sequence: cmnfld2's kernels of this step are on `side`, nothing has waited for them yet
-  // the same option's bits 2 and 4, small launches beside long ones: diapfl's momentum mixing beside thermf and mxlayr's first kernels (2),
-  // updtrc's ideal-age step beside barotp's first kernels (4), mxlayr's copy-back clamp beside the rest of mxlayr (8; `updtrc_on_side` says that
-  // something on the second stream has to be waited for in front of pbcor2).  (pgforc's p / dpu / dpv beside diffus' tile kernel: measured, dropped --
-  // a kernel that fills the chip leaves a second queue only its tail, whatever the queue's priority)
-  bool diapfl_mom_on_side = false, updtrc_on_side = false;
-  bool pscan_done_ahead = false; // in sequence: st_cmnfld2 has launched the pressure scan of difest_isobml's front part (blomgpu_halo_difest)
+  hipStream_t side3 = nullptr;   // the viscous march's land-side pairs beside its all-wet pairs (mom_aw_split = 2)
+  hipEvent_t ev_side3[2] = {nullptr, nullptr};
+  int mom_aw_key = -1, mom_aw_n[2] = {0, 0};
+  int *mom_aw_dev = nullptr;     // the two launch lists, device memory
+  int nlev_real[NF_REAL];
+  int nlev_int[NF_INT];
+  std::unordered_map<std::string, int> real_ids, int_ids;
+  std::unordered_map<std::string, KTimer> timers;
+  Tiling tiling;
+  BtGlobal *bt_global = nullptr; // RCCL tiles: barotp gathers its 2-D inputs and solves the global domain on a second context
+  std::string err;
+  // device error words: [0] diapfl, [1] eddtra, [2] barotp abort.  Stage entries read theirs back at once;
+  // blomgpu_step defers the read-back to the end of the step (one host sync per step instead of three)
+  int *err_dev = nullptr;
+  StepState seq;                 // hand-overs between the stages of the step that is running
+  // these two live across TWO steps of one blomgpu_step call (tmsmt2 of a step does the next step's tmsmt1), so they are not part of
+  // StepState: blomgpu_step sets tmsmt1_ahead per step, tmsmt2 sets tmsmt1_done_ahead, the next step_sequence consumes it
+  bool tmsmt1_ahead = false, tmsmt1_done_ahead = false;
+  hipGraphExec_t step_graph[2] = {nullptr, nullptr};
+  int steps_done = 0;
+  int steps_warm = 0;            // plain steps since the last option change (graph capture waits for 2: both time levels' buffers exist)
+  long long graph_steps = 0;     // steps replayed as graphs (blomgpu_get_real "graph_steps")
+  int graph_failures = 0;        // captures that began and failed (tried again after two more plain steps, three times at most)
+  bool cppm_ready = false;       // init_cppm has run (tables on the device)
+  void *ale = nullptr;           // ale_regrid_remap: the engine's structures; the pressure levels of vcoord_type = 'plevel'
+  double *ale_plevel = nullptr;
+  bool bt_restart = true;        // the next persistent barotp launch zeroes the completion counts and starts at epoch 0
+  unsigned bt_epoch = 0;         // completion count every tile has reached after the launches so far
+  unsigned *bt_flags = nullptr;  // abort word + per-tile completion counts of the persistent barotp kernel
+  int num_cus = 0;
+  int bt4_blocks_per_cu[2] = {-1, -1};          // the same for the temporally blocked kernel (k_bt_steps4)
+  int bt_blocks_per_cu[4] = {-1, -1, -1, -1};   // occupancy query results for the persistent barotp kernel's shapes (-1: not asked yet)
+  long long *bt_prof = nullptr;   // debug: phase timestamps of k_bt_pair
+  long long *kprof = nullptr;     // debug (builds with -DBLOM_KPROF): per-wavefront phase timestamps of a column kernel, 8 words a wave (blomgpu_dbg_kprof)
+  int kprof_words = 0;
+  double *arc_strip = nullptr;                 // arctic patch, tiles of one process in strips mode: this tile's strip
+  size_t arc_cap = 0;
+  double *xcsum_dev = nullptr;                 // sums that stay on the device (thermf), 8 slots
+  double *xcsum_buf = nullptr;                 // [0] the sum, [1..jj] the row sums of xcsum
+  double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space

@@ -448,7 +448,7 @@ int rccl_barotp_replicated(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m
   hipStream_t st = c->stream;
   // the solver's scalar options follow the tile's (set through the tile's context only)
   if (memcmp(&G->h.P, &h.P, sizeof(Params)) != 0) { G->h.P = h.P; G->dirty = true; }
-  G->defer_checks = c->defer_checks;
+  G->seq.defer_checks = c->seq.defer_checks;
   ctx_sync_view(G);
   if (int rc = st_barotp_bounds(c, m, nn)) return rc;        // :177-224: the one part of barotp that reads 3-D fields
   BtPlanes PT, PG;

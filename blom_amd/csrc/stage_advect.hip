@@ -186,9 +186,9 @@ int st_advect(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   // rim lies inside the tile -- they read no halo point of cau, cav or the tracers -- run meanwhile; the tiles along the
   // edge follow when the halos have landed.  The exchange reads interior strips and writes halo points only.
   // inside blomgpu_step the tile kernel also does the update and hands the new dp, T, S, tracers to pbcor1 through the work space
-  const bool fold = c->in_sequence && c->remap_fold;
+  const bool fold = c->seq.in_sequence && c->remap_fold;
   // the flux arrays of level m were zeroed in this step and nothing has added to them: the tile kernel's fluxes ARE uflx .. vsflx (m)
-  const int mmlean = !fold && c->in_sequence && c->fluxes_zeroed && c->lean_fluxes ? mm : -1;
+  const int mmlean = !fold && c->seq.in_sequence && c->seq.fluxes_zeroed && c->lean_fluxes ? mm : -1;
   const bool ovl = c->tiling.rccl && c->xstream && c->halo_overlap && !c->timing;
   if (ovl) {
     HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
@@ -208,7 +208,7 @@ int st_advect(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     if (int rc = remap_tile_launch(c, n, mm, nn, 0, fold)) return rc;
     if (!fold) hipLaunchKernelGGL(k_remap_update, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, nn, mmlean);
   }
-  c->remap_handed_over = fold;
+  c->seq.remap_handed_over = fold;
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -891,7 +891,7 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
   int rc;
   // the status of the engine's calls is read back once, at the end -- or, inside blomgpu_step, with the other sticky error
   // words every check_period steps (ale_check_deferred): no host synchronisation inside the step
-  const bool defer = c->defer_checks;
+  const bool defer = c->seq.defer_checks;
   // an error return between here and the end of the stage must leave no work of the second diffusion stream unjoined and the
   // engine's grids out of their sticky mode (the status then reaches the caller through the failing call itself)
   struct Unwind {
@@ -1016,7 +1016,7 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
     A.rec_n = a->nd_reck; A.rec_k = a->nd_reck + 2 * np; A.rec_s = A.rec_k + a->nd_nrec * 2 * np; A.rec_g = a->nd_recg;
     A.rec_f = a->nd_rec; A.nrec_max = (int)a->nd_nrec;
     A.prof = c->kprof; A.prof_words = c->kprof_words;     // (its own buffer with its size: until round 6 the barotropic profiler's, unchecked)
-    A.flux_zero = c->in_sequence && c->fluxes_zeroed ? 1 : 0;
+    A.flux_zero = c->seq.in_sequence && c->seq.fluxes_zeroed ? 1 : 0;
     A.puv = A.scr + ndiff_scratch_planes(h.kk) * 2 * np;
     A.kk = h.kk; A.npc = npc; A.ntr_loc = a->ntr_loc; A.mm = mm; A.nn = nn; A.surface_align = c->ndiff_surface_align;
     HIPCHK(c, hipEventRecord(a->ev_fork2, c->stream));
@@ -1024,7 +1024,7 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
     unwind.forked2 = true;
     if (int rc2 = st_ndiff_prep_flux(c, a->side2, a->ev_snap, A, a->nd_ks, a->nd_ks + np, a->nd_col, a->nd_col + (size_t)4 * per, a->nd_col + (size_t)6 * per))
       return rc2;
-    c->fluxes_zeroed = false;                   // utflx .. vsflx carry the diffusive fluxes now: advect must add to them
+    c->seq.fluxes_zeroed = false;                   // utflx .. vsflx carry the diffusive fluxes now: advect must add to them
   }
   if ((rc = blomgpu_h3m_prepare_remapping(a->grid, a->map, pdst))) return ale_fail(c, "prepare_remapping", rc);
   const double *flx = ndiff ? a->nd_col + (size_t)8 * per : nullptr;

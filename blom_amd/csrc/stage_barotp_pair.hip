@@ -1190,6 +1190,6 @@ int bt_block_launch(blomgpu_ctx *c, int mode, int m, int n, int ml, int nl, cons
 
 // did any tile of the persistent launches give up waiting?  (checked once per barotp call)
 int bt_phase_check(blomgpu_ctx *c) {
-  if (c->defer_checks) return 0;
+  if (c->seq.defer_checks) return 0;
   return ctx_check_errors(c);
 }

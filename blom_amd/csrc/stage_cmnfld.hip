@@ -666,7 +666,7 @@ int st_cmnfld2(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     // at the start of difest_isobml (api.hip: blomgpu_halo_difest; nothing in between changes dp or its halo): that scan goes in front of the
     // fork, so that no kernel writes p while these read it
     if (int rc = launch_pscan(c, nn, -2, 3)) return rc;
-    c->pscan_done_ahead = true;
+    c->seq.pscan_done_ahead = true;
     if (int rc = ctx_side_fork(c, 4)) return rc;
     s = c->side;
   }
@@ -679,6 +679,6 @@ int st_cmnfld2(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     default: hipLaunchKernelGGL(k_cmn_nslope<2>, g2, dim3(64), 0, s, c->d, n, nn); break;
   }
   HIPCHK(c, hipGetLastError());
-  c->cmn_on_side = aside;
+  c->seq.cmn_on_side = aside;
   return 0;
 }

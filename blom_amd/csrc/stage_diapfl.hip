@@ -235,14 +235,14 @@ int st_diapfl(blomgpu_ctx *c, int n, int nn, int k1n) {
     // inside blomgpu_step the stage that follows (mxlayr's tail, phy/mod_mxlayr.F90:1266-1310) recomputes dpu, dpv of this
     // level from the same p with the same expression over a larger range before anything reads them: skipped there
     // (with full_physics the real mxlayr follows, which reads them first)
-    if (!c->in_sequence || c->full_physics) hipLaunchKernelGGL(k_diapfl_dpudpv, plane_grid(h, h.kk), dim3(256), 0, s, c->d, nn);
+    if (!c->seq.in_sequence || c->full_physics) hipLaunchKernelGGL(k_diapfl_dpudpv, plane_grid(h, h.kk), dim3(256), 0, s, c->d, nn);
     if (aside) {
       if (int rc = ctx_side_done(c, 7)) return rc;
-      c->diapfl_mom_on_side = true;
+      c->seq.diapfl_mom_on_side = true;
     }
   }
   HIPCHK(c, hipGetLastError());
   // the reference aborts (xchalt) when the implicit solve does not converge, :520-530
-  if (!c->defer_checks) return ctx_check_errors(c);
+  if (!c->seq.defer_checks) return ctx_check_errors(c);
   return 0;
 }

@@ -1069,7 +1069,7 @@ int st_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn) {
     if (D.rhsctp) hipLaunchKernelGGL(k_dfi_falign, plane_grid(h, h.kk), dim3(256), 0, sl, c->d, n, nn);
     hipLaunchKernelGGL(k_dfi_lateral, g1, b64, 0, sl, c->d, D, n, nn);
     if (aside) {
-      c->cmn_on_side = false;
+      c->seq.cmn_on_side = false;
       if (int rc = ctx_side_done(c, 4)) return rc;
       if (int rc = ctx_side_join(c, 4)) return rc;
     }

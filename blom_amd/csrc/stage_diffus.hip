@@ -217,8 +217,8 @@ int st_diffus(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   const DevView &h = c->h;
   const size_t np = h.nplane;
   if (3 + h.ntr > h.nwk || h.ntr > 64) return ctx_fail(c, "diffus: work space too small for this many tracers");
-  const bool handed = c->pbcor1_handed_over;                 // pbcor1 left S, T and its tracers in the work space
-  c->pbcor1_handed_over = false;
+  const bool handed = c->seq.pbcor1_handed_over;                 // pbcor1 left S, T and its tracers in the work space
+  c->seq.pbcor1_handed_over = false;
   if (int rc = st_xctilr(c, h.f[F_dp] + (size_t)(k1n - 1) * np, 1, h.kk, 3, 3, 1)) return rc;        // :58
   if (h.P.ltedtp_opt == 2) {
     // ltedtp = 'neutral', :59-70: the lateral diffusion is ale_regrid_remap's (stage_ndiff.hip); only the halo updates remain

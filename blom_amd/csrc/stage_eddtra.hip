@@ -334,6 +334,6 @@ int st_eddtra(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     hipLaunchKernelGGL(k_eddtra_ts, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, mm);
   }
   HIPCHK(c, hipGetLastError());
-  if (h.P.eitmth == 2 && !c->defer_checks) return ctx_check_errors(c);      // :536-555, :640-660
+  if (h.P.eitmth == 2 && !c->seq.defer_checks) return ctx_check_errors(c);      // :536-555, :640-660
   return 0;
 }

@@ -386,6 +386,6 @@ int st_eddtra_ale(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n
     hipLaunchKernelGGL(k_eda_ts, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, mm);
   }
   HIPCHK(c, hipGetLastError());
-  if (!c->defer_checks) return ctx_check_errors(c);
+  if (!c->seq.defer_checks) return ctx_check_errors(c);
   return 0;
 }

@@ -122,7 +122,7 @@ static int momtum_visc_chain(blomgpu_ctx *c, int m, int n, int mm, int nn) {
 // reads u, v (n), dpu, dpv (m), pbu, pbv, ubflxs_p, difwgt and the grid -- nothing that eddtra, advect, pbcor1, diffus or
 // pgforc write -- and writes momtum's own planes and utotn, vtotn (read by barotp only)
 int st_momtum_early(blomgpu_ctx *c, int m, int n, int mm, int nn) {
-  c->mom_early_done = false;
+  c->seq.mom_early_done = false;
   if (!ctx_overlap_on(c) || c->tiling.multi()) return 0;
   if (int rc = st_xctilr(c, c->h.f[F_difwgt], 1, 1, 2, 2, 1)) return rc;                    // :340 (difwgt is not written in between)
   if (int rc = ctx_side_fork(c, 0)) return rc;
@@ -132,7 +132,7 @@ int st_momtum_early(blomgpu_ctx *c, int m, int n, int mm, int nn) {
   c->stream = main;
   if (rc) return rc;
   if (int rc2 = ctx_side_done(c, 1)) return rc2;
-  c->mom_early_done = true;
+  c->seq.mom_early_done = true;
   return 0;
 }
 
@@ -149,11 +149,11 @@ int st_momtum(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   // the module arrays p, pu, pv as the reference's momtum leaves them: p (:245-254) and, outside the interior, pu, pv (:322-338; inside
   // it the vertical pass rewrites them, :1252-1267).  Inside blomgpu_step's isopycnic sequence only the ring of p outside the interior:
   // convec's column kernel, the next writer of the interior's p, may already be running on the second stream
-  hipLaunchKernelGGL(k_mom_pscan, gcol, b64, 0, c->stream, c->d, mm, -1, 2, c->in_sequence && h.P.vcoord_tag == 1 ? 1 : 0);
+  hipLaunchKernelGGL(k_mom_pscan, gcol, b64, 0, c->stream, c->d, mm, -1, 2, c->seq.in_sequence && h.P.vcoord_tag == 1 ? 1 : 0);
   hipLaunchKernelGGL(k_mom_pupv, gcol, b64, 0, c->stream, c->d, mm, -1, 2, 1);
   hipLaunchKernelGGL(k_mom_drag, gcol, b64, 0, c->stream, ctx_view(c, VIEW_MOM_B), n, nn);
-  if (c->mom_early_done) {
-    c->mom_early_done = false;
+  if (c->seq.mom_early_done) {
+    c->seq.mom_early_done = false;
     if (int rc = ctx_side_join(c, 1)) return rc;
   } else {
     if (int rc = st_xctilr(c, h.f[F_difwgt], 1, 1, 2, 2, 1)) return rc;                     // :340

@@ -1049,8 +1049,8 @@ int st_mxlayr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   if (int rc = st_xctilr(c, h.f[F_util1], 1, 1, 1, 1, 1)) return rc;
   hipLaunchKernelGGL(k_mxl_bg2_grad, plane_grid(h), dim3(256), 0, c->stream, c->d);
   hipLaunchKernelGGL(k_mxl_bg2_sum, plane_grid(h), dim3(256), 0, c->stream, c->d);
-  if (c->diapfl_mom_on_side) {               // diapfl's momentum mixing on the second stream (stage_diapfl.hip): u, v, dpu, dpv are read from here on
-    c->diapfl_mom_on_side = false;
+  if (c->seq.diapfl_mom_on_side) {               // diapfl's momentum mixing on the second stream (stage_diapfl.hip): u, v, dpu, dpv are read from here on
+    c->seq.diapfl_mom_on_side = false;
     if (int rc = ctx_side_join(c, 7)) return rc;
   }
   if (c->rm5 > 0.) {                                                                            // :287-290
@@ -1067,7 +1067,7 @@ int st_mxlayr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     if (int rc = ctx_side_fork(c, 6)) return rc;
   hipLaunchKernelGGL(k_mxl_clamp, plane_grid(h, h.ntr + 1, 64), dim3(64), 0, clamp_aside ? c->side : c->stream, c->d, nn);
   HIPCHK(c, hipGetLastError());
-  if (clamp_aside) c->updtrc_on_side = true;
+  if (clamp_aside) c->seq.updtrc_on_side = true;
   // 'old' interface pressures at the velocity points (:1243-1262), the dp halo, p and the new dpu, dpv (:1264-1310), the
   // velocities onto the new layers (:1312-1374)
   if (int rc = st_mom_pupv(c, nn, 1, 0)) return rc;

@@ -114,8 +114,8 @@ static int pbcor(blomgpu_ctx *c, int which, int m, int n, int mm, int nn, int k1
     }
   }
   TimeScope ts(c, which == 1 ? "pbcor1" : "pbcor2");
-  const int from_remap = which == 1 && c->in_sequence && c->remap_handed_over ? 1 : 0;
-  if (which == 1) c->remap_handed_over = false;
+  const int from_remap = which == 1 && c->seq.in_sequence && c->seq.remap_handed_over ? 1 : 0;
+  if (which == 1) c->seq.remap_handed_over = false;
   hipLaunchKernelGGL(k_pbc_pscan, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, which, offc, from_remap);
   hipLaunchKernelGGL(k_pbc_total, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, which, m, n, offf);
   if (int rc = pbcor_tile_launch(c, which, m, offc, offf, from_remap)) return rc;

@@ -47,17 +47,17 @@ int st_init_fluxes(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
   (void)m; (void)n; (void)nn; (void)k1m; (void)k1n;
   const DevView &h = c->h;
   TimeScope ts(c, "init_fluxes");
-  if (c->in_sequence && c->lean_fluxes && h.P.advmth == 0 && h.P.vcoord_tag == 1 && !c->remap_fold) {
+  if (c->seq.in_sequence && c->lean_fluxes && h.P.advmth == 0 && h.P.vcoord_tag == 1 && !c->remap_fold) {
     hipLaunchKernelGGL(k_init_fluxes_ring, dim3((h.ii + h.jj + 6 + 63) / 64, h.kk), dim3(64), 0, c->stream, c->d, mm);
     HIPCHK(c, hipGetLastError());
-    c->fluxes_zeroed = true;
-    c->fluxes_lean = true;         // the contract: the next toucher of uflx .. vsflx (m) is remap's STORING tile kernel (checked there and in blomgpu_step)
+    c->seq.fluxes_zeroed = true;
+    c->seq.fluxes_lean = true;         // the contract: the next toucher of uflx .. vsflx (m) is remap's STORING tile kernel (checked there and in blomgpu_step)
     return 0;
   }
   hipLaunchKernelGGL(k_init_fluxes, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, mm);
   HIPCHK(c, hipGetLastError());
-  c->fluxes_zeroed = c->in_sequence;
-  c->fluxes_lean = false;
+  c->seq.fluxes_zeroed = c->seq.in_sequence;
+  c->seq.fluxes_lean = false;
   return 0;
 }
 
@@ -317,12 +317,12 @@ __global__ void k_tmsmt_dpold_seam(const DevView *__restrict__ Vp, int mm) {
 
 int st_tmsmt2(blomgpu_ctx *c, int m, int mm, int nn, int k1m) {
   TimeScope ts(c, "tmsmt");
-  const int dp_in_wk = c->pbcor2_dp_in_wk ? 1 : 0;
-  c->pbcor2_dp_in_wk = false;
+  const int dp_in_wk = c->seq.pbcor2_dp_in_wk ? 1 : 0;
+  c->seq.pbcor2_dp_in_wk = false;
   hipLaunchKernelGGL(k_tmsmt2_fac, plane_grid(c->h, 1, 64), dim3(64), 0, c->stream, c->d, m, nn, dp_in_wk);
-  const int from_wk = c->pbcor2_handed_over ? 1 : 0;
-  c->pbcor2_handed_over = false;
-  const int ahead = c->in_sequence && c->tmsmt1_ahead ? 1 : 0;
+  const int from_wk = c->seq.pbcor2_handed_over ? 1 : 0;
+  c->seq.pbcor2_handed_over = false;
+  const int ahead = c->seq.in_sequence && c->tmsmt1_ahead ? 1 : 0;
   hipLaunchKernelGGL(k_tmsmt2, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, mm, nn, from_wk, ahead, dp_in_wk);
   HIPCHK(c, hipGetLastError());
   c->tmsmt1_done_ahead = ahead != 0;
@@ -386,7 +386,7 @@ int st_updtrc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   HIPCHK(c, hipGetLastError());
   if (aside) {
     if (int rc = ctx_side_done(c, 9)) return rc;
-    c->updtrc_on_side = true;
+    c->seq.updtrc_on_side = true;
   }
   return 0;
 }

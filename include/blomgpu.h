@@ -50,6 +50,9 @@ int  blomgpu_set_real(blomgpu_ctx *ctx, const char *name, double v);
 int  blomgpu_set_int (blomgpu_ctx *ctx, const char *name, int v);
 int  blomgpu_set_str (blomgpu_ctx *ctx, const char *name, const char *v);
 int  blomgpu_get_real(blomgpu_ctx *ctx, const char *name, double *v);
+/* The names the three setters know, one table (blom_amd/csrc/api.hip): index 0, 1, ... until the return value is non-zero;
+ * kind 0 = blomgpu_set_real, 1 = blomgpu_set_int, 2 = blomgpu_set_int (stored as v != 0), 3 = blomgpu_set_str. */
+int  blomgpu_option_name(int index, char *buf, int cap, int *kind);
 
 /* Field access.  nlev is the size of the third dimension (trc: 2*kdm*ntr). */
 int  blomgpu_field_info(blomgpu_ctx *ctx, const char *name, int *nlev, int *is_int);
