@@ -436,6 +436,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   if (c->err_dev) (void)hipFree(c->err_dev);
   if (c->bt_flags) (void)hipFree(c->bt_flags);
   ale_free(c);
+  dia_free(c);
   if (c->ale_plevel) (void)hipFree(c->ale_plevel);
   if (c->arc_strip) (void)hipFree(c->arc_strip);
   if (c->xcsum_buf) (void)hipFree(c->xcsum_buf);
@@ -624,6 +625,19 @@ int blomgpu_tmsmt1(blomgpu_ctx *c, int nn) { ctx_sync_view(c); return st_tmsmt1(
 int blomgpu_tmsmt2(blomgpu_ctx *c, int m, int mm, int nn, int k1m) { ctx_sync_view(c); return st_tmsmt2(c, m, mm, nn, k1m); }
 int blomgpu_initms(blomgpu_ctx *c, int mm) { ctx_sync_view(c); return st_initms(c, mm); }
 int blomgpu_diapfl(blomgpu_ctx *c, int n, int nn, int k1n) { ctx_sync_view(c); return st_diapfl(c, n, nn, k1n); }
+// diaacc (phy/mod_dia.F90:1092): the count of accumulated steps first (:1123-1125), then the accumulation (stage_diaacc.hip)
+int blomgpu_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
+  if (!dia_active(c)) return 0;
+  ctx_sync_view(c);
+  dia_count(c);
+  return st_diaacc(c, m, n, mm, nn, k1m, k1n);
+}
+int blomgpu_dia_select(blomgpu_ctx *c, const char *names) { return dia_select(c, names); }
+int blomgpu_dia_nacc(blomgpu_ctx *c, int *nacc) { return dia_nacc(c, nacc); }
+int blomgpu_dia_get(blomgpu_ctx *c, const char *name, double *out) { return dia_get(c, name, out); }
+int blomgpu_dia_finalize(blomgpu_ctx *c) { return dia_finalize(c); }
+int blomgpu_dia_reset(blomgpu_ctx *c) { return dia_reset(c); }
+int blomgpu_dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) { return dia_name(index, buf, cap, is_lyr, grid); }
 // sfcstr, phy/mod_sfcstr.F90:33-62: the surface stress of the idealised experiments is set at initialisation
 // (or absent), so the stage is empty for them; the coupled/reanalysis branches live in modules that are
 // not part of this path.
@@ -778,7 +792,8 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
   X(halo_difest_hyb, blomgpu_halo_difest_hyb(c, 0, k1n)) X(halo_difest_vert, blomgpu_halo_difest_hyb(c, 1, k1n))                  \
   X(mxlayr_tail, blomgpu_mxlayr_tail(c, nn, k1n)) X(mxlayr, blomgpu_mxlayr(ALL6)) X(thermf, blomgpu_thermf(ALL6))                 \
   X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
-  X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6))
+  X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6)) \
+  X(diaacc, blomgpu_diaacc(ALL6))
 enum StageId {
 #define X(nm, call) S_##nm,
   BLOM_STAGES(X)
@@ -872,7 +887,12 @@ static int step_sequence(STAGE_ARGS) {
     leave.failed = false;
   }
   // (outside the sequence: nothing is handed to it and it defers nothing)
-  if (!ale && (c->cmnfld1 || c->full_physics)) return stage(S_cmnfld1);     // phy/mod_blom_step.F90:233
+  if (!ale && (c->cmnfld1 || c->full_physics))
+    if (int rc = stage(S_cmnfld1)) return rc;                               // phy/mod_blom_step.F90:233
+  // diaacc (:239) with a selection: on the context's stream, behind everything the step put on the second one (the last of it
+  // is joined in front of pbcor2).  Its sources are arrays of the finished step; the tmsmt1 that tmsmt_ahead folded into tmsmt2
+  // wrote *old arrays only.  blomgpu_step counts the step (a capture passes here without executing)
+  if (dia_active(c)) return st_diaacc(ALL6);
   return 0;
 }
 #undef ALL6
@@ -884,6 +904,7 @@ static int step_sequence(STAGE_ARGS) {
 // Single tile only (the RCCL transport and the in-process tile groups synchronise on the host); not while stage timers run.
 int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
   const int kk = c->h.kk;
+  if (int rc = dia_step_check(c)) return rc;
   for (int it = 0; it < nsteps; it++) {
     const int ns = *nstep;
     const int m = ns % 2 + 1, n = (ns + 1) % 2 + 1;
@@ -928,6 +949,7 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     }
     if (graph) { HIPCHK(c, hipGraphLaunch(ge, c->stream)); c->graph_steps++; }
     else if (int rc = step_sequence(c, m, n, mm, nn, k1m, k1n)) { c->tmsmt1_done_ahead = false; return rc; }
+    dia_count(c);                                          // nacc_phy, phy/mod_dia.F90:1123-1125
     c->steps_done++;
     c->steps_warm++;
     // the stages' error words are sticky: one read-back (a host synchronisation) per check_period steps (every step with

@@ -239,6 +239,7 @@ struct blomgpu_ctx;
 struct TileGroup;            // in-process transport: several tiles (contexts) on one device, one host thread each
 struct RcclComm;             // one process per GPU, neighbour ncclSend/ncclRecv over xGMI
 struct BtGlobal;             // RCCL tiles: the barotropic solve replicated on every rank (comm_rccl.hip)
+struct DiaState;             // the selected time-mean diagnostics and their accumulators (stage_diaacc.hip)
 // The general tile table of xcspmd (phy/mod_xc.F90:1332-1720), kept for ragged layouts only: tile rows cut differently,
 // tiles shrunk to their sea points, all-land tiles eliminated (ii = 0).  Tensor-product layouts never carry one.
 struct TileTable {
@@ -452,6 +453,7 @@ struct blomgpu_ctx {
   double *xcsum_dev = nullptr;                 // sums that stay on the device (thermf), 8 slots
   double *xcsum_buf = nullptr;                 // [0] the sum, [1..jj] the row sums of xcsum
   double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
+  DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space
@@ -535,6 +537,19 @@ int st_ale_regrid_remap(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, in
 void ale_free(blomgpu_ctx *);
 int ale_check_deferred(blomgpu_ctx *);      // stage_ale.hip: the engine's status of the steps since the last check
 int st_mxlayr(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_mxlayr.hip
+// stage_diaacc.hip: diaacc's accumulators (phy/mod_dia.F90).  st_diaacc launches the accumulation and leaves the count of
+// accumulated steps to its callers (dia_count): a graph capture runs the sequence without executing it
+int st_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
+int dia_select(blomgpu_ctx *, const char *names);
+int dia_reset(blomgpu_ctx *);
+int dia_finalize(blomgpu_ctx *);
+int dia_nacc(blomgpu_ctx *, int *nacc);
+int dia_get(blomgpu_ctx *, const char *name, double *out);
+int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
+int dia_step_check(blomgpu_ctx *);           // a selection that reads z / dz in a sequence without cmnfld1: fails
+bool dia_active(const blomgpu_ctx *);
+void dia_count(blomgpu_ctx *);
+void dia_free(blomgpu_ctx *);
 int st_mom_pupv(blomgpu_ctx *, int off, int lo, int hi);                          // stage_momtum.hip
 int st_convec_velocity(blomgpu_ctx *, int nn);                                    // stage_convec.hip
 int launch_dpudpv(blomgpu_ctx *, int off, int flags);                                        // stage_simple.hip

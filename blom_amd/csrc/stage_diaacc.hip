@@ -1,0 +1,381 @@
+// diaacc: the time-mean diagnostics of phy/mod_dia.F90 accumulated on the device (phy/mod_blom_step.F90:239).
+//
+// The reference's accumulators are `acc = acc + fld*w` (acch2d :5182, acclyr :5471), `acc = max(acc, fld)` (maxh2d :5285) and
+// `acc = acc + fld*fld` (sqh2d :5409) at the owned points i = 1..ii, j = 1..jj where the grid's own mask is set, starting from
+// `inival*mask` over the whole padded plane (inih2d :5001, inilyr :5055).  No bit depends on an order of summation, there is no
+// halo and no communication: pure streaming read-modify-write, HBM-bound.
+//
+// The selected accumulators live in ONE allocation [slot][level][padded plane] in the model's plane layout.  A step launches
+// k_diaacc twice: once over (plane, level) for all selected layer accumulators, once over the plane for the 2-D ones.  One thread
+// per point and level; it loads its masks (mpack) once, each weight dp / dpu / dpv (km) and each shared source ub / vb (m) once,
+// and then walks the slot table -- a table of ints in the kernel arguments, fetched with scalar loads in a
+// wave-uniform loop -- DIA_U slots at a time: all loads of the group are issued before its stores.
+// Algorithmic bytes per launch: (2 n_acc + n_distinct_sources) F.
+#include "../../include/blomgpu.h"
+#include "blomgpu_internal.h"
+#include <cstring>
+
+namespace {
+enum { G_P = 0, G_U = 1, G_V = 2 };                 // the grid = the bit of mpack that masks it
+enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2 };
+enum { W_NONE = 0, W_DP = 1, W_DPU = 2, W_DPV = 3 };       // weight (km); also: the register a source is taken from
+enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src + ub(m) | src + vb(m) | src + a second plane | src*onem
+// the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
+enum { LV_0, LV_M, LV_N, LV_KK, LV_MM, LV_NN, LV_TKE, LV_GLS };
+enum { SRC_DPML = -1 };                             // dpml as :1148-1171 forms it
+constexpr double ONEM = 9806.;                      // phy/mod_constants.F90
+constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948)
+constexpr double EPSIL = 1.e-11, NF90_FILL_DOUBLE = 9.9692099683868690e+36;   // finlyr, :6126, :6140
+
+// One row per accumulator; the name is the reference's ACC_* suffix in lower case, `line` the call in phy/mod_dia.F90.
+struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; };
+#define H2D(nm, g, f, lv, ln) {#nm, 0, g, OP_SUM, f, lv, W_NONE, A_NONE, ln}
+#define LYR(nm, g, f, lv, w, ln) {#nm, 1, g, OP_SUM, f, lv, w, A_NONE, ln}
+const DiaRow g_rows[] = {
+  // ---- acch2d, :1547-1745 ----
+  H2D(ub, G_U, F_ub, LV_M, 1547), H2D(ubflxs, G_U, F_ubflxs, LV_N, 1550), H2D(taux, G_U, F_taux, LV_0, 1556),
+  H2D(vb, G_V, F_vb, LV_M, 1565), H2D(vbflxs, G_V, F_vbflxs, LV_N, 1568), H2D(tauy, G_V, F_tauy, LV_0, 1574),
+  H2D(psrf, G_P, F_p, LV_0, 1583), H2D(pbot, G_P, F_p, LV_KK, 1586), H2D(sealv, G_P, F_z, LV_0, 1589),
+  H2D(sigmx, G_P, F_sigma, LV_MM, 1592), H2D(swa, G_P, F_swa, LV_0, 1616), H2D(nsf, G_P, F_nsf, LV_0, 1619),
+  H2D(hmltfz, G_P, F_hmltfz, LV_0, 1625), H2D(lip, G_P, F_lip, LV_0, 1631), H2D(sop, G_P, F_sop, LV_0, 1634),
+  H2D(eva, G_P, F_eva, LV_0, 1637), H2D(fmltfz, G_P, F_fmltfz, LV_0, 1640), H2D(sfl, G_P, F_sfl, LV_0, 1643),
+  H2D(rnfflx, G_P, F_rnf, LV_0, 1649), H2D(rfiflx, G_P, F_rfi, LV_0, 1652), H2D(ustar, G_P, F_ustar, LV_0, 1655),
+  H2D(ustar3, G_P, F_ustar3, LV_0, 1658), H2D(idkedt, G_P, F_idkedt, LV_0, 1661), H2D(mtkeus, G_P, F_mtkeus, LV_0, 1667),
+  H2D(mtkeni, G_P, F_mtkeni, LV_0, 1670), H2D(mtkebf, G_P, F_mtkebf, LV_0, 1673), H2D(mtkers, G_P, F_mtkers, LV_0, 1676),
+  H2D(mtkepe, G_P, F_mtkepe, LV_0, 1679), H2D(mtkeke, G_P, F_mtkeke, LV_0, 1682), H2D(sss, G_P, F_saln, LV_MM, 1691),
+  H2D(sst, G_P, F_temp, LV_MM, 1694), H2D(bld, G_P, SRC_DPML, LV_0, 1703), H2D(surflx, G_P, F_surflx, LV_0, 1718),
+  H2D(salflx, G_P, F_salflx, LV_0, 1721), H2D(surrlx, G_P, F_surrlx, LV_0, 1724), H2D(salrlx, G_P, F_salrlx, LV_0, 1727),
+  H2D(brnflx, G_P, F_brnflx, LV_0, 1730), H2D(brnpd, G_P, F_pbrnda, LV_0, 1733),
+  // ---- maxh2d, :1752 ----
+  {"maxbld", 0, G_P, OP_MAX, SRC_DPML, LV_0, W_NONE, A_NONE, 1752},
+  // ---- sqh2d, :1780-1786 ----
+  {"slvsq", 0, G_P, OP_SQ, F_z, LV_0, W_NONE, A_NONE, 1780}, {"ssssq", 0, G_P, OP_SQ, F_saln, LV_MM, W_NONE, A_NONE, 1783},
+  {"sstsq", 0, G_P, OP_SQ, F_temp, LV_MM, W_NONE, A_NONE, 1786},
+  // ---- acclyr, :1793-1913 (uvel = u(km) + ub(m), :1173-1186; vvel likewise) ----
+  {"uvel", 1, G_U, OP_SUM, F_u, LV_MM, W_DPU, A_UB, 1793}, LYR(dpu, G_U, F_dpu, LV_MM, W_NONE, 1796),
+  LYR(uflx, G_U, F_uflx, LV_NN, W_NONE, 1799), LYR(utflx, G_U, F_utflx, LV_NN, W_NONE, 1802), LYR(usflx, G_U, F_usflx, LV_NN, W_NONE, 1805),
+  LYR(umfltd, G_U, F_umfltd, LV_NN, W_NONE, 1808), LYR(umflsm, G_U, F_umflsm, LV_NN, W_NONE, 1811),
+  LYR(utfltd, G_U, F_utfltd, LV_NN, W_NONE, 1814), LYR(utflsm, G_U, F_utflsm, LV_NN, W_NONE, 1817),
+  LYR(utflld, G_U, F_utflld, LV_NN, W_NONE, 1820), LYR(usfltd, G_U, F_usfltd, LV_NN, W_NONE, 1823),
+  LYR(usflsm, G_U, F_usflsm, LV_NN, W_NONE, 1826), LYR(usflld, G_U, F_usflld, LV_NN, W_NONE, 1829),
+  {"vvel", 1, G_V, OP_SUM, F_v, LV_MM, W_DPV, A_VB, 1832}, LYR(dpv, G_V, F_dpv, LV_MM, W_NONE, 1835),
+  LYR(vflx, G_V, F_vflx, LV_NN, W_NONE, 1838), LYR(vtflx, G_V, F_vtflx, LV_NN, W_NONE, 1841), LYR(vsflx, G_V, F_vsflx, LV_NN, W_NONE, 1844),
+  LYR(vmfltd, G_V, F_vmfltd, LV_NN, W_NONE, 1847), LYR(vmflsm, G_V, F_vmflsm, LV_NN, W_NONE, 1850),
+  LYR(vtfltd, G_V, F_vtfltd, LV_NN, W_NONE, 1853), LYR(vtflsm, G_V, F_vtflsm, LV_NN, W_NONE, 1856),
+  LYR(vtflld, G_V, F_vtflld, LV_NN, W_NONE, 1859), LYR(vsfltd, G_V, F_vsfltd, LV_NN, W_NONE, 1862),
+  LYR(vsflsm, G_V, F_vsflsm, LV_NN, W_NONE, 1865), LYR(vsflld, G_V, F_vsflld, LV_NN, W_NONE, 1868),
+  LYR(saln, G_P, F_saln, LV_MM, W_DP, 1871), LYR(temp, G_P, F_temp, LV_MM, W_DP, 1874), LYR(dp, G_P, F_dp, LV_MM, W_NONE, 1877),
+  LYR(dz, G_P, F_dz, LV_0, W_NONE, 1880), LYR(bfsq, G_P, F_bfsql, LV_0, W_DP, 1883), LYR(difint, G_P, F_difint, LV_0, W_DP, 1886),
+  LYR(difiso, G_P, F_difiso, LV_0, W_DP, 1889), LYR(difdia, G_P, F_difdia, LV_0, W_DP, 1893),
+  LYR(tke, G_P, F_trc, LV_TKE, W_DP, 1909), LYR(gls_psi, G_P, F_trc, LV_GLS, W_DP, 1913),
+};
+#undef H2D
+#undef LYR
+constexpr int NROW = (int)(sizeof(g_rows) / sizeof(g_rows[0]));
+
+int find_row(const std::string &name) {
+  for (int r = 0; r < NROW; r++)
+    if (name == g_rows[r].name) return r;
+  return -1;
+}
+}  // namespace
+
+// the selection of a context (blomgpu_dia_select) and its accumulators
+struct DiaState {
+  std::vector<int> rows;        // the selected rows in the table's order: 2-D slots first, then the layer slots
+  std::vector<int> plane0;      // first plane of each slot in `acc`
+  size_t nplanes = 0;
+  double *acc = nullptr;
+  int nacc = 0;                 // nacc_phy, :1123-1125
+  bool needs_z = false;         // a selected row reads z or dz (cmnfld1's output)
+  int slot_of(int row) const {
+    for (size_t s = 0; s < rows.size(); s++)
+      if (rows[s] == row) return (int)s;
+    return -1;
+  }
+};
+
+// ---- the slot table a launch carries ------------------------------------------------------------------------------------------
+#define DIA_MAXSLOT 42         // the larger of the table's 2-D (42) and layer (36) row counts
+#ifndef DIA_U
+#define DIA_U 4                // slots whose loads are in flight together
+#endif
+// per slot: [0] source field, [1] source plane (of layer 1), [2] second plane's field, [3] its plane, [4] code, [5] first plane of the
+// slot in the allocation.  code = grid | op << 2 | weight << 4 | aux << 6 | source register << 9 (W_*: the source IS that weight)
+struct DiaTab {
+  int n, need;                 // need: bit 0 dp, 1 dpu, 2 dpv (km), 3 ub, 4 vb (m) are loaded
+  int lyr, mlev;               // 1: blockIdx.y is the layer; m - 1
+  int d[DIA_MAXSLOT][6];
+};
+
+__global__ __launch_bounds__(256) void k_diaacc(const DevView *__restrict__ Vp, double *__restrict__ accp, const DiaTab T, int mm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;          // owned points only: min(ii, il*) on the u-grid too (:5209)
+  const int msk = V.m[I_mpack][t] & 7;
+  if (!msk) return;
+  const int k = T.lyr ? (int)by : 0;
+  const size_t np = V.nplane, c = t, okm = c + (size_t)(mm + k) * np;
+  gd_t acc = global_ptr(accp);
+  // each weight and each shared source once per point
+  const double wdp = (T.need & 1) && (msk & 1) ? V.f[F_dp][okm] : 0.;
+  const double wdpu = (T.need & 2) && (msk & 2) ? V.f[F_dpu][okm] : 0.;
+  const double wdpv = (T.need & 4) && (msk & 4) ? V.f[F_dpv][okm] : 0.;
+  const double sub = (T.need & 8) && (msk & 2) ? V.f[F_ub][c + (size_t)T.mlev * np] : 0.;
+  const double svb = (T.need & 16) && (msk & 4) ? V.f[F_vb][c + (size_t)T.mlev * np] : 0.;
+  for (int s0 = 0; s0 < T.n; s0 += DIA_U) {                     // wave-uniform
+    double a[DIA_U], v[DIA_U], x[DIA_U];
+    size_t oa[DIA_U];
+    bool on[DIA_U];
+#pragma unroll
+    for (int u = 0; u < DIA_U; u++) {
+      const int s = s0 + u < T.n ? s0 + u : T.n - 1;             // (uniform; the table is read inside its bounds)
+      const int code = T.d[s][4];
+      on[u] = s0 + u < T.n && ((msk >> (code & 3)) & 1);
+      oa[u] = c + ((size_t)T.d[s][5] + k) * np;
+      a[u] = v[u] = x[u] = 0.;
+      if (on[u]) {
+        a[u] = acc[oa[u]];
+        if (!((code >> 9) & 3)) v[u] = V.f[T.d[s][0]][c + ((size_t)T.d[s][1] + k) * np];
+        if (((code >> 6) & 7) == A_PLANE) x[u] = V.f[T.d[s][2]][c + (size_t)T.d[s][3] * np];
+      }
+    }
+    // (selects on wave-uniform codes, no branches: the group's arithmetic is straight-line code between its loads and its stores)
+    double r[DIA_U];
+#pragma unroll
+    for (int u = 0; u < DIA_U; u++) {
+      const int s = s0 + u < T.n ? s0 + u : T.n - 1, code = T.d[s][4];
+      const int op = (code >> 2) & 3, wg = (code >> 4) & 3, aux = (code >> 6) & 7, sr = (code >> 9) & 3;
+      double f = sr == W_DP ? wdp : sr == W_DPU ? wdpu : sr == W_DPV ? wdpv : v[u];
+      // fld = u(km) + ub(m) (:1180) | v(km) + vb(m) (:1195) | dp(1+mm) + dp(2+mm) (:1155) | OBLdepth*onem (:1165)
+      f = aux == A_UB ? f + sub : aux == A_VB ? f + svb : aux == A_PLANE ? f + x[u] : aux == A_ONEM ? f * ONEM : f;
+      const double w = wg == W_DP ? wdp : wg == W_DPU ? wdpu : wdpv;
+      // acc + fld*fld (:5454) | acc + fld*wghts (:5266, :5513) | acc + fld (:5256, :5500) | max(acc, fld) (:5330) as amdflang lowers it
+      const double add = op == OP_SQ ? f * f : wg ? f * w : f;
+      r[u] = op == OP_MAX ? fmax2(a[u], f) : a[u] + add;
+    }
+#pragma unroll
+    for (int u = 0; u < DIA_U; u++)
+      if (on[u]) acc[oa[u]] = r[u];
+  }
+}
+
+// inih2d / inilyr (:5001-5113): inival*mask over the WHOLE padded plane (so land is -0.0 under maxbld's -spval)
+struct DiaIni { int n; int d[2 * DIA_MAXSLOT][3]; };            // per slot: first plane, levels, grid | is_max << 2
+__global__ __launch_bounds__(256) void k_dia_init(const DevView *__restrict__ Vp, double *__restrict__ accp, const DiaIni T) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, k = by;
+  if (t >= V.nplane) return;
+  const int msk = V.m[I_mpack][t];
+  gd_t acc = global_ptr(accp);
+  for (int s = 0; s < T.n; s++) {
+    if (k >= T.d[s][1]) continue;
+    const double inival = (T.d[s][2] >> 2) ? -SPVAL : 0.;
+    acc[(size_t)t + ((size_t)T.d[s][0] + k) * V.nplane] = inival * (double)((msk >> (T.d[s][2] & 3)) & 1);
+  }
+}
+
+// finlyr (:6114-6185) in place: acc / wgt where wgt > epsil, else nf90_fill_double; one (slot, weight slot) pair per launch
+__global__ __launch_bounds__(256) void k_dia_finlyr(const DevView *__restrict__ Vp, double *__restrict__ accp, int pa, int pw, int grid) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, k = by;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj || !((V.m[I_mpack][t] >> grid) & 1)) return;
+  gd_t acc = global_ptr(accp);
+  const size_t oa = (size_t)t + ((size_t)pa + k) * V.nplane, ow = (size_t)t + ((size_t)pw + k) * V.nplane;
+  const double w = acc[ow], a = acc[oa];
+  acc[oa] = w > EPSIL ? a / w : NF90_FILL_DOUBLE;
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+static int dia_init(blomgpu_ctx *c, DiaState *S) {
+  DiaIni T;
+  T.n = 0;
+  int maxlev = 1;
+  for (size_t s = 0; s < S->rows.size(); s++) {
+    const DiaRow &r = g_rows[S->rows[s]];
+    const int nl = r.lyr ? c->h.kk : 1;
+    T.d[T.n][0] = S->plane0[s]; T.d[T.n][1] = nl; T.d[T.n][2] = r.grid | (r.op == OP_MAX) << 2;
+    T.n++;
+    if (nl > maxlev) maxlev = nl;
+  }
+  S->nacc = 0;
+  if (!T.n) return 0;
+  ctx_sync_view(c);
+  hipLaunchKernelGGL(k_dia_init, plane_grid(c->h, maxlev), dim3(256), 0, c->stream, c->d, S->acc, T);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+void dia_free(blomgpu_ctx *c) {
+  if (!c->dia) return;
+  (void)hipStreamSynchronize(c->stream);
+  if (c->dia->acc) (void)hipFree(c->dia->acc);
+  delete c->dia;
+  c->dia = nullptr;
+}
+
+bool dia_active(const blomgpu_ctx *c) { return c->dia != nullptr; }
+void dia_count(blomgpu_ctx *c) { if (c->dia) c->dia->nacc++; }
+
+// z and dz are cmnfld1's: a step that does not run it would accumulate whatever the arrays hold
+int dia_step_check(blomgpu_ctx *c) {
+  if (!c->dia || !c->dia->needs_z) return 0;
+  if (c->h.P.vcoord_tag != 1 || c->cmnfld1 || c->full_physics) return 0;
+  std::string names;
+  for (int r : c->dia->rows)
+    if (g_rows[r].src == F_z || g_rows[r].src == F_dz) names += std::string(names.empty() ? "" : " ") + g_rows[r].name;
+  return ctx_fail(c, "blomgpu_step: the selected accumulators " + names + " read z / dz, which this step sequence does not compute (set cmnfld1 = 1 or full_physics = 1)");
+}
+
+int dia_select(blomgpu_ctx *c, const char *names) {
+  if (!names) return ctx_fail(c, "blomgpu_dia_select: null argument");
+  std::vector<char> want(NROW, 0);
+  const std::string all(names);
+  size_t pos = 0;
+  bool any = false;
+  while (pos < all.size()) {
+    while (pos < all.size() && (all[pos] == ' ' || all[pos] == ',' || all[pos] == '\t' || all[pos] == '\n')) pos++;
+    size_t end = pos;
+    while (end < all.size() && !(all[end] == ' ' || all[end] == ',' || all[end] == '\t' || all[end] == '\n')) end++;
+    if (end == pos) break;
+    const std::string nm = all.substr(pos, end - pos);
+    pos = end;
+    const int r = find_row(nm);
+    if (r < 0) return ctx_fail(c, "blomgpu_dia_select: unknown accumulator " + nm);
+    if (g_rows[r].lev == LV_TKE && c->h.P.itrtke < 1)
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the TKE tracers (itrtke >= 1, phy/mod_dia.F90:1907)");
+    if (g_rows[r].lev == LV_GLS && !(c->h.P.itrtke >= 1 && c->h.P.gls && c->h.P.itrgls >= 1))
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the two-equation closure (itrtke >= 1, gls = 1)");
+    if ((g_rows[r].lev == LV_TKE || g_rows[r].lev == LV_GLS) && (c->h.P.itrtke > c->h.ntr || c->h.P.itrgls > c->h.ntr))
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + ": itrtke / itrgls outside 1..ntr");
+    want[r] = 1;
+    any = true;
+  }
+  // diaini's dependencies (:598-608): a dp-weighted row needs dp, uvel needs dpu, vvel needs dpv
+  for (int r = 0; r < NROW; r++)
+    if (want[r] && g_rows[r].wgt) want[find_row(g_rows[r].wgt == W_DP ? "dp" : g_rows[r].wgt == W_DPU ? "dpu" : "dpv")] = 1;
+  DiaState *S = nullptr;
+  if (any) {
+    S = new DiaState;
+    int n2d = 0, nly = 0;
+    for (int pass = 0; pass < 2; pass++)
+      for (int r = 0; r < NROW; r++)
+        if (want[r] && g_rows[r].lyr == pass) {
+          S->rows.push_back(r);
+          S->plane0.push_back((int)S->nplanes);
+          S->nplanes += pass ? c->h.kk : 1;
+          (pass ? nly : n2d)++;
+          if (g_rows[r].src == F_z || g_rows[r].src == F_dz) S->needs_z = true;
+        }
+    if (n2d > DIA_MAXSLOT || nly > DIA_MAXSLOT) { delete S; return ctx_fail(c, "blomgpu_dia_select: more slots than a launch carries"); }
+    (void)hipSetDevice(c->device);
+    if (hipMalloc((void **)&S->acc, sizeof(double) * S->nplanes * (size_t)c->h.nplane) != hipSuccess) {
+      (void)hipGetLastError();
+      const size_t mb = sizeof(double) * S->nplanes * (size_t)c->h.nplane >> 20;
+      delete S;
+      return ctx_fail(c, "blomgpu_dia_select: no device memory for " + std::to_string(mb) + " MB of accumulators");
+    }
+    if (dia_init(c, S)) { (void)hipFree(S->acc); delete S; return 1; }
+  }
+  dia_free(c);                       // the previous selection goes only now that the new one stands
+  c->dia = S;
+  ctx_drop_graphs(c);
+  return 0;
+}
+
+int dia_reset(blomgpu_ctx *c) { return c->dia ? dia_init(c, c->dia) : 0; }       // inifld, :5864
+
+int dia_nacc(blomgpu_ctx *c, int *nacc) {
+  if (!nacc) return ctx_fail(c, "blomgpu_dia_nacc: null argument");
+  *nacc = c->dia ? c->dia->nacc : 0;
+  return 0;
+}
+
+int dia_get(blomgpu_ctx *c, const char *name, double *out) {
+  if (!name || !out) return ctx_fail(c, "blomgpu_dia_get: null argument");
+  const int r = find_row(name), s = r >= 0 && c->dia ? c->dia->slot_of(r) : -1;
+  if (r < 0) return ctx_fail(c, std::string("blomgpu_dia_get: unknown accumulator ") + name);
+  if (s < 0) return ctx_fail(c, std::string("blomgpu_dia_get: accumulator ") + name + " is not selected");
+  const size_t np = c->h.nplane, nl = g_rows[r].lyr ? c->h.kk : 1;
+  HIPCHK(c, hipMemcpyAsync(out, c->dia->acc + (size_t)c->dia->plane0[s] * np, sizeof(double) * nl * np, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return 0;
+}
+
+int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) {
+  if (index < 0 || index >= NROW || !buf || cap < 2) return 1;
+  snprintf(buf, cap, "%s", g_rows[index].name);
+  if (is_lyr) *is_lyr = g_rows[index].lyr;
+  if (grid) *grid = g_rows[index].grid;
+  return 0;
+}
+
+// finlyr for the weighted layer pairs of :2597-2611; the table holds no weighted 2-D row (finh2d's are the ice fields, :2591-2594)
+int dia_finalize(blomgpu_ctx *c) {
+  DiaState *S = c->dia;
+  if (!S) return 0;
+  ctx_sync_view(c);
+  for (size_t s = 0; s < S->rows.size(); s++) {
+    const DiaRow &r = g_rows[S->rows[s]];
+    if (!r.lyr || !r.wgt) continue;
+    const int ws = S->slot_of(find_row(r.wgt == W_DP ? "dp" : r.wgt == W_DPU ? "dpu" : "dpv"));
+    hipLaunchKernelGGL(k_dia_finlyr, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, S->acc, S->plane0[s], S->plane0[ws], r.grid);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// the accumulation of one step (without the count: blomgpu_diaacc and blomgpu_step add it, a graph capture must not)
+int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
+  (void)k1m; (void)k1n;
+  DiaState *S = c->dia;
+  if (!S) return 0;
+  const DevView &h = c->h;
+  for (int pass = 1; pass >= 0; pass--) {
+    DiaTab T;
+    T.n = 0; T.need = 0; T.lyr = pass; T.mlev = m - 1;
+    for (size_t s = 0; s < S->rows.size(); s++) {
+      const DiaRow &r = g_rows[S->rows[s]];
+      if (r.lyr != pass) continue;
+      int src = r.src, aux = r.aux, f2 = 0, l2 = 0, lev = 0, sreg = 0;
+      switch (r.lev) {
+        case LV_0: lev = 0; break;
+        case LV_M: lev = m - 1; break;
+        case LV_N: lev = n - 1; break;
+        case LV_KK: lev = h.kk; break;
+        case LV_MM: lev = mm; break;
+        case LV_NN: lev = nn; break;
+        case LV_TKE: lev = (h.P.itrtke - 1) * 2 * h.kk + mm; break;       // trc(:,:,k1m,itrtke)
+        case LV_GLS: lev = (h.P.itrgls - 1) * 2 * h.kk + mm; break;
+      }
+      if (src == SRC_DPML) {
+        if (h.P.vcoord_tag == 1) { src = F_dp; lev = mm; aux = A_PLANE; f2 = F_dp; l2 = mm + 1; }      // :1155
+        else { src = F_OBLdepth; lev = 0; aux = A_ONEM; }                                              // :1165
+      }
+      if (pass && lev == mm && (src == F_dp || src == F_dpu || src == F_dpv)) sreg = src == F_dp ? W_DP : src == F_dpu ? W_DPU : W_DPV;
+      if (r.wgt) T.need |= 1 << (r.wgt - 1);
+      if (sreg) T.need |= 1 << (sreg - 1);
+      if (aux == A_UB) T.need |= 8;
+      if (aux == A_VB) T.need |= 16;
+      int *d = T.d[T.n++];
+      d[0] = src; d[1] = lev; d[2] = f2; d[3] = l2;
+      d[4] = r.grid | r.op << 2 | r.wgt << 4 | aux << 6 | sreg << 9;
+      d[5] = S->plane0[s];
+    }
+    if (!T.n) continue;
+    TimeScope ts(c, pass ? "diaacc_lyr" : "diaacc_h2d");
+    hipLaunchKernelGGL(k_diaacc, plane_grid(h, pass ? h.kk : 1), dim3(256), 0, c->stream, c->d, S->acc, T, mm);
+  }
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}

@@ -278,6 +278,7 @@ contains
       call pbcor2(m,n,mm,nn,k1m,k1n)
       call tmsmt2(m,mm,nn,k1m)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
+      call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
       call gpu_set('delt1', baclin+baclin)
       return
     end if
@@ -304,6 +305,7 @@ contains
       call pbcor2(m,n,mm,nn,k1m,k1n)
       call tmsmt2(m,mm,nn,k1m)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
+      call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
       call gpu_set('delt1', baclin+baclin)
       return
     end if
@@ -325,6 +327,7 @@ contains
     call barotp(m,n,mm,nn,k1m,k1n)
     call pbcor2(m,n,mm,nn,k1m,k1n)
     call tmsmt2(m,mm,nn,k1m)
+    call diaacc(m,n,mm,nn,k1m,k1n)                 ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
     call gpu_set('delt1', baclin+baclin)           ! phy/mod_blom_step.F90:300
   end subroutine blom_step
 

@@ -81,6 +81,30 @@ module mod_blomgpu
       type(*) :: host(*)
       integer(c_int), value :: nlev
     end function
+    integer(c_int) function blomgpu_dia_select(c, names) bind(C, name='blomgpu_dia_select')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: names(*)
+    end function
+    integer(c_int) function blomgpu_dia_get(c, name, host) bind(C, name='blomgpu_dia_get')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: name(*)
+      type(*) :: host(*)
+    end function
+    integer(c_int) function blomgpu_dia_nacc(c, nacc) bind(C, name='blomgpu_dia_nacc')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), intent(out) :: nacc
+    end function
+    integer(c_int) function blomgpu_dia_finalize(c) bind(C, name='blomgpu_dia_finalize')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_dia_reset(c) bind(C, name='blomgpu_dia_reset')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
     integer(c_int) function blomgpu_field_info(c, name, nlev, isint) bind(C, name='blomgpu_field_info')
       import :: c_ptr, c_int, c_char
       type(c_ptr), value :: c
@@ -194,7 +218,8 @@ module mod_blomgpu
   public :: init_fluxes, tmsmt1, tmsmt2, advect, pbcor1, pbcor2, diffus, pgforc, momtum, &
             diapfl, barotp, eddtra, convec, sfcstr, updtrc, init_cppm, halo_cmnfld2, halo_difest, mxlayr_tail, &
             cmnfld1, cmnfld2, ale_regrid_remap, ale_vdifft, ale_vdiffm, ale_forcing, &
-            cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr
+            cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc
+  public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc
 
   interface gpu_set
     module procedure gpu_set_real, gpu_set_int, gpu_set_str
@@ -497,6 +522,36 @@ contains
     integer, intent(in) :: m,n,mm,nn,k1m,k1n
     call stage6('cmnfld1',m,n,mm,nn,k1m,k1n)
   end subroutine cmnfld1
+  ! diaacc (phy/mod_dia.F90:1092, called at phy/mod_blom_step.F90:239): the accumulators selected with gpu_dia_select; without a
+  ! selection it does nothing
+  subroutine diaacc(m,n,mm,nn,k1m,k1n)
+    integer, intent(in) :: m,n,mm,nn,k1m,k1n
+    call stage6('diaacc',m,n,mm,nn,k1m,k1n)
+  end subroutine diaacc
+  ! the selection: a blank-separated list of the reference's ACC_* suffixes in lower case ('temp saln uvel sealv'), '' for none;
+  ! replaces the previous one, adds diaini's dependencies (phy/mod_dia.F90:598-608), initialises as inifld does
+  subroutine gpu_dia_select(names)
+    character(len=*), intent(in) :: names
+    call gpu_check(blomgpu_dia_select(ctx, cz(names)), 'gpu_dia_select')
+  end subroutine
+  ! the accumulator on the tile's padded plane(s): nlev = 1 for a 2-D name, kdm for a layer name (phyh2d / phylyr of the reference)
+  subroutine gpu_dia_get(name, a, nlev)
+    character(len=*), intent(in) :: name
+    integer, intent(in) :: nlev
+    real(8), intent(out) :: a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,nlev)
+    call gpu_check(blomgpu_dia_get(ctx, cz(name), a), 'gpu_dia_get')
+  end subroutine
+  subroutine gpu_dia_finalize()                 ! finlyr for the weighted layer pairs, phy/mod_dia.F90:2597-2611
+    call gpu_check(blomgpu_dia_finalize(ctx), 'gpu_dia_finalize')
+  end subroutine
+  subroutine gpu_dia_reset()                    ! inifld, phy/mod_dia.F90:5864
+    call gpu_check(blomgpu_dia_reset(ctx), 'gpu_dia_reset')
+  end subroutine
+  integer function gpu_dia_nacc()               ! nacc_phy
+    integer(c_int) :: v
+    call gpu_check(blomgpu_dia_nacc(ctx, v), 'gpu_dia_nacc')
+    gpu_dia_nacc = v
+  end function
   subroutine cmnfld2(m,n,mm,nn,k1m,k1n)         ! phy/mod_cmnfld_routines.F90:1158 (halo updates, bfsqf, neutral slopes)
     integer, intent(in) :: m,n,mm,nn,k1m,k1n
     call stage6('cmnfld2',m,n,mm,nn,k1m,k1n)

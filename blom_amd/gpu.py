@@ -210,6 +210,46 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_budget_get(self.ctx, {"sdp": 0, "tdp": 1, "trdp": 2, "tkedp": 3}[which], ncall, n, C.byref(v)))
         return v.value
 
+    # -- time-mean diagnostics (diaacc, phy/mod_dia.F90) -------------------------------------
+    def dia_names(self):
+        """the accumulator table: [(name, is_layer, grid)] with grid one of "p", "u", "v" """
+        rows, buf, k = [], C.create_string_buffer(32), 0
+        lyr, grid = C.c_int(0), C.c_int(0)
+        while self.lib.blomgpu_dia_name(k, buf, 32, C.byref(lyr), C.byref(grid)) == 0:
+            rows.append((buf.value.decode(), bool(lyr.value), "puv"[grid.value]))
+            k += 1
+        return rows
+
+    def dia_select(self, names):
+        """replace the selection (a blank-separated string or a list of names; empty: none) -- blomgpu_dia_select"""
+        if not isinstance(names, str):
+            names = " ".join(names)
+        self._chk(self.lib.blomgpu_dia_select(self.ctx, names.encode()))
+
+    def diaacc(self, m, n, mm, nn, k1m, k1n):
+        self._chk(self.lib.blomgpu_diaacc(self.ctx, m, n, mm, nn, k1m, k1n))
+
+    def dia_nacc(self):
+        v = C.c_int(0)
+        self._chk(self.lib.blomgpu_dia_nacc(self.ctx, C.byref(v)))
+        return v.value
+
+    def dia_get(self, name):
+        """the accumulator as get() would return a field: (1 | kdm, nj, ni)"""
+        if not hasattr(self, "_dia_lyr"):
+            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names()}
+        if name not in self._dia_lyr:
+            raise KeyError(name)
+        a = np.empty((self.kdm if self._dia_lyr[name] else 1, self.nj, self.ni), dtype=np.float64)
+        self._chk(self.lib.blomgpu_dia_get(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p)))
+        return a
+
+    def dia_finalize(self):
+        self._chk(self.lib.blomgpu_dia_finalize(self.ctx))
+
+    def dia_reset(self):
+        self._chk(self.lib.blomgpu_dia_reset(self.ctx))
+
     # -- tile decomposition ---------------------------------------------------------------
     def rccl_init(self, id128, rank, nranks):
         buf = (C.c_char * 128).from_buffer_copy(bytes(id128))

@@ -32,6 +32,11 @@ FULL_STAGES = FULL_STAGES[:FULL_STAGES.index("diapfl") + 1] + ("thermf", "mxlayr
 # option difest_live): the whole routine in place of its front part
 FULL_STAGES_LIVE = tuple("difest_isobml" if s == "difest_isobml_pre" else s for s in FULL_STAGES)
 
+# diaacc (phy/mod_blom_step.F90:239): the time-mean diagnostics of the accumulators selected with BlomGpu.dia_select.  Part of no
+# list above: a host that steps stage by stage appends it (stages=FULL_STAGES + DIAG_STAGES); BlomGpu.step runs it by itself
+# whenever a selection exists.
+DIAG_STAGES = ("diaacc",)
+
 STAGES_FROZEN_EDDY_FLUXES = tuple(s for s in DYNCORE_STAGES if s != "eddtra")    # umfltd.. stay as uploaded
 
 # The step of the other vertical coordinates (vcoord_type = 'cntiso_hybrid' or 'plevel'), phy/mod_blom_step.F90:126-233, as far

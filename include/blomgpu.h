@@ -193,6 +193,35 @@ int  blomgpu_ale_vdiffm(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, in
  * (phy/mod_vcoord.F90:99, :948-970) */
 int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv);
 
+/* Time-mean diagnostics accumulated on the device: diaacc of phy/mod_dia.F90:1092 (phy/mod_blom_step.F90:239) for the accumulators
+ * that read arrays the device holds -- acch2d (:1547-1745, :5182), maxh2d (:1752, :5285), sqh2d (:1780-1786, :5409), acclyr
+ * (:1793-1913, :5471) -- one output group.  A name is the reference's ACC_* suffix in lower case: "ub", "sealv", "maxbld", "uvel",
+ * "temp" ... (the table: blom_amd/csrc/stage_diaacc.hip, enumerated by blomgpu_dia_name; what is left out: DESIGN.md 7).
+ * Writing files, z-level interpolation and the scaling by 1/nacc (wrth2d, wrtlyr) stay on the host.
+ *
+ * blomgpu_dia_select: `names` is a blank-separated list that REPLACES the selection; "" deselects everything and frees the
+ *   accumulators.  Adds diaini's dependencies (:598-608: a dp-weighted name selects "dp", "uvel" selects "dpu", "vvel" "dpv"),
+ *   allocates one array [slot][level][padded plane], initialises it as inih2d / inilyr do (:5001-5113: inival*mask over the whole
+ *   padded plane; inival = -1e33 for "maxbld", 0 otherwise) and sets nacc = 0.  An unknown name, or "tke" / "gls_psi" without
+ *   itrtke >= 1 / gls (:1907), fails with a message that names it and leaves the previous selection and its contents in force.
+ * blomgpu_diaacc: the stage (also blomgpu_stage "diaacc"): nacc = nacc + 1 (:1123-1125), then the accumulation at the owned points
+ *   of each accumulator's grid.  Without a selection it does nothing.  With one, blomgpu_step runs it at the end of every step
+ *   (after cmnfld1); "sealv", "slvsq", "dz" read cmnfld1's z / dz, and a step whose sequence does not run cmnfld1 refuses them.
+ * blomgpu_dia_nacc: the number of accumulated steps (nacc_phy).
+ * blomgpu_dia_get: the accumulator's padded plane (2-D names) or kdm planes (layer names), laid out as blomgpu_download's.
+ * blomgpu_dia_finalize: finlyr (:6114-6185) in place for the weighted layer pairs of :2597-2611 -- acc/wgt where wgt > 1e-11, else
+ *   nf90_fill_double = 9.9692099683868690e+36.  (finh2d, :6054: the table has no weighted 2-D row.)
+ * blomgpu_dia_reset: inifld (:5864) for the selection: re-initialises and sets nacc = 0.
+ * blomgpu_dia_name: row `index` of the table (0, 1, ... until the return value is non-zero); is_lyr 0 = 2-D, 1 = kdm layers;
+ *   grid 0 p, 1 u, 2 v. */
+int  blomgpu_dia_select(blomgpu_ctx *, const char *names);
+int  blomgpu_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
+int  blomgpu_dia_nacc(blomgpu_ctx *, int *nacc);
+int  blomgpu_dia_get(blomgpu_ctx *, const char *name, double *out);
+int  blomgpu_dia_finalize(blomgpu_ctx *);
+int  blomgpu_dia_reset(blomgpu_ctx *);
+int  blomgpu_dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
+
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
                    int k1m, int k1n);
