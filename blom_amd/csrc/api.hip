@@ -638,6 +638,9 @@ int blomgpu_dia_get(blomgpu_ctx *c, const char *name, double *out) { return dia_
 int blomgpu_dia_finalize(blomgpu_ctx *c) { return dia_finalize(c); }
 int blomgpu_dia_reset(blomgpu_ctx *c) { return dia_reset(c); }
 int blomgpu_dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) { return dia_name(index, buf, cap, is_lyr, grid); }
+int blomgpu_dia_set_levels(blomgpu_ctx *c, const double *bnds, int ddm) { return dia_set_levels(c, bnds, ddm); }
+int blomgpu_dia_levels_levitus2x(blomgpu_ctx *c) { return dia_levels_levitus2x(c); }
+int blomgpu_dia_get_levels(blomgpu_ctx *c, double *bnds, int cap, int *ddm) { return dia_get_levels(c, bnds, cap, ddm); }
 // sfcstr, phy/mod_sfcstr.F90:33-62: the surface stress of the idealised experiments is set at initialisation
 // (or absent), so the stage is empty for them; the coupled/reanalysis branches live in modules that are
 // not part of this path.

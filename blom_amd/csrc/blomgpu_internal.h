@@ -454,6 +454,7 @@ struct blomgpu_ctx {
   double *xcsum_buf = nullptr;                 // [0] the sum, [1..jj] the row sums of xcsum
   double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
   DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
+  std::vector<double> dia_edges;               // blomgpu_dia_set_levels: the ddm + 1 edges of the depth levels; empty: the 35-level table
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space
@@ -546,6 +547,9 @@ int dia_finalize(blomgpu_ctx *);
 int dia_nacc(blomgpu_ctx *, int *nacc);
 int dia_get(blomgpu_ctx *, const char *name, double *out);
 int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
+int dia_set_levels(blomgpu_ctx *, const double *bnds, int ddm);
+int dia_levels_levitus2x(blomgpu_ctx *);
+int dia_get_levels(blomgpu_ctx *, double *bnds, int cap, int *ddm);
 int dia_step_check(blomgpu_ctx *);           // a selection that reads z / dz in a sequence without cmnfld1: fails
 bool dia_active(const blomgpu_ctx *);
 void dia_count(blomgpu_ctx *);

@@ -11,13 +11,16 @@
 // and then walks the slot table -- a table of ints in the kernel arguments, fetched with scalar loads in a
 // wave-uniform loop -- DIA_U slots at a time: all loads of the group are issued before its stores.
 // Algorithmic bytes per launch: (2 n_acc + n_distinct_sources) F.
+//
+// The z-level (Levitus) accumulators -- diazlv (:4737-4993) + acclvl (:5709-5781), called per layer from diaacc (:2000-2053,
+// :2119-2168, :2222-2271) -- are k_dialvl further down: one thread per column of a grid, one launch per grid with a selected name.
 #include "../../include/blomgpu.h"
 #include "blomgpu_internal.h"
 #include <cstring>
 
 namespace {
 enum { G_P = 0, G_U = 1, G_V = 2 };                 // the grid = the bit of mpack that masks it
-enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2 };
+enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4 };   // the last two: acclvl with diazlv's weights | weightsflx
 enum { W_NONE = 0, W_DP = 1, W_DPU = 2, W_DPV = 3 };       // weight (km); also: the register a source is taken from
 enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src + ub(m) | src + vb(m) | src + a second plane | src*onem
 // the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
@@ -26,11 +29,15 @@ enum { SRC_DPML = -1 };                             // dpml as :1148-1171 forms 
 constexpr double ONEM = 9806.;                      // phy/mod_constants.F90
 constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948)
 constexpr double EPSIL = 1.e-11, NF90_FILL_DOUBLE = 9.9692099683868690e+36;   // finlyr, :6126, :6140
+constexpr double EPSILP = 1.e-12;                   // phy/mod_constants.F90:43
+constexpr double DZEPS = 1e1 * EPSILP, DPEPS = 1e5 * EPSILP, FLXEPS = 1e5 * EPSILP;   // diazlv, :4760-4762
 
 // One row per accumulator; the name is the reference's ACC_* suffix in lower case, `line` the call in phy/mod_dia.F90.
-struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; };
+struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; };   // lyr: 0 2-D, 1 kk layers, 2 ddm depth levels
 #define H2D(nm, g, f, lv, ln) {#nm, 0, g, OP_SUM, f, lv, W_NONE, A_NONE, ln}
 #define LYR(nm, g, f, lv, w, ln) {#nm, 1, g, OP_SUM, f, lv, w, A_NONE, ln}
+#define LVF(nm, g, f, ln) {#nm, 2, g, OP_LVLFLX, f, LV_NN, W_NONE, A_NONE, ln}
+#define LVP(nm, f, lv, ln) {#nm, 2, G_P, OP_LVL, f, lv, W_NONE, A_NONE, ln}
 const DiaRow g_rows[] = {
   // ---- acch2d, :1547-1745 ----
   H2D(ub, G_U, F_ub, LV_M, 1547), H2D(ubflxs, G_U, F_ubflxs, LV_N, 1550), H2D(taux, G_U, F_taux, LV_0, 1556),
@@ -68,10 +75,35 @@ const DiaRow g_rows[] = {
   LYR(dz, G_P, F_dz, LV_0, W_NONE, 1880), LYR(bfsq, G_P, F_bfsql, LV_0, W_DP, 1883), LYR(difint, G_P, F_difint, LV_0, W_DP, 1886),
   LYR(difiso, G_P, F_difiso, LV_0, W_DP, 1889), LYR(difdia, G_P, F_difdia, LV_0, W_DP, 1893),
   LYR(tke, G_P, F_trc, LV_TKE, W_DP, 1909), LYR(gls_psi, G_P, F_trc, LV_GLS, W_DP, 1913),
+  // ---- acclvl on the u-grid, :2010-2054 (isopyc_bulkml; :1955-1996 otherwise, without uvellvl) ----
+  {"uvellvl", 2, G_U, OP_LVL, F_u, LV_MM, W_NONE, A_UB, 2010}, LVF(uflxlvl, G_U, F_uflx, 2013), LVF(utflxlvl, G_U, F_utflx, 2017),
+  LVF(usflxlvl, G_U, F_usflx, 2021), LVF(umfltdlvl, G_U, F_umfltd, 2025), LVF(umflsmlvl, G_U, F_umflsm, 2029),
+  LVF(utfltdlvl, G_U, F_utfltd, 2033), LVF(utflsmlvl, G_U, F_utflsm, 2037), LVF(utflldlvl, G_U, F_utflld, 2041),
+  LVF(usfltdlvl, G_U, F_usfltd, 2045), LVF(usflsmlvl, G_U, F_usflsm, 2049), LVF(usflldlvl, G_U, F_usflld, 2053),
+  // ---- the v-grid, :2125-2169 (:2070-2111 otherwise, without vvellvl) ----
+  {"vvellvl", 2, G_V, OP_LVL, F_v, LV_MM, W_NONE, A_VB, 2125}, LVF(vflxlvl, G_V, F_vflx, 2128), LVF(vtflxlvl, G_V, F_vtflx, 2132),
+  LVF(vsflxlvl, G_V, F_vsflx, 2136), LVF(vmfltdlvl, G_V, F_vmfltd, 2140), LVF(vmflsmlvl, G_V, F_vmflsm, 2144),
+  LVF(vtfltdlvl, G_V, F_vtfltd, 2148), LVF(vtflsmlvl, G_V, F_vtflsm, 2152), LVF(vtflldlvl, G_V, F_vtflld, 2156),
+  LVF(vsfltdlvl, G_V, F_vsfltd, 2160), LVF(vsflsmlvl, G_V, F_vsflsm, 2164), LVF(vsflldlvl, G_V, F_vsflld, 2168),
+  // ---- the p-grid, :2233-2271 (:2185-2217 otherwise, without salnlvl and templvl) ----
+  LVP(salnlvl, F_saln, LV_MM, 2233), LVP(templvl, F_temp, LV_MM, 2236), LVP(bfsqlvl, F_bfsql, LV_0, 2239),
+  LVP(difintlvl, F_difint, LV_0, 2242), LVP(difisolvl, F_difiso, LV_0, 2245), LVP(difdialvl, F_difdia, LV_0, 2248),
+  LVP(tkelvl, F_trc, LV_TKE, 2264), LVP(gls_psilvl, F_trc, LV_GLS, 2267), LVP(dzlvl, F_dz, LV_0, 2271),
 };
 #undef H2D
 #undef LYR
+#undef LVF
+#undef LVP
 constexpr int NROW = (int)(sizeof(g_rows) / sizeof(g_rows[0]));
+
+// depthslev_bnds as its ddm + 1 edges: bnds(1,d) = edge[d-1], bnds(2,d) = edge[d] (:119-128; with LEVITUS2X :142-159)
+const double g_edges35[] = {0., 5., 15., 25., 40., 62.5, 87.5, 112.5, 137.5, 175., 225., 275., 350., 450., 550., 650., 750., 850., 950., 1050.,
+  1150., 1250., 1350., 1450., 1625., 1875., 2250., 2750., 3250., 3750., 4250., 4750., 5250., 5750., 6250., 8000.};
+const double g_edges70[] = {0., 2.5, 7.5, 12.5, 17.5, 22.5, 27.5, 35., 45., 56.2, 68.8, 81.2, 93.8, 106.2, 118.8, 131.2, 143.8, 162.5, 187.5,
+  212.5, 237.5, 262.5, 287.5, 325., 375., 425., 475., 525., 575., 625., 675., 725., 775., 825., 875., 925., 975., 1025., 1075., 1125.,
+  1175., 1225., 1275., 1325., 1375., 1425., 1475., 1562.5, 1687.5, 1812.5, 1937.5, 2125., 2375., 2625., 2875., 3125., 3375., 3625.,
+  3875., 4125., 4375., 4625., 4875., 5125., 5375., 5625., 5875., 6125., 6375., 6625., 8000.};
+static_assert(sizeof(g_edges35) == 36 * sizeof(double) && sizeof(g_edges70) == 71 * sizeof(double), "ddm = 35 | 70");
 
 int find_row(const std::string &name) {
   for (int r = 0; r < NROW; r++)
@@ -88,6 +120,9 @@ struct DiaState {
   double *acc = nullptr;
   int nacc = 0;                 // nacc_phy, :1123-1125
   bool needs_z = false;         // a selected row reads z or dz (cmnfld1's output)
+  int ddm = 0;                  // levels of a depth-level slot; 0: none selected.  Their ddm + 1 edges lie behind the last plane of `acc`
+  double *edges() const { return acc + nplanes * np; }
+  size_t np = 0;
   int slot_of(int row) const {
     for (size_t s = 0; s < rows.size(); s++)
       if (rows[s] == row) return (int)s;
@@ -165,7 +200,7 @@ __global__ __launch_bounds__(256) void k_diaacc(const DevView *__restrict__ Vp, 
 }
 
 // inih2d / inilyr (:5001-5113): inival*mask over the WHOLE padded plane (so land is -0.0 under maxbld's -spval)
-struct DiaIni { int n; int d[2 * DIA_MAXSLOT][3]; };            // per slot: first plane, levels, grid | is_max << 2
+struct DiaIni { int n; int d[3 * DIA_MAXSLOT][3]; };            // per slot: first plane, levels, grid | is_max << 2
 __global__ __launch_bounds__(256) void k_dia_init(const DevView *__restrict__ Vp, double *__restrict__ accp, const DiaIni T) {
   const DevView &V = *Vp;
   unsigned bx, by;
@@ -196,6 +231,181 @@ __global__ __launch_bounds__(256) void k_dia_finlyr(const DevView *__restrict__ 
   acc[oa] = w > EPSIL ? a / w : NF90_FILL_DOUBLE;
 }
 
+// ---- the depth levels: diazlv + acclvl ------------------------------------------------------------------------------------------
+// One thread per column of grid G (owned points with the grid's mask bit, as above; the reference's extra u-column ii+1 and v-row
+// jj+1 are the neighbour tile's and never written to a file).  Sweep 1 is the column's total thickness (:4806-4816 | :4839-4849 |
+// :4872-4882), sweep 2 walks the layers with the reference's own loop over the levels (:4915-4927 | :4940-4953 | :4966-4979): the
+// carried ind1, `cycle`, `exit`, the comparisons non-strict on p and strict on u / v.  zbot(k) = sum(1..k)*bath/sum(1..kk) with the
+// sum in k order (:4819-4830: the product first; zbot(kk) is rescaled last, so every layer divides by the unscaled total).
+// A grid's slots (<= 12) are dealt to blockIdx.y four at a time.  The accumulators of ONE level -- the one the lane is in -- live in
+// registers for the thread's slots: a one-entry cache keyed by the level, loaded when the lane enters a level, stored when it leaves.  So every element gets its additions in ascending k
+// starting from the value in memory, is read and written once a step, and a u / v layer that re-enters the level above because a
+// bound EQUALS its top (it adds fld*0 there) finds that level's values in memory again.
+// Algorithmic bytes per grid: (2 n_acc ddm + (n_src + 2) kk) planes.
+#define LVL_MAXSLOT 12
+#define DIA_MAXLEV 128
+struct LvlTab {
+  int n, ddm, mlev;            // slots, levels, m - 1
+  int tfld, cfld, clev;        // thickness dp | dpu | dpv (at mm); the condition's field and first plane: dp (mm) | uflx | vflx (nn)
+  int d[LVL_MAXSLOT][4];       // source field, plane of its layer 1, bit 0: weightsflx, bit 1: + ub | vb (m), first plane of the slot
+};
+
+#define LVL_NS 4               // slots of a thread: a grid's slots are dealt to blockIdx.y in groups of four
+#define LVL_KB 2               // layers ahead whose sources are in flight (3: 142 VGPRs on u / v)
+template <int G>
+__global__ __launch_bounds__(256) void k_dialvl(const DevView *__restrict__ Vp, double *__restrict__ accp, const double *__restrict__ edgep, const LvlTab T, int mm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;
+  if (!((V.m[I_mpack][t] >> G) & 1)) return;
+  const size_t np = V.nplane, c = t;
+  const int kk = V.kk, ddm = T.ddm;
+  const int s0 = (int)by * LVL_NS, ns = T.n - s0 < LVL_NS ? T.n - s0 : LVL_NS;      // wave-uniform
+  gd_t acc = global_ptr(accp);
+  gcd_t edge = global_ptr(edgep);                                 // bnds(1,d) = edge[d-1], bnds(2,d) = edge[d]
+  gcd_t th = V.f[T.tfld] + (c + (size_t)mm * np), cs = V.f[T.cfld] + (c + (size_t)T.clev * np);
+  // pbath | ubath | vbath, :1078-1088
+  double bath = V.f[F_depths][c];
+  if (G == G_U) bath = fmin2(bath, V.f[F_depths][c - 1]);
+  if (G == G_V) bath = fmin2(bath, V.f[F_depths][c - V.ni]);
+  // sweep 1: zbot(kk) before the rescaling
+  double tot = 0.;
+  for (int k0 = 0; k0 < kk; k0 += COLUMN_U) {
+    double v[COLUMN_U];
+#pragma unroll
+    for (int u = 0; u < COLUMN_U; u++) v[u] = th[(size_t)(k0 + u < kk ? k0 + u : kk - 1) * np];
+#pragma unroll
+    for (int u = 0; u < COLUMN_U; u++)
+      if (k0 + u < kk) {
+        const double x = G == G_P ? v[u] : fmax2(v[u], DPEPS);
+        tot = k0 + u == 0 ? x : tot + x;
+      }
+  }
+  // sweep 2.  A slot's source and accumulators are a wave-uniform pointer plus the lane's offset.
+  gcd_t sp[LVL_NS];
+  gd_t ap[LVL_NS];
+  int flx = 0, aux = 0;
+#pragma unroll
+  for (int s = 0; s < LVL_NS; s++) {
+    const int q = s0 + (s < ns ? s : 0);
+    sp[s] = V.f[T.d[q][0]] + (size_t)T.d[q][1] * np;
+    ap[s] = acc + (size_t)T.d[q][3] * np;
+    if (s < ns && (T.d[q][2] & 1)) flx |= 1 << s;
+    if (s < ns && (T.d[q][2] & 2)) aux |= 1 << s;
+  }
+  const double sub = aux ? V.f[G == G_V ? F_vb : F_ub][c + (size_t)T.mlev * np] : 0.;      // uvel = u(km) + ub(m), :1180; vvel :1195
+  // a: the level the lane is in (dc); an: the level below it (dn), requested when the lane entered dc, behind the store that the
+  // entry issued -- so a lane that steps back one level (the u / v equality case) and forward again reads what it stored
+  double a[LVL_NS], an[LVL_NS];
+#pragma unroll
+  for (int s = 0; s < LVL_NS; s++) a[s] = an[s] = 0.;
+  double run = 0., ztop = 0.;
+  int ind1 = 0, dc = -1, dn = -1;
+  // the sources of the next LVL_KB layers wait in a queue of registers: layer k + LVL_KB is requested at the top of layer k
+  double thq[LVL_KB], csq[LVL_KB], fq[LVL_KB][LVL_NS];
+#pragma unroll
+  for (int u = 0; u < LVL_KB; u++) {
+    const size_t o = (size_t)(u < kk ? u : kk - 1) * np;
+    thq[u] = th[o];
+    csq[u] = cs[o];
+#pragma unroll
+    for (int s = 0; s < LVL_NS; s++) fq[u][s] = s < ns ? sp[s][c + o] : 0.;
+  }
+  for (int k = 0; k < kk; k++) {
+    {
+      const double thk = thq[0], csk = csq[0];
+      double f[LVL_NS];
+#pragma unroll
+      for (int s = 0; s < LVL_NS; s++) f[s] = (aux >> s) & 1 ? fq[0][s] + sub : fq[0][s];
+#pragma unroll
+      for (int u = 0; u + 1 < LVL_KB; u++) {
+        thq[u] = thq[u + 1];
+        csq[u] = csq[u + 1];
+#pragma unroll
+        for (int s = 0; s < LVL_NS; s++) fq[u][s] = fq[u + 1][s];
+      }
+      {
+        const size_t o = (size_t)(k + LVL_KB < kk ? k + LVL_KB : kk - 1) * np;
+        thq[LVL_KB - 1] = th[o];
+        csq[LVL_KB - 1] = cs[o];
+#pragma unroll
+        for (int s = 0; s < LVL_NS; s++)
+          if (s < ns) fq[LVL_KB - 1][s] = sp[s][c + o];
+      }
+      const double x = G == G_P ? thk : fmax2(thk, DPEPS);
+      run = k == 0 ? x : run + x;
+      const double zbot = run * bath / tot;
+      if (G == G_P ? csk > DPEPS : fabs(csk) > FLXEPS) {
+        for (int d = ind1; d < ddm; d++) {
+          const double lo = edge[d], hi = edge[d + 1];
+          if (G == G_P ? hi <= ztop : hi < ztop) { ind1 = d + 1; continue; }
+          if (G == G_P ? lo >= zbot : lo > zbot) break;
+          if (d != dc) {
+            const size_t od = c + (size_t)d * np;
+            if (dc >= 0) {
+#pragma unroll
+              for (int s = 0; s < LVL_NS; s++)
+                if (s < ns) ap[s][c + (size_t)dc * np] = a[s];
+            }
+            if (d == dn) {
+#pragma unroll
+              for (int s = 0; s < LVL_NS; s++) a[s] = an[s];
+            } else {
+#pragma unroll
+              for (int s = 0; s < LVL_NS; s++)
+                if (s < ns) a[s] = ap[s][od];
+            }
+            dc = d;
+            dn = d + 1 < ddm ? d + 1 : -1;
+            if (dn >= 0) {
+#pragma unroll
+              for (int s = 0; s < LVL_NS; s++)
+                if (s < ns) an[s] = ap[s][od + np];
+            }
+          }
+          const double r = fmin2(zbot, hi) - fmax2(ztop, lo);
+          const double w = r / fmax2(DZEPS, fmin2(bath, hi) - lo);           // r/dlev(d), :4776-4789, :4924-4926 | :4951 | :4977
+          const double wf = G == G_P ? 0. : r / (zbot - ztop);               // weightsflx, :4952 | :4978
+#pragma unroll
+          for (int s = 0; s < LVL_NS; s++)
+            if (s < ns) a[s] = a[s] + f[s] * (G != G_P && ((flx >> s) & 1) ? wf : w);     // acclvl, :5741 | :5754 | :5767
+        }
+      }
+      ztop = zbot;
+    }
+  }
+  if (dc >= 0) {
+#pragma unroll
+    for (int s = 0; s < LVL_NS; s++)
+      if (s < ns) ap[s][c + (size_t)dc * np] = a[s];
+  }
+}
+
+// msklvl (:6659-6738): at EVERY owned point, wet or not, the levels behind kmax -- the last one whose upper bound lies above the
+// bottom (of the shallower of the two p-points on u / v) -- become nf90_fill_double.  The bounds increase, so level d is kept
+// exactly when bath > bnds(1,d).
+struct MskTab { int n, ddm; int d[3 * LVL_MAXSLOT][2]; };         // per slot: first plane, grid
+__global__ __launch_bounds__(256) void k_dia_msklvl(const DevView *__restrict__ Vp, double *__restrict__ accp, const double *__restrict__ edgep, const MskTab T) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, d = by;
+  if (t >= V.nplane || d >= T.ddm) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;
+  gd_t acc = global_ptr(accp);
+  const double lo = global_ptr(edgep)[d], dep = V.f[F_depths][t];
+  const double bath[3] = {dep, fmin2(dep, V.f[F_depths][t - 1]), fmin2(dep, V.f[F_depths][t - V.ni])};
+  for (int s = 0; s < T.n; s++) {
+    const double b = T.d[s][1] == G_P ? bath[0] : T.d[s][1] == G_U ? bath[1] : bath[2];
+    if (!(b > lo)) acc[(size_t)t + ((size_t)T.d[s][0] + d) * V.nplane] = NF90_FILL_DOUBLE;
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static int dia_init(blomgpu_ctx *c, DiaState *S) {
   DiaIni T;
@@ -203,7 +413,7 @@ static int dia_init(blomgpu_ctx *c, DiaState *S) {
   int maxlev = 1;
   for (size_t s = 0; s < S->rows.size(); s++) {
     const DiaRow &r = g_rows[S->rows[s]];
-    const int nl = r.lyr ? c->h.kk : 1;
+    const int nl = r.lyr == 2 ? S->ddm : r.lyr ? c->h.kk : 1;
     T.d[T.n][0] = S->plane0[s]; T.d[T.n][1] = nl; T.d[T.n][2] = r.grid | (r.op == OP_MAX) << 2;
     T.n++;
     if (nl > maxlev) maxlev = nl;
@@ -228,7 +438,16 @@ bool dia_active(const blomgpu_ctx *c) { return c->dia != nullptr; }
 void dia_count(blomgpu_ctx *c) { if (c->dia) c->dia->nacc++; }
 
 // z and dz are cmnfld1's: a step that does not run it would accumulate whatever the arrays hold
+static bool hybrid_remapped(int r) {       // the level rows the hybrid coordinate forms inside ale_regrid_remap (:1944, :2059, :2174 leave them out)
+  const std::string nm = g_rows[r].name;
+  return nm == "uvellvl" || nm == "vvellvl" || nm == "salnlvl" || nm == "templvl";
+}
+
 int dia_step_check(blomgpu_ctx *c) {
+  if (c->dia && c->h.P.vcoord_tag != 1)
+    for (int r : c->dia->rows)
+      if (hybrid_remapped(r))
+        return ctx_fail(c, std::string("blomgpu_step: ") + g_rows[r].name + " is selected, which cntiso_hybrid / plevel form inside ale_regrid_remap (not built)");
   if (!c->dia || !c->dia->needs_z) return 0;
   if (c->h.P.vcoord_tag != 1 || c->cmnfld1 || c->full_physics) return 0;
   std::string names;
@@ -258,6 +477,8 @@ int dia_select(blomgpu_ctx *c, const char *names) {
       return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the two-equation closure (itrtke >= 1, gls = 1)");
     if ((g_rows[r].lev == LV_TKE || g_rows[r].lev == LV_GLS) && (c->h.P.itrtke > c->h.ntr || c->h.P.itrgls > c->h.ntr))
       return ctx_fail(c, "blomgpu_dia_select: " + nm + ": itrtke / itrgls outside 1..ntr");
+    if (c->h.P.vcoord_tag != 1 && hybrid_remapped(r))
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + " is formed inside ale_regrid_remap under cntiso_hybrid / plevel (phy/mod_dia.F90:1944, :2059, :2174 leave it out): not built");
     want[r] = 1;
     any = true;
   }
@@ -267,23 +488,35 @@ int dia_select(blomgpu_ctx *c, const char *names) {
   DiaState *S = nullptr;
   if (any) {
     S = new DiaState;
-    int n2d = 0, nly = 0;
-    for (int pass = 0; pass < 2; pass++)
+    int n2d = 0, nly = 0, nlv = 0;
+    for (int r = 0; r < NROW; r++)
+      if (want[r] && g_rows[r].lyr == 2) nlv++;
+    const std::vector<double> edges = c->dia_edges.empty() ? std::vector<double>(g_edges35, g_edges35 + 36) : c->dia_edges;
+    S->np = c->h.nplane;
+    S->ddm = nlv ? (int)edges.size() - 1 : 0;
+    for (int pass = 0; pass < 3; pass++)
       for (int r = 0; r < NROW; r++)
         if (want[r] && g_rows[r].lyr == pass) {
           S->rows.push_back(r);
           S->plane0.push_back((int)S->nplanes);
-          S->nplanes += pass ? c->h.kk : 1;
-          (pass ? nly : n2d)++;
+          S->nplanes += pass == 2 ? S->ddm : pass ? c->h.kk : 1;
+          if (pass < 2) (pass ? nly : n2d)++;
           if (g_rows[r].src == F_z || g_rows[r].src == F_dz) S->needs_z = true;
         }
     if (n2d > DIA_MAXSLOT || nly > DIA_MAXSLOT) { delete S; return ctx_fail(c, "blomgpu_dia_select: more slots than a launch carries"); }
     (void)hipSetDevice(c->device);
-    if (hipMalloc((void **)&S->acc, sizeof(double) * S->nplanes * (size_t)c->h.nplane) != hipSuccess) {
+    // (the edges of the depth levels lie behind the last plane)
+    if (hipMalloc((void **)&S->acc, sizeof(double) * (S->nplanes * (size_t)c->h.nplane + (S->ddm ? S->ddm + 1 : 0))) != hipSuccess) {
       (void)hipGetLastError();
       const size_t mb = sizeof(double) * S->nplanes * (size_t)c->h.nplane >> 20;
       delete S;
       return ctx_fail(c, "blomgpu_dia_select: no device memory for " + std::to_string(mb) + " MB of accumulators");
+    }
+    if (S->ddm && hipMemcpy(S->edges(), edges.data(), sizeof(double) * edges.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(S->acc);
+      delete S;
+      return ctx_fail(c, "blomgpu_dia_select: the depth levels could not be copied to the device");
     }
     if (dia_init(c, S)) { (void)hipFree(S->acc); delete S; return 1; }
   }
@@ -306,7 +539,7 @@ int dia_get(blomgpu_ctx *c, const char *name, double *out) {
   const int r = find_row(name), s = r >= 0 && c->dia ? c->dia->slot_of(r) : -1;
   if (r < 0) return ctx_fail(c, std::string("blomgpu_dia_get: unknown accumulator ") + name);
   if (s < 0) return ctx_fail(c, std::string("blomgpu_dia_get: accumulator ") + name + " is not selected");
-  const size_t np = c->h.nplane, nl = g_rows[r].lyr ? c->h.kk : 1;
+  const size_t np = c->h.nplane, nl = g_rows[r].lyr == 2 ? c->dia->ddm : g_rows[r].lyr ? c->h.kk : 1;
   HIPCHK(c, hipMemcpyAsync(out, c->dia->acc + (size_t)c->dia->plane0[s] * np, sizeof(double) * nl * np, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
@@ -327,11 +560,49 @@ int dia_finalize(blomgpu_ctx *c) {
   ctx_sync_view(c);
   for (size_t s = 0; s < S->rows.size(); s++) {
     const DiaRow &r = g_rows[S->rows[s]];
-    if (!r.lyr || !r.wgt) continue;
+    if (r.lyr != 1 || !r.wgt) continue;
     const int ws = S->slot_of(find_row(r.wgt == W_DP ? "dp" : r.wgt == W_DPU ? "dpu" : "dpv"));
     hipLaunchKernelGGL(k_dia_finlyr, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, S->acc, S->plane0[s], S->plane0[ws], r.grid);
   }
+  // msklvl for every depth-level slot (:2642-2679)
+  MskTab M;
+  M.n = 0; M.ddm = S->ddm;
+  for (size_t s = 0; s < S->rows.size(); s++)
+    if (g_rows[S->rows[s]].lyr == 2) { M.d[M.n][0] = S->plane0[s]; M.d[M.n][1] = g_rows[S->rows[s]].grid; M.n++; }
+  if (M.n) hipLaunchKernelGGL(k_dia_msklvl, plane_grid(c->h, S->ddm), dim3(256), 0, c->stream, c->d, S->acc, S->edges(), M);
   HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// ---- the depth levels (blomgpu_dia_set_levels): ddm + 1 edges kept in the context, copied to the device with a selection ----------
+static bool dia_has_levels(const blomgpu_ctx *c) { return c->dia && c->dia->ddm; }
+
+int dia_set_levels(blomgpu_ctx *c, const double *bnds, int ddm) {
+  if (dia_has_levels(c)) return ctx_fail(c, "blomgpu_dia_set_levels: a depth-level accumulator is selected; deselect the *lvl names first");
+  if (!bnds && ddm == 0) { c->dia_edges.clear(); return 0; }             // back to the 35 levels of :111-128
+  if (!bnds || ddm < 1) return ctx_fail(c, "blomgpu_dia_set_levels: bounds and ddm >= 1, or NULL and 0 for the default table");
+  if (ddm > DIA_MAXLEV) return ctx_fail(c, "blomgpu_dia_set_levels: ddm = " + std::to_string(ddm) + ": at most " + std::to_string(DIA_MAXLEV) + " levels");
+  for (int d = 0; d < ddm; d++) {
+    if (!(bnds[2 * d + 1] > bnds[2 * d])) return ctx_fail(c, "blomgpu_dia_set_levels: the bounds of level " + std::to_string(d + 1) + " are not increasing");
+    if (d + 1 < ddm && bnds[2 * d + 1] != bnds[2 * d + 2])
+      return ctx_fail(c, "blomgpu_dia_set_levels: levels " + std::to_string(d + 1) + " and " + std::to_string(d + 2) + " are not contiguous (bnds[d][1] == bnds[d+1][0])");
+  }
+  c->dia_edges.assign(1, bnds[0]);
+  for (int d = 0; d < ddm; d++) c->dia_edges.push_back(bnds[2 * d + 1]);
+  return 0;
+}
+
+int dia_levels_levitus2x(blomgpu_ctx *c) {                                 // LEVITUS2X, :130-159
+  if (dia_has_levels(c)) return ctx_fail(c, "blomgpu_dia_levels_levitus2x: a depth-level accumulator is selected; deselect the *lvl names first");
+  c->dia_edges.assign(g_edges70, g_edges70 + 71);
+  return 0;
+}
+
+int dia_get_levels(blomgpu_ctx *c, double *bnds, int cap, int *ddm) {
+  if (!ddm) return ctx_fail(c, "blomgpu_dia_get_levels: null argument");
+  const double *e = c->dia_edges.empty() ? g_edges35 : c->dia_edges.data();
+  *ddm = c->dia_edges.empty() ? 35 : (int)c->dia_edges.size() - 1;
+  for (int d = 0; bnds && d < *ddm && d < cap; d++) { bnds[2 * d] = e[d]; bnds[2 * d + 1] = e[d + 1]; }
   return 0;
 }
 
@@ -375,6 +646,32 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     if (!T.n) continue;
     TimeScope ts(c, pass ? "diaacc_lyr" : "diaacc_h2d");
     hipLaunchKernelGGL(k_diaacc, plane_grid(h, pass ? h.kk : 1), dim3(256), 0, c->stream, c->d, S->acc, T, mm);
+  }
+  // the depth levels: one launch per grid that has a selected name, in the reference's order u, v, p
+  static const int order[3] = {G_U, G_V, G_P};
+  for (int o = 0; S->ddm && o < 3; o++) {
+    const int g = order[o];
+    LvlTab T;
+    T.n = 0; T.ddm = S->ddm; T.mlev = m - 1;
+    T.tfld = g == G_P ? F_dp : g == G_U ? F_dpu : F_dpv;
+    T.cfld = g == G_P ? F_dp : g == G_U ? F_uflx : F_vflx;
+    T.clev = g == G_P ? mm : nn;
+    for (size_t s = 0; s < S->rows.size(); s++) {
+      const DiaRow &r = g_rows[S->rows[s]];
+      if (r.lyr != 2 || r.grid != g) continue;
+      int *d = T.d[T.n++];
+      d[0] = r.src;
+      d[1] = r.lev == LV_MM ? mm : r.lev == LV_NN ? nn : r.lev == LV_TKE ? (h.P.itrtke - 1) * 2 * h.kk + mm : r.lev == LV_GLS ? (h.P.itrgls - 1) * 2 * h.kk + mm : 0;
+      d[2] = (r.op == OP_LVLFLX ? 1 : 0) | (r.aux != A_NONE ? 2 : 0);
+      d[3] = S->plane0[s];
+    }
+    if (!T.n) continue;
+    for (int s = T.n; s < LVL_MAXSLOT; s++) T.d[s][0] = T.d[s][1] = T.d[s][2] = T.d[s][3] = 0;
+    TimeScope ts(c, g == G_P ? "dialvl_p" : g == G_U ? "dialvl_u" : "dialvl_v");
+    const dim3 grid = plane_grid(h, (T.n + LVL_NS - 1) / LVL_NS);
+    if (g == G_P) hipLaunchKernelGGL((k_dialvl<G_P>), grid, dim3(256), 0, c->stream, c->d, S->acc, S->edges(), T, mm);
+    else if (g == G_U) hipLaunchKernelGGL((k_dialvl<G_U>), grid, dim3(256), 0, c->stream, c->d, S->acc, S->edges(), T, mm);
+    else hipLaunchKernelGGL((k_dialvl<G_V>), grid, dim3(256), 0, c->stream, c->d, S->acc, S->edges(), T, mm);
   }
   HIPCHK(c, hipGetLastError());
   return 0;

@@ -105,6 +105,21 @@ module mod_blomgpu
       import :: c_ptr, c_int
       type(c_ptr), value :: c
     end function
+    integer(c_int) function blomgpu_dia_set_levels(c, bnds, ddm) bind(C, name='blomgpu_dia_set_levels')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, bnds
+      integer(c_int), value :: ddm
+    end function
+    integer(c_int) function blomgpu_dia_levels_levitus2x(c) bind(C, name='blomgpu_dia_levels_levitus2x')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_dia_get_levels(c, bnds, cap, ddm) bind(C, name='blomgpu_dia_get_levels')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, bnds
+      integer(c_int), value :: cap
+      integer(c_int), intent(out) :: ddm
+    end function
     integer(c_int) function blomgpu_field_info(c, name, nlev, isint) bind(C, name='blomgpu_field_info')
       import :: c_ptr, c_int, c_char
       type(c_ptr), value :: c
@@ -220,6 +235,7 @@ module mod_blomgpu
             cmnfld1, cmnfld2, ale_regrid_remap, ale_vdifft, ale_vdiffm, ale_forcing, &
             cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc
   public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc
+  public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
 
   interface gpu_set
     module procedure gpu_set_real, gpu_set_int, gpu_set_str
@@ -534,7 +550,8 @@ contains
     character(len=*), intent(in) :: names
     call gpu_check(blomgpu_dia_select(ctx, cz(names)), 'gpu_dia_select')
   end subroutine
-  ! the accumulator on the tile's padded plane(s): nlev = 1 for a 2-D name, kdm for a layer name (phyh2d / phylyr of the reference)
+  ! the accumulator on the tile's padded plane(s): nlev = 1 for a 2-D name, kdm for a layer name, ddm for a depth-level name
+  ! (phyh2d / phylyr / phylvl of the reference)
   subroutine gpu_dia_get(name, a, nlev)
     character(len=*), intent(in) :: name
     integer, intent(in) :: nlev
@@ -546,6 +563,26 @@ contains
   end subroutine
   subroutine gpu_dia_reset()                    ! inifld, phy/mod_dia.F90:5864
     call gpu_check(blomgpu_dia_reset(ctx), 'gpu_dia_reset')
+  end subroutine
+  ! the depth levels of the *lvl names as depthslev_bnds(2,ddm) (phy/mod_dia.F90:119-128); refused while a *lvl name is selected
+  subroutine gpu_dia_set_levels(bnds, ddm)
+    integer, intent(in) :: ddm
+    real(8), intent(in), target :: bnds(2,ddm)
+    call gpu_check(blomgpu_dia_set_levels(ctx, c_loc(bnds), int(ddm, c_int)), 'gpu_dia_set_levels')
+  end subroutine
+  subroutine gpu_dia_default_levels()           ! the 35 levels of phy/mod_dia.F90:111-128
+    call gpu_check(blomgpu_dia_set_levels(ctx, c_null_ptr, 0_c_int), 'gpu_dia_default_levels')
+  end subroutine
+  subroutine gpu_dia_levitus2x()                ! the 70 levels of LEVITUS2X, :130-159
+    call gpu_check(blomgpu_dia_levels_levitus2x(ctx), 'gpu_dia_levitus2x')
+  end subroutine
+  subroutine gpu_dia_get_levels(bnds, cap, ddm) ! ddm, and the first min(cap, ddm) levels' bounds
+    integer, intent(in) :: cap
+    real(8), intent(out), target :: bnds(2,cap)
+    integer, intent(out) :: ddm
+    integer(c_int) :: v
+    call gpu_check(blomgpu_dia_get_levels(ctx, c_loc(bnds), int(cap, c_int), v), 'gpu_dia_get_levels')
+    ddm = v
   end subroutine
   integer function gpu_dia_nacc()               ! nacc_phy
     integer(c_int) :: v

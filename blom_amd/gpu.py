@@ -212,11 +212,12 @@ class BlomGpu:
 
     # -- time-mean diagnostics (diaacc, phy/mod_dia.F90) -------------------------------------
     def dia_names(self):
-        """the accumulator table: [(name, is_layer, grid)] with grid one of "p", "u", "v" """
+        """the accumulator table: [(name, kind, grid)] with kind 0 = 2-D, 1 = kdm layers, 2 = ddm depth levels and grid one of
+        "p", "u", "v" """
         rows, buf, k = [], C.create_string_buffer(32), 0
         lyr, grid = C.c_int(0), C.c_int(0)
         while self.lib.blomgpu_dia_name(k, buf, 32, C.byref(lyr), C.byref(grid)) == 0:
-            rows.append((buf.value.decode(), bool(lyr.value), "puv"[grid.value]))
+            rows.append((buf.value.decode(), lyr.value, "puv"[grid.value]))
             k += 1
         return rows
 
@@ -235,12 +236,13 @@ class BlomGpu:
         return v.value
 
     def dia_get(self, name):
-        """the accumulator as get() would return a field: (1 | kdm, nj, ni)"""
+        """the accumulator as get() would return a field: (1 | kdm | ddm, nj, ni)"""
         if not hasattr(self, "_dia_lyr"):
             self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names()}
         if name not in self._dia_lyr:
             raise KeyError(name)
-        a = np.empty((self.kdm if self._dia_lyr[name] else 1, self.nj, self.ni), dtype=np.float64)
+        nlev = (1, self.kdm, len(self.dia_levels()))[self._dia_lyr[name]]
+        a = np.empty((nlev, self.nj, self.ni), dtype=np.float64)
         self._chk(self.lib.blomgpu_dia_get(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p)))
         return a
 
@@ -249,6 +251,25 @@ class BlomGpu:
 
     def dia_reset(self):
         self._chk(self.lib.blomgpu_dia_reset(self.ctx))
+
+    def dia_set_levels(self, bnds=None, levitus2x=False):
+        """the depth levels of the *lvl names: bnds[ddm][2] (upper, lower bound in metres; increasing, contiguous), None for the
+        default 35 levels, levitus2x=True for the reference's 70 -- blomgpu_dia_set_levels / blomgpu_dia_levels_levitus2x"""
+        if levitus2x:
+            self._chk(self.lib.blomgpu_dia_levels_levitus2x(self.ctx))
+        elif bnds is None:
+            self._chk(self.lib.blomgpu_dia_set_levels(self.ctx, None, 0))
+        else:
+            a = np.ascontiguousarray(bnds, dtype=np.float64).reshape(-1, 2)
+            self._chk(self.lib.blomgpu_dia_set_levels(self.ctx, a.ctypes.data_as(C.c_void_p), C.c_int(a.shape[0])))
+
+    def dia_levels(self):
+        """the depth levels in force, (ddm, 2) -- blomgpu_dia_get_levels"""
+        ddm = C.c_int(0)
+        self._chk(self.lib.blomgpu_dia_get_levels(self.ctx, None, 0, C.byref(ddm)))
+        a = np.empty((ddm.value, 2), dtype=np.float64)
+        self._chk(self.lib.blomgpu_dia_get_levels(self.ctx, a.ctypes.data_as(C.c_void_p), ddm, C.byref(ddm)))
+        return a
 
     # -- tile decomposition ---------------------------------------------------------------
     def rccl_init(self, id128, rank, nranks):

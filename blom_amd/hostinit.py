@@ -203,6 +203,9 @@ def init_state(be, case):
 
     for nm, arr in case.grid.items():
         be.put(nm, arr[None])
+    # the bathymetry with bigrid's edits (mod_grid's depths): read by the depth-level diagnostics only (blomgpu_dia_select, *lvl names)
+    if getattr(be, "has_field", lambda nm: False)("depths"):
+        be.put("depths", bigrid_np(case.depth, ii, jj, arctic=nreg == 2)[1][None])
     difmxp, difmxq, umax, vmax = numerical_bounds_np(case.grid, be.masks, P["baclin"], nreg, ii, jj)
     be.put("difmxp", difmxp[None])
     be.put("difmxq", difmxq[None])

@@ -197,7 +197,9 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  * that read arrays the device holds -- acch2d (:1547-1745, :5182), maxh2d (:1752, :5285), sqh2d (:1780-1786, :5409), acclyr
  * (:1793-1913, :5471) -- one output group.  A name is the reference's ACC_* suffix in lower case: "ub", "sealv", "maxbld", "uvel",
  * "temp" ... (the table: blom_amd/csrc/stage_diaacc.hip, enumerated by blomgpu_dia_name; what is left out: DESIGN.md 7).
- * Writing files, z-level interpolation and the scaling by 1/nacc (wrth2d, wrtlyr) stay on the host.
+ * Writing files and the scaling by 1/nacc (wrth2d, wrtlyr, wrtlvl) stay on the host.  The z-level (Levitus) interpolation does
+ * not: a layer is mapped onto the depth levels with THAT step's interfaces (diazlv :4737-4993, acclvl :5709-5781), so the level
+ * names below are accumulated on the device every step like the others.
  *
  * blomgpu_dia_select: `names` is a blank-separated list that REPLACES the selection; "" deselects everything and frees the
  *   accumulators.  Adds diaini's dependencies (:598-608: a dp-weighted name selects "dp", "uvel" selects "dpu", "vvel" "dpv"),
@@ -212,8 +214,22 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  * blomgpu_dia_finalize: finlyr (:6114-6185) in place for the weighted layer pairs of :2597-2611 -- acc/wgt where wgt > 1e-11, else
  *   nf90_fill_double = 9.9692099683868690e+36.  (finh2d, :6054: the table has no weighted 2-D row.)
  * blomgpu_dia_reset: inifld (:5864) for the selection: re-initialises and sets nacc = 0.
- * blomgpu_dia_name: row `index` of the table (0, 1, ... until the return value is non-zero); is_lyr 0 = 2-D, 1 = kdm layers;
- *   grid 0 p, 1 u, 2 v. */
+ * blomgpu_dia_name: row `index` of the table (0, 1, ... until the return value is non-zero); is_lyr 0 = 2-D, 1 = kdm layers,
+ *   2 = ddm depth levels; grid 0 p, 1 u, 2 v.  Rows 0..77 are the 2-D and layer rows, rows 78..110 the depth-level rows.
+ *
+ * Depth-level names (33; isopycnic coordinate :2000-2053, :2119-2168, :2222-2271): "uvellvl" and the u-fluxes "uflxlvl utflxlvl
+ *   usflxlvl umfltdlvl umflsmlvl utfltdlvl utflsmlvl utflldlvl usfltdlvl usflsmlvl usflldlvl", the same twelve on v, and on p
+ *   "salnlvl templvl bfsqlvl difintlvl difisolvl difdialvl tkelvl gls_psilvl dzlvl".  They add no dependencies; "tkelvl" /
+ *   "gls_psilvl" need what "tke" / "gls_psi" need; "dzlvl" reads cmnfld1's dz like "dz".  Under cntiso_hybrid / plevel the
+ *   reference forms "uvellvl vvellvl salnlvl templvl" inside ale_regrid_remap (:1944, :2059, :2174 leave them out): those four
+ *   are refused there.  blomgpu_dia_get returns ddm planes for a level name; blomgpu_dia_finalize applies msklvl (:6659-6738) to
+ *   them: at every owned point the levels whose upper bound is not above the bottom become nf90_fill_double.  Not built:
+ *   accilv (difvmolvl difvholvl difvsolvl), pvlvl, wflxlvl / wflx2lvl (diavfl), the tracer levels (:3688-3788).
+ * blomgpu_dia_set_levels: the depth levels as bnds[ddm][2] = (upper, lower) bound of each level in metres, increasing and
+ *   contiguous (bnds[d][1] == bnds[d+1][0]), ddm <= 128; otherwise, or while a level name is selected, it fails with a message and
+ *   changes nothing.  bnds == NULL with ddm == 0 restores the default, the 35 levels of :111-128.
+ * blomgpu_dia_levels_levitus2x: the 70 levels of LEVITUS2X (:130-159); refused while a level name is selected.
+ * blomgpu_dia_get_levels: *ddm, and the first min(cap, ddm) rows of the bounds into bnds (may be NULL). */
 int  blomgpu_dia_select(blomgpu_ctx *, const char *names);
 int  blomgpu_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int  blomgpu_dia_nacc(blomgpu_ctx *, int *nacc);
@@ -221,6 +237,9 @@ int  blomgpu_dia_get(blomgpu_ctx *, const char *name, double *out);
 int  blomgpu_dia_finalize(blomgpu_ctx *);
 int  blomgpu_dia_reset(blomgpu_ctx *);
 int  blomgpu_dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
+int  blomgpu_dia_set_levels(blomgpu_ctx *, const double *bnds /* [ddm][2] */, int ddm);
+int  blomgpu_dia_levels_levitus2x(blomgpu_ctx *);
+int  blomgpu_dia_get_levels(blomgpu_ctx *, double *bnds /* [cap][2] */, int cap, int *ddm);
 
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,

@@ -46,7 +46,7 @@ def bound_bytes(rows, selected, case):
     """(2 n_acc + n_distinct_sources) F for the layer launch, the same with G for the 2-D launch"""
     F = case.idm * case.jdm * case.kdm * 8
     G = case.idm * case.jdm * 8
-    lyr = [nm for nm, is_lyr, _ in rows if is_lyr and nm in selected]
+    lyr = [nm for nm, is_lyr, _ in rows if is_lyr == 1 and nm in selected]
     h2d = [nm for nm, is_lyr, _ in rows if not is_lyr and nm in selected]
     # a layer row reads its own 3-D source, except dp / dpu / dpv, whose source is the weight the point has loaded anyway
     src_l = len([nm for nm in lyr if nm not in ("dp", "dpu", "dpv")]) + len({"dp", "dpu", "dpv"} & (set(lyr) | {WEIGHT[nm] for nm in lyr if nm in WEIGHT}))
@@ -69,7 +69,7 @@ def main():
     for label in ("whole", "monthly"):
         gpu = bench.device_for_bench(case, nreg, masks, live=True)
         rows = gpu.dia_names()
-        names = MONTHLY if label == "monthly" else [nm for nm, _, _ in rows if nm != "gls_psi"]
+        names = MONTHLY if label == "monthly" else [nm for nm, kind, _ in rows if nm != "gls_psi" and kind != 2]           # (the depth levels: tools/gpu_dialvl_cost.py)
         gpu.dia_select(names)
         selected = set(names) | {WEIGHT[nm] for nm in names if nm in WEIGHT}       # diaini's dependencies, phy/mod_dia.F90:598-608
         b = bound_bytes(rows, selected, case)
