@@ -24,6 +24,7 @@ reference, so the values below ARE this project's published choic
 Array convention everywhere on the host side: numpy C-order (nlev, jdm+8, idm+8);
 Fortran a(i,j,k) is arr[k-1, j+3, i+3]  (nbdy = 4, phy/mod_xc.F90:45).
 """
+import contextlib
 from dataclasses import dataclass, field
 import numpy as np
 
@@ -376,11 +377,103 @@ def fuk95_ref_case(ntr=1, **overrides):
     return Case(name="fuk95_ref", idm=idm, jdm=jdm, kdm=kdm, nreg=nreg, params=p, depth=depth, grid=g, ic=ic, ntr=ntr)
 
 
-def make_case(name, ntr=None, carve=None, **overrides):
+# ---- curvilinear grids: anisotropic, spatially varying metrics and a Coriolis parameter that varies (and changes sign) ----
+GRIDS = ("uniform", "warped", "warped_eq")
+# grid type of each array (xctilr's itype: 1 p, 2 q, 3 u, 4 v; phy/mod_inigeo.F90:136-156)
+GRID_ITYPE = dict(scqx=2, scqy=2, scpx=1, scpy=1, scux=3, scuy=3, scvx=4, scvy=4, scq2=2, scp2=1, scu2=3, scv2=4,
+                  scq2i=2, scp2i=1, scuxi=3, scuyi=3, scvxi=4, scvyi=4, corioq=2, coriop=1, betafp=1)
+# location of each point type relative to p(i,j), in grid indices (phy/mod_grid.F90: q at the SW corner, u on the W, v on the S side)
+_STAGGER = {"p": (0.0, 0.0), "q": (-0.5, -0.5), "u": (-0.5, 0.0), "v": (0.0, -0.5)}
+
+
+def warped_grid(idm, jdm, nreg, dx, kind):
+    """The metric arrays of a synthetic curvilinear grid, for the parity tests: on a uniform Cartesian f-plane a kernel that reads
+    scuy for scvy, a neighbour one point off, scp2 for scu2, corioq at the wrong corner or a wrong window of the grid gives the bits of
+    the correct one.  Here every base array sc[pquv][xy] is its own smooth function (x and y spacings differ in shape, amplitude about
+    +-30 %, mean aspect ratio 0.7) evaluated at the location of its own point type, so that no two of them agree anywhere and none
+    equals its own neighbours; corioq and coriop are one f(x, y) at q and at p, varying in both directions, positive everywhere
+    (`warped`) or changing sign inside the domain with no point at zero (`warped_eq`); betafp is non-zero and varies between
+    5e-12 and 2.5e-11 m-1 s-1, the planet's range: it enters difest's Rossby radius, equatorial scale, eddy phase speed and planetary
+    Rhines scale, and stays below a fifth (1 / rhiscf) of the topographic beta of hostinit.init_difest (2e-10 .. 1.8e-9), so that with
+    rhsctp the topographic Rhines scale is the smaller one, as on the f-plane (a betafp of 1e-10 and more takes that branch away:
+    tests/test_xcheck_difest.py::test_rhsctp_acts_on_the_layer_interface_diffusivities then misses its bar on box_s).
+    The functions are periodic in i and j where the domain is; at the arctic seam the grid is not symmetric (the halo rule below
+    decides what the seam rows hold, as it does in the reference).
+
+    The rest follows phy/mod_inigeo.F90:100-156: products (channel/mod_channel.F90:150-153) and guarded inverses on the interior, then
+    every array gets its halo from xctilr with its own point type.  The halos are therefore exact copies of interior values (not the
+    functions evaluated again, which differ from them by an ulp at a periodic seam), and closed sides hold xctilr's land value 0."""
+    from .hostinit import xctilr_np
+    assert kind in ("warped", "warped_eq"), kind
+    ni, nj = idm + 2 * NBDY, jdm + 2 * NBDY
+    jj_, ii_ = np.meshgrid(np.arange(1.0, jdm + 1), np.arange(1.0, idm + 1), indexing="ij")
+    two_pi = 2.0 * np.pi
+
+    def at(pt):
+        ox, oy = _STAGGER[pt]
+        return (ii_ + ox) / idm, (jj_ + oy) / jdm
+
+    def sx(pt):
+        x, y = at(pt)
+        return dx * (1.0 + 0.19 * np.sin(two_pi * x + 0.37) + 0.11 * np.cos(two_pi * y + 1.13))
+
+    def sy(pt):
+        x, y = at(pt)
+        return 0.7 * dx * (1.0 + 0.13 * np.cos(two_pi * 2.0 * x + 0.71) + 0.17 * np.sin(two_pi * y + 2.29))
+
+    def fcor(pt):
+        x, y = at(pt)
+        if kind == "warped":
+            return 1.0e-4 * (1.0 + 0.45 * np.sin(two_pi * y + 0.53) + 0.25 * np.cos(two_pi * x + 1.91))
+        # the zero line wanders about mid-domain (y = 0.5137 + 0.08 cos(..)): both signs on wet points of every case
+        return 2.0e-4 * ((y - 0.5137) - 0.08 * np.cos(two_pi * x + 1.91))
+
+    inner = {}
+    for pt in "pquv":
+        inner["sc%sx" % pt] = sx(pt)
+        inner["sc%sy" % pt] = sy(pt)
+        inner["sc%s2" % pt] = inner["sc%sx" % pt] * inner["sc%sy" % pt]
+    for nm, src in (("scq2i", "scq2"), ("scp2i", "scp2"), ("scuxi", "scux"), ("scvyi", "scvy"), ("scuyi", "scuy"), ("scvxi", "scvx")):
+        inner[nm] = 1.0 / np.maximum(1.0, inner[src])
+    inner["corioq"] = fcor("q")
+    inner["coriop"] = fcor("p")
+    x, y = at("p")
+    inner["betafp"] = 5.0e-12 + 2.0e-11 * (0.5 + 0.5 * np.sin(two_pi * x + 0.9)) * (0.5 + 0.5 * np.cos(two_pi * y + 0.4))
+    g = {}
+    for nm, a in inner.items():
+        full = np.zeros((1, nj, ni))
+        full[0, NBDY:NBDY + jdm, NBDY:NBDY + idm] = a
+        xctilr_np(full, 1, 1, NBDY, NBDY, nreg, idm, jdm, itype=GRID_ITYPE[nm])
+        g[nm] = full[0]
+    return g
+
+
+_default_grid = "uniform"
+
+
+@contextlib.contextmanager
+def default_grid(grid):
+    """Within the block make_case builds `grid` wherever its caller names none: a test runs another test's helper, which builds its
+    own case, on a curvilinear grid without that helper knowing of grids.  (Set and read by the calling thread alone.)"""
+    global _default_grid
+    assert grid in GRIDS, grid
+    old, _default_grid = _default_grid, grid
+    try:
+        yield
+    finally:
+        _default_grid = old
+
+
+def make_case(name, ntr=None, carve=None, *, grid=None, **overrides):
     """`<grid>_tke`: the grid with the reference's default tracer set (meson_options.txt:17-21: turbclo = oneeq +
     advection, iage => -DTKE -DTKEADV -DIDLAGE): ntr = 3 = TKE, the generic-length-scale slot, ideal age
-    (trc/mod_tracers.F90:85-127).  Without the suffix: the -DTRC -DIDLAGE build, ntr = 1."""
+    (trc/mod_tracers.F90:85-127).  Without the suffix: the -DTRC -DIDLAGE build, ntr = 1.
+    grid: "uniform" (Cartesian f-plane) | "warped" | "warped_eq" (warped_grid above; every case but fuk95_ref, which restates the
+    reference's own generator); None: "uniform", or what an enclosing default_grid block names."""
+    grid = _default_grid if grid is None else grid
+    assert grid in GRIDS, grid
     if name == "fuk95_ref":
+        assert grid == "uniform", "fuk95_ref is the reference's own f-plane case"
         return fuk95_ref_case(ntr=1 if ntr is None else ntr, **overrides)
     full_name = name
     tk2 = name.endswith("_tk2")          # turbclo = twoeq, advection, isodif: -DTKE -DGLS -DTKEADV -DTKEIDF
@@ -404,20 +497,23 @@ def make_case(name, ntr=None, carve=None, **overrides):
     if carve is not None:          # test hook: edit the interior bathymetry (0 = land) before the state is derived from it
         carve(depth[NBDY:NBDY + jdm, NBDY:NBDY + idm])
 
-    # ---- grid metrics: uniform Cartesian f-plane (channel/mod_channel.F90:140-161) ----
-    g = {}
-    one = np.ones((nj, ni))
-    for nm in ("scqx", "scqy", "scpx", "scpy", "scux", "scuy", "scvx", "scvy"):
-        g[nm] = dx * one
-    for nm in ("scq2", "scp2", "scu2", "scv2"):
-        g[nm] = (dx * dx) * one
-    for nm, src in (("scq2i", "scq2"), ("scp2i", "scp2"), ("scuxi", "scux"), ("scuyi", "scuy"),
-                    ("scvxi", "scvx"), ("scvyi", "scvy")):
-        g[nm] = 1.0 / g[src]
-    f0 = 1.0e-4
-    g["corioq"] = f0 * one
-    g["coriop"] = f0 * one
-    g["betafp"] = 0.0 * one
+    if grid == "uniform":
+        # ---- grid metrics: uniform Cartesian f-plane (channel/mod_channel.F90:140-161) ----
+        g = {}
+        one = np.ones((nj, ni))
+        for nm in ("scqx", "scqy", "scpx", "scpy", "scux", "scuy", "scvx", "scvy"):
+            g[nm] = dx * one
+        for nm in ("scq2", "scp2", "scu2", "scv2"):
+            g[nm] = (dx * dx) * one
+        for nm, src in (("scq2i", "scq2"), ("scp2i", "scp2"), ("scuxi", "scux"), ("scuyi", "scuy"),
+                        ("scvxi", "scvx"), ("scvyi", "scvy")):
+            g[nm] = 1.0 / g[src]
+        f0 = 1.0e-4
+        g["corioq"] = f0 * one
+        g["coriop"] = f0 * one
+        g["betafp"] = 0.0 * one
+    else:
+        g = warped_grid(idm, jdm, nreg, dx, grid)
 
     # ---- initial layer structure on the interior ------------------------------------
     pref = p["pref"]

@@ -321,21 +321,24 @@ def init_state(be, case):
     def q2(a, b):
         with np.errstate(divide="ignore"):          # land points are masked out below
             return 2. / (a + b)
+    def fq(f, q):
+        with np.errstate(invalid="ignore"):         # 0 * inf where a closed side's halo (f = 0) meets land: masked out as well
+            return f * q
     Ju0, Iu0 = sl(0, jj), sl(1, ii)                       # u-points j=0..jj, i=1..ii
     mu0 = iu[Ju0, Iu0] > 0
     qu = q2(pb_p[0, Ju0, Iu0], pb_p[0, Ju0, sl(0, ii - 1)])
     # writer (i,j') -> q(i,j'+1) first (it is overridden by writer (i,j'+1) -> q(i,j'+1) if valid)
     tgt = pv_[:, sl(1, jj + 1), Iu0]
-    tgt[:] = np.where(mu0[None], (corioq[sl(1, jj + 1), Iu0] * qu)[None], tgt)
+    tgt[:] = np.where(mu0[None], (fq(corioq[sl(1, jj + 1), Iu0], qu))[None], tgt)
     tgt = pv_[:, Ju0, Iu0]
-    tgt[:] = np.where(mu0[None], (corioq[Ju0, Iu0] * qu)[None], tgt)
+    tgt[:] = np.where(mu0[None], (fq(corioq[Ju0, Iu0], qu))[None], tgt)
     Jv0, Iv0 = sl(1, jj), sl(0, ii)                       # v-points j=1..jj, i=0..ii
     mv0 = iv[Jv0, Iv0] > 0
     qv = q2(pb_p[0, Jv0, Iv0], pb_p[0, sl(0, jj - 1), Iv0])
     tgt = pv_[:, Jv0, sl(1, ii + 1)]
-    tgt[:] = np.where(mv0[None], (corioq[Jv0, sl(1, ii + 1)] * qv)[None], tgt)
+    tgt[:] = np.where(mv0[None], (fq(corioq[Jv0, sl(1, ii + 1)], qv))[None], tgt)
     tgt = pv_[:, Jv0, Iv0]
-    tgt[:] = np.where(mv0[None], (corioq[Jv0, Iv0] * qv)[None], tgt)
+    tgt[:] = np.where(mv0[None], (fq(corioq[Jv0, Iv0], qv))[None], tgt)
     mq = iq[J, I] > 0
     with np.errstate(divide="ignore", invalid="ignore"):
         qq = corioq[J, I] * 4. / (pb_p[0, J, I] + pb_p[0, J, Im] + pb_p[0, Jm, I] + pb_p[0, Jm, Im])
