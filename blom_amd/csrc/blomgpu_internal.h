@@ -455,6 +455,7 @@ struct blomgpu_ctx {
   double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
   DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
   std::vector<double> dia_edges;               // blomgpu_dia_set_levels: the ddm + 1 edges of the depth levels; empty: the 35-level table
+  std::vector<double> dia_sigdia;              // blomgpu_dia_set_sigdia: the kk diagnostic density classes; empty: none (a class name is refused)
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space
@@ -547,6 +548,9 @@ int dia_finalize(blomgpu_ctx *);
 int dia_nacc(blomgpu_ctx *, int *nacc);
 int dia_get(blomgpu_ctx *, const char *name, double *out);
 int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
+int dia_name_all(int index, char *buf, int cap, int *kind, int *grid);
+int dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
+int dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
 int dia_set_levels(blomgpu_ctx *, const double *bnds, int ddm);
 int dia_levels_levitus2x(blomgpu_ctx *);
 int dia_get_levels(blomgpu_ctx *, double *bnds, int cap, int *ddm);

@@ -14,13 +14,17 @@
 //
 // The z-level (Levitus) accumulators -- diazlv (:4737-4993) + acclvl (:5709-5781), called per layer from diaacc (:2000-2053,
 // :2119-2168, :2222-2271) -- are k_dialvl further down: one thread per column of a grid, one launch per grid with a selected name.
+//
+// The mass fluxes binned into the diagnostic density classes sigdia (:1368-1538) are k_diasig at the end of the kernels: one thread
+// per column of the u- or v-grid, the classes' bins of the step in LDS.  The first family that communicates: the one-point halo of
+// sigint is exchanged in front of it (:1392).
 #include "../../include/blomgpu.h"
 #include "blomgpu_internal.h"
 #include <cstring>
 
 namespace {
 enum { G_P = 0, G_U = 1, G_V = 2 };                 // the grid = the bit of mpack that masks it
-enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4 };   // the last two: acclvl with diazlv's weights | weightsflx
+enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4, OP_CLS = 5 };   // acclvl with diazlv's weights | weightsflx; the density classes
 enum { W_NONE = 0, W_DP = 1, W_DPU = 2, W_DPV = 3 };       // weight (km); also: the register a source is taken from
 enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src + ub(m) | src + vb(m) | src + a second plane | src*onem
 // the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
@@ -30,14 +34,16 @@ constexpr double ONEM = 9806.;                      // phy/mod_constants.F90
 constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948)
 constexpr double EPSIL = 1.e-11, NF90_FILL_DOUBLE = 9.9692099683868690e+36;   // finlyr, :6126, :6140
 constexpr double EPSILP = 1.e-12;                   // phy/mod_constants.F90:43
+constexpr double SIGEPS = 1.e-9;                    // phy/mod_dia.F90:1120
 constexpr double DZEPS = 1e1 * EPSILP, DPEPS = 1e5 * EPSILP, FLXEPS = 1e5 * EPSILP;   // diazlv, :4760-4762
 
 // One row per accumulator; the name is the reference's ACC_* suffix in lower case, `line` the call in phy/mod_dia.F90.
-struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; };   // lyr: 0 2-D, 1 kk layers, 2 ddm depth levels
+struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; };   // lyr: 0 2-D, 1 kk layers, 2 ddm depth levels, 3 kk density classes
 #define H2D(nm, g, f, lv, ln) {#nm, 0, g, OP_SUM, f, lv, W_NONE, A_NONE, ln}
 #define LYR(nm, g, f, lv, w, ln) {#nm, 1, g, OP_SUM, f, lv, w, A_NONE, ln}
 #define LVF(nm, g, f, ln) {#nm, 2, g, OP_LVLFLX, f, LV_NN, W_NONE, A_NONE, ln}
 #define LVP(nm, f, lv, ln) {#nm, 2, G_P, OP_LVL, f, lv, W_NONE, A_NONE, ln}
+#define CLS(nm, g, f, ln) {#nm, 3, g, OP_CLS, f, LV_NN, W_NONE, A_NONE, ln}
 const DiaRow g_rows[] = {
   // ---- acch2d, :1547-1745 ----
   H2D(ub, G_U, F_ub, LV_M, 1547), H2D(ubflxs, G_U, F_ubflxs, LV_N, 1550), H2D(taux, G_U, F_taux, LV_0, 1556),
@@ -89,12 +95,17 @@ const DiaRow g_rows[] = {
   LVP(salnlvl, F_saln, LV_MM, 2233), LVP(templvl, F_temp, LV_MM, 2236), LVP(bfsqlvl, F_bfsql, LV_0, 2239),
   LVP(difintlvl, F_difint, LV_0, 2242), LVP(difisolvl, F_difiso, LV_0, 2245), LVP(difdialvl, F_difdia, LV_0, 2248),
   LVP(tkelvl, F_trc, LV_TKE, 2264), LVP(gls_psilvl, F_trc, LV_GLS, 2267), LVP(dzlvl, F_dz, LV_0, 2271),
+  // ---- the density classes, :1368-1538: acclyr of the step's bins.  Enumerated by blomgpu_dia_name_all only ----
+  CLS(umfll, G_U, F_uflx, 1457), CLS(umfltdl, G_U, F_umfltd, 1461), CLS(umflsml, G_U, F_umflsm, 1465),
+  CLS(vmfll, G_V, F_vflx, 1530), CLS(vmfltdl, G_V, F_vmfltd, 1534), CLS(vmflsml, G_V, F_vmflsm, 1538),
 };
 #undef H2D
 #undef LYR
 #undef LVF
 #undef LVP
+#undef CLS
 constexpr int NROW = (int)(sizeof(g_rows) / sizeof(g_rows[0]));
+constexpr int NROW_CLS = 6, NROW_NAMED = NROW - NROW_CLS;      // blomgpu_dia_name stops in front of the class rows
 
 // depthslev_bnds as its ddm + 1 edges: bnds(1,d) = edge[d-1], bnds(2,d) = edge[d] (:119-128; with LEVITUS2X :142-159)
 const double g_edges35[] = {0., 5., 15., 25., 40., 62.5, 87.5, 112.5, 137.5, 175., 225., 275., 350., 450., 550., 650., 750., 850., 950., 1050.,
@@ -122,6 +133,8 @@ struct DiaState {
   bool needs_z = false;         // a selected row reads z or dz (cmnfld1's output)
   int ddm = 0;                  // levels of a depth-level slot; 0: none selected.  Their ddm + 1 edges lie behind the last plane of `acc`
   double *edges() const { return acc + nplanes * np; }
+  int ncls = 0;                 // selected density-class slots; their kk class densities lie behind the edges
+  double *sigdia() const { return edges() + (ddm ? ddm + 1 : 0); }
   size_t np = 0;
   int slot_of(int row) const {
     for (size_t s = 0; s < rows.size(); s++)
@@ -406,6 +419,133 @@ __global__ __launch_bounds__(256) void k_dia_msklvl(const DevView *__restrict__ 
   }
 }
 
+// ---- the density classes: :1368-1538 ---------------------------------------------------------------------------------------------
+// sigint at the owned p-points under isopyc_bulkml (:1372-1390): sigma(k1m) | .5*(sigma(km-1) + sigma(km)); nothing elsewhere
+__global__ __launch_bounds__(256) void k_diasig_int(const DevView *__restrict__ Vp, int mm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, k = by;
+  if (t >= V.nplane || k >= V.kk) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj || !(V.m[I_mpack][t] & 1)) return;
+  gcd_t sg = V.f[F_sigma] + ((size_t)t + (size_t)(mm + k) * V.nplane);
+  gd_t si = V.f[F_sigint];
+  const double lo = sg[0];
+  const double up = sg[k ? -(ptrdiff_t)V.nplane : 0];
+  si[(size_t)t + (size_t)k * V.nplane] = k == 0 ? lo : .5 * (up + lo);
+}
+
+// One thread per owned, masked column of grid G (u | v), one wave per block, one slot per blockIdx.y (a grid has <= 3): the kk bins
+// of the step (tmp3d, :1394 | :1467) live in LDS as [bin][lane] -- every lane has its own bank pair, and the bin is the lane's own
+// kup.  The class densities sit in LDS beside them.  KCAP >= kk fixes the static LDS of an instance: (KCAP*64 + KCAP) doubles.
+// The walk is :1398-1453 | :1471-1526 line for line: kup carried down the column from 2, the two-branch search with its exits, the
+// klo search against sigdia(klo) + sigeps, q = 1/(sigmax - sigmin), three pieces or the whole flux.  Then acclyr (:5500): acc =
+// acc + tmp for ALL k.  sigup of layer k + 1 is siglo of layer k (the same two loads, the same operations) and is carried; the
+// interface pair and the flux of the next DSG_KB layers are requested ahead.
+// Algorithmic bytes per grid: (2 + n_sel + 2 n_sel) kk planes; the dealing re-reads sigint per slot: (2 n_sel + n_sel + 2 n_sel).
+#define DSG_KB 2
+#define DSG_W 64
+#define DSG_MAXK 120
+struct SigTab { int n; int d[3][3]; };            // per slot: source field, plane of its layer 1 (nn), first plane of the slot
+template <int G, int KCAP>
+__global__ __launch_bounds__(DSG_W) void k_diasig(const DevView *__restrict__ Vp, double *__restrict__ accp, const double *__restrict__ sigdiap, const SigTab T) {
+  __shared__ double bins[KCAP * DSG_W], sd[KCAP];
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int lane = threadIdx.x, t = bx * DSG_W + lane;
+  const int kk = V.kk;
+  for (int k = lane; k < kk && k < KCAP; k += DSG_W) sd[k] = global_ptr(sigdiap)[k];
+  __syncthreads();
+  bool on = t < V.nplane && (int)by < T.n && kk <= KCAP;
+  if (on) {
+    const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+    on = i >= 1 && i <= V.ii && j >= 1 && j <= V.jj && ((V.m[I_mpack][t] >> G) & 1);
+  }
+  if (!on) return;
+  const size_t np = V.nplane, c = t, cn = c - (G == G_U ? (size_t)1 : (size_t)V.ni);   // the western | southern p-point
+  gcd_t sg = V.f[F_sigint];
+  gcd_t src = V.f[T.d[by][0]] + (c + (size_t)T.d[by][1] * np);
+  gd_t acc = global_ptr(accp) + (c + (size_t)T.d[by][2] * np);
+  double *bin = bins + lane;
+  for (int k = 0; k < kk; k++) bin[k * DSG_W] = 0.;                 // tmp3d(:,:,:) = 0.
+  double a0 = sg[c], b0 = sg[cn];
+  double aq[DSG_KB], bq[DSG_KB], fq[DSG_KB];
+#pragma unroll
+  for (int u = 0; u < DSG_KB; u++) {
+    const size_t o = (size_t)(1 + u < kk ? 1 + u : kk - 1) * np;
+    aq[u] = sg[c + o];
+    bq[u] = sg[cn + o];
+    fq[u] = src[(size_t)(u < kk ? u : kk - 1) * np];
+  }
+  int kup = 2;
+  for (int k = 0; k < kk; k++) {
+    const double a1 = aq[0], b1 = bq[0], f = fq[0];
+#pragma unroll
+    for (int u = 0; u + 1 < DSG_KB; u++) { aq[u] = aq[u + 1]; bq[u] = bq[u + 1]; fq[u] = fq[u + 1]; }
+    {
+      const size_t o = (size_t)(k + 1 + DSG_KB < kk ? k + 1 + DSG_KB : kk - 1) * np;
+      aq[DSG_KB - 1] = sg[c + o];
+      bq[DSG_KB - 1] = sg[cn + o];
+      fq[DSG_KB - 1] = src[(size_t)(k + DSG_KB < kk ? k + DSG_KB : kk - 1) * np];
+    }
+    const double sigup = .5 * (b0 + a0), siglo = .5 * (b1 + a1);   // :1406-1407 | :1479-1480 (level min(kk, k+1): the queue clamps)
+    a0 = a1;
+    b0 = b1;
+    const double sigmin = fmin2(sigup, siglo), sigmax = fmax2(sigup, siglo);
+    // sigdia(x) = sd[x - 1]; kup, klo are the reference's 1-based indices
+    if (sigmin > sd[kup - 2]) {
+      while (sigmin > sd[kup - 1]) {
+        if (kup == kk) break;
+        kup++;
+      }
+    } else {
+      for (;;) {
+        if (kup == 2) break;
+        if (sigmin > sd[kup - 2]) break;
+        kup--;
+      }
+    }
+    int klo = kup;
+    while (sigmax > sd[klo - 1] + SIGEPS) {
+      if (klo == kk) break;
+      klo++;
+    }
+    if (kup < klo) {
+      const double q = 1. / (sigmax - sigmin);
+      double w = (sd[kup - 1] - sigmin) * q;
+      bin[(kup - 2) * DSG_W] = bin[(kup - 2) * DSG_W] + w * f;
+      for (int kt = kup; kt <= klo - 2; kt++) {
+        w = (sd[kt] - sd[kt - 1]) * q;
+        bin[(kt - 1) * DSG_W] = bin[(kt - 1) * DSG_W] + w * f;
+      }
+      w = (sigmax - sd[klo - 2]) * q;
+      bin[(klo - 2) * DSG_W] = bin[(klo - 2) * DSG_W] + w * f;
+    } else {
+      bin[(kup - 2) * DSG_W] = bin[(kup - 2) * DSG_W] + f;
+    }
+  }
+  // acclyr, op 0 (:5500): every class, touched or not
+  for (int k0 = 0; k0 < kk; k0 += COLUMN_U) {
+    double v[COLUMN_U];
+#pragma unroll
+    for (int u = 0; u < COLUMN_U; u++) v[u] = acc[(size_t)(k0 + u < kk ? k0 + u : kk - 1) * np];
+#pragma unroll
+    for (int u = 0; u < COLUMN_U; u++)
+      if (k0 + u < kk) acc[(size_t)(k0 + u) * np] = v[u] + bin[(k0 + u) * DSG_W];
+  }
+}
+
+template <int G>
+static void launch_diasig(blomgpu_ctx *c, DiaState *S, const SigTab &T) {
+  const int kk = c->h.kk;
+  const dim3 grid = plane_grid(c->h, T.n, DSG_W);
+  if (kk <= 32) hipLaunchKernelGGL((k_diasig<G, 32>), grid, dim3(DSG_W), 0, c->stream, c->d, S->acc, S->sigdia(), T);
+  else if (kk <= 56) hipLaunchKernelGGL((k_diasig<G, 56>), grid, dim3(DSG_W), 0, c->stream, c->d, S->acc, S->sigdia(), T);
+  else hipLaunchKernelGGL((k_diasig<G, DSG_MAXK>), grid, dim3(DSG_W), 0, c->stream, c->d, S->acc, S->sigdia(), T);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static int dia_init(blomgpu_ctx *c, DiaState *S) {
   DiaIni T;
@@ -413,7 +553,7 @@ static int dia_init(blomgpu_ctx *c, DiaState *S) {
   int maxlev = 1;
   for (size_t s = 0; s < S->rows.size(); s++) {
     const DiaRow &r = g_rows[S->rows[s]];
-    const int nl = r.lyr == 2 ? S->ddm : r.lyr ? c->h.kk : 1;
+    const int nl = r.lyr == 2 ? S->ddm : r.lyr ? c->h.kk : 1;          // (kk for the layers and the density classes)
     T.d[T.n][0] = S->plane0[s]; T.d[T.n][1] = nl; T.d[T.n][2] = r.grid | (r.op == OP_MAX) << 2;
     T.n++;
     if (nl > maxlev) maxlev = nl;
@@ -444,6 +584,8 @@ static bool hybrid_remapped(int r) {       // the level rows the hybrid coordina
 }
 
 int dia_step_check(blomgpu_ctx *c) {
+  if (c->dia && c->dia->ncls && c->h.P.vcoord_tag == 3)
+    return ctx_fail(c, "blomgpu_step: a density-class accumulator is selected, which reads sigint; vcoord_type = 'plevel' never writes it");
   if (c->dia && c->h.P.vcoord_tag != 1)
     for (int r : c->dia->rows)
       if (hybrid_remapped(r))
@@ -479,6 +621,14 @@ int dia_select(blomgpu_ctx *c, const char *names) {
       return ctx_fail(c, "blomgpu_dia_select: " + nm + ": itrtke / itrgls outside 1..ntr");
     if (c->h.P.vcoord_tag != 1 && hybrid_remapped(r))
       return ctx_fail(c, "blomgpu_dia_select: " + nm + " is formed inside ale_regrid_remap under cntiso_hybrid / plevel (phy/mod_dia.F90:1944, :2059, :2174 leave it out): not built");
+    if (g_rows[r].lyr == 3) {
+      if (c->dia_sigdia.empty())
+        return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the diagnostic density classes sigdia (blomgpu_dia_set_sigdia)");
+      if (c->h.P.vcoord_tag == 3)
+        return ctx_fail(c, "blomgpu_dia_select: " + nm + " reads sigint, which vcoord_type = 'plevel' never writes (phy/mod_vcoord.F90:1059: it stays spval)");
+      if ((int)c->dia_sigdia.size() != c->h.kk || c->h.kk < 2 || c->h.kk > DSG_MAXK)
+        return ctx_fail(c, "blomgpu_dia_select: " + nm + ": the density classes need 2 <= kdm <= " + std::to_string(DSG_MAXK) + " and a sigdia of kdm values");
+    }
     want[r] = 1;
     any = true;
   }
@@ -494,19 +644,20 @@ int dia_select(blomgpu_ctx *c, const char *names) {
     const std::vector<double> edges = c->dia_edges.empty() ? std::vector<double>(g_edges35, g_edges35 + 36) : c->dia_edges;
     S->np = c->h.nplane;
     S->ddm = nlv ? (int)edges.size() - 1 : 0;
-    for (int pass = 0; pass < 3; pass++)
+    for (int pass = 0; pass < 4; pass++)
       for (int r = 0; r < NROW; r++)
         if (want[r] && g_rows[r].lyr == pass) {
           S->rows.push_back(r);
           S->plane0.push_back((int)S->nplanes);
           S->nplanes += pass == 2 ? S->ddm : pass ? c->h.kk : 1;
           if (pass < 2) (pass ? nly : n2d)++;
+          if (pass == 3) S->ncls++;
           if (g_rows[r].src == F_z || g_rows[r].src == F_dz) S->needs_z = true;
         }
     if (n2d > DIA_MAXSLOT || nly > DIA_MAXSLOT) { delete S; return ctx_fail(c, "blomgpu_dia_select: more slots than a launch carries"); }
     (void)hipSetDevice(c->device);
-    // (the edges of the depth levels lie behind the last plane)
-    if (hipMalloc((void **)&S->acc, sizeof(double) * (S->nplanes * (size_t)c->h.nplane + (S->ddm ? S->ddm + 1 : 0))) != hipSuccess) {
+    // (the edges of the depth levels lie behind the last plane, the density classes behind them)
+    if (hipMalloc((void **)&S->acc, sizeof(double) * (S->nplanes * (size_t)c->h.nplane + (S->ddm ? S->ddm + 1 : 0) + (S->ncls ? c->h.kk : 0))) != hipSuccess) {
       (void)hipGetLastError();
       const size_t mb = sizeof(double) * S->nplanes * (size_t)c->h.nplane >> 20;
       delete S;
@@ -517,6 +668,12 @@ int dia_select(blomgpu_ctx *c, const char *names) {
       (void)hipFree(S->acc);
       delete S;
       return ctx_fail(c, "blomgpu_dia_select: the depth levels could not be copied to the device");
+    }
+    if (S->ncls && hipMemcpy(S->sigdia(), c->dia_sigdia.data(), sizeof(double) * c->dia_sigdia.size(), hipMemcpyHostToDevice) != hipSuccess) {
+      (void)hipGetLastError();
+      (void)hipFree(S->acc);
+      delete S;
+      return ctx_fail(c, "blomgpu_dia_select: the density classes could not be copied to the device");
     }
     if (dia_init(c, S)) { (void)hipFree(S->acc); delete S; return 1; }
   }
@@ -545,13 +702,16 @@ int dia_get(blomgpu_ctx *c, const char *name, double *out) {
   return 0;
 }
 
-int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) {
+int dia_name_all(int index, char *buf, int cap, int *kind, int *grid) {
   if (index < 0 || index >= NROW || !buf || cap < 2) return 1;
   snprintf(buf, cap, "%s", g_rows[index].name);
-  if (is_lyr) *is_lyr = g_rows[index].lyr;
+  if (kind) *kind = g_rows[index].lyr;
   if (grid) *grid = g_rows[index].grid;
   return 0;
 }
+
+// (the 2-D, layer and depth-level rows: where the table ended before the density classes)
+int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) { return index >= NROW_NAMED ? 1 : dia_name_all(index, buf, cap, is_lyr, grid); }
 
 // finlyr for the weighted layer pairs of :2597-2611; the table holds no weighted 2-D row (finh2d's are the ice fields, :2591-2594)
 int dia_finalize(blomgpu_ctx *c) {
@@ -606,12 +766,63 @@ int dia_get_levels(blomgpu_ctx *c, double *bnds, int cap, int *ddm) {
   return 0;
 }
 
+// ---- the density classes (blomgpu_dia_set_sigdia): kk values kept in the context, copied to the device with a selection -----------
+int dia_set_sigdia(blomgpu_ctx *c, const double *sigdia, int n) {
+  const bool selected = c->dia && c->dia->ncls;
+  const char *held = "blomgpu_dia_set_sigdia: a density-class accumulator is selected; deselect the class names first";
+  if (!sigdia && n == 0) {
+    if (selected) return ctx_fail(c, held);
+    c->dia_sigdia.clear();
+    return 0;
+  }
+  if (!sigdia || n != c->h.kk) return ctx_fail(c, "blomgpu_dia_set_sigdia: sigdia and n == kdm = " + std::to_string(c->h.kk) + ", or NULL and 0 to clear the table");
+  for (int k = 0; k < n; k++)
+    if (!(sigdia[k] - sigdia[k] == 0.)) return ctx_fail(c, "blomgpu_dia_set_sigdia: sigdia(" + std::to_string(k + 1) + ") is not finite");
+  if (selected) return ctx_fail(c, held);
+  c->dia_sigdia.assign(sigdia, sigdia + n);        // otherwise as given: the reference checks nothing (phy/mod_vcoord.F90:978-1005, :1103)
+  return 0;
+}
+
+int dia_get_sigdia(blomgpu_ctx *c, double *out, int cap, int *n) {
+  if (!n) return ctx_fail(c, "blomgpu_dia_get_sigdia: null argument");
+  *n = (int)c->dia_sigdia.size();
+  for (int k = 0; out && k < *n && k < cap; k++) out[k] = c->dia_sigdia[k];
+  return 0;
+}
+
 // the accumulation of one step (without the count: blomgpu_diaacc and blomgpu_step add it, a graph capture must not)
 int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   (void)k1m; (void)k1n;
   DiaState *S = c->dia;
   if (!S) return 0;
   const DevView &h = c->h;
+  // the density classes, in the reference's position (:1368-1538, in front of acch2d): sigint at the owned points under isopyc_bulkml
+  // (cntiso_hybrid: what ale_regrid_remap left, stage_ale.hip), its one-point halo, then one launch per grid with a selected name
+  if (S->ncls) {
+    if (h.P.vcoord_tag == 3) return ctx_fail(c, "diaacc: a density-class accumulator is selected, which reads sigint; vcoord_type = 'plevel' never writes it");
+    if (h.P.vcoord_tag == 1) {
+      TimeScope ts(c, "diasig_int");
+      hipLaunchKernelGGL(k_diasig_int, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, mm);
+      HIPCHK(c, hipGetLastError());
+    }
+    if (int rc = st_xctilr(c, h.f[F_sigint], 1, h.kk, 1, 1, 1)) return rc;          // xctilr(sigint,1,kk, 1,1, halo_ps), :1392
+    for (int g = G_U; g <= G_V; g++) {
+      SigTab T;
+      T.n = 0;
+      memset(T.d, 0, sizeof(T.d));
+      for (size_t s = 0; s < S->rows.size(); s++) {
+        const DiaRow &r = g_rows[S->rows[s]];
+        if (r.lyr != 3 || r.grid != g) continue;
+        int *d = T.d[T.n++];
+        d[0] = r.src; d[1] = nn; d[2] = S->plane0[s];
+      }
+      if (!T.n) continue;
+      TimeScope ts(c, g == G_U ? "diasig_u" : "diasig_v");
+      if (g == G_U) launch_diasig<G_U>(c, S, T);
+      else launch_diasig<G_V>(c, S, T);
+      HIPCHK(c, hipGetLastError());
+    }
+  }
   for (int pass = 1; pass >= 0; pass--) {
     DiaTab T;
     T.n = 0; T.need = 0; T.lyr = pass; T.mlev = m - 1;

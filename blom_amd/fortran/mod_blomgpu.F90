@@ -120,6 +120,17 @@ module mod_blomgpu
       integer(c_int), value :: cap
       integer(c_int), intent(out) :: ddm
     end function
+    integer(c_int) function blomgpu_dia_set_sigdia(c, sigdia, n) bind(C, name='blomgpu_dia_set_sigdia')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, sigdia
+      integer(c_int), value :: n
+    end function
+    integer(c_int) function blomgpu_dia_get_sigdia(c, sigdia, cap, n) bind(C, name='blomgpu_dia_get_sigdia')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, sigdia
+      integer(c_int), value :: cap
+      integer(c_int), intent(out) :: n
+    end function
     integer(c_int) function blomgpu_field_info(c, name, nlev, isint) bind(C, name='blomgpu_field_info')
       import :: c_ptr, c_int, c_char
       type(c_ptr), value :: c
@@ -236,6 +247,7 @@ module mod_blomgpu
             cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc
   public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
+  public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
   interface gpu_set
     module procedure gpu_set_real, gpu_set_int, gpu_set_str
@@ -583,6 +595,24 @@ contains
     integer(c_int) :: v
     call gpu_check(blomgpu_dia_get_levels(ctx, c_loc(bnds), int(cap, c_int), v), 'gpu_dia_get_levels')
     ddm = v
+  end subroutine
+  ! the diagnostic density classes sigdia(kdm) (phy/mod_vcoord.F90:978-1005) of the class names umfll umfltdl umflsml vmfll vmfltdl
+  ! vmflsml (phy/mod_dia.F90:1368-1538); before the selection, refused while a class name is selected
+  subroutine gpu_dia_set_sigdia(sigdia, n)
+    integer, intent(in) :: n
+    real(8), intent(in), target :: sigdia(n)
+    call gpu_check(blomgpu_dia_set_sigdia(ctx, c_loc(sigdia), int(n, c_int)), 'gpu_dia_set_sigdia')
+  end subroutine
+  subroutine gpu_dia_clear_sigdia()
+    call gpu_check(blomgpu_dia_set_sigdia(ctx, c_null_ptr, 0_c_int), 'gpu_dia_clear_sigdia')
+  end subroutine
+  subroutine gpu_dia_get_sigdia(sigdia, cap, n) ! n (0: no table), and the first min(cap, n) values
+    integer, intent(in) :: cap
+    real(8), intent(out), target :: sigdia(cap)
+    integer, intent(out) :: n
+    integer(c_int) :: v
+    call gpu_check(blomgpu_dia_get_sigdia(ctx, c_loc(sigdia), int(cap, c_int), v), 'gpu_dia_get_sigdia')
+    n = v
   end subroutine
   integer function gpu_dia_nacc()               ! nacc_phy
     integer(c_int) :: v

@@ -221,6 +221,16 @@ class BlomGpu:
             k += 1
         return rows
 
+    def dia_names_all(self):
+        """the whole table: the rows of dia_names() in their order, then the six density-class rows (kind 3: kdm classes) --
+        blomgpu_dia_name_all"""
+        rows, buf, k = [], C.create_string_buffer(32), 0
+        kind, grid = C.c_int(0), C.c_int(0)
+        while self.lib.blomgpu_dia_name_all(k, buf, 32, C.byref(kind), C.byref(grid)) == 0:
+            rows.append((buf.value.decode(), kind.value, "puv"[grid.value]))
+            k += 1
+        return rows
+
     def dia_select(self, names):
         """replace the selection (a blank-separated string or a list of names; empty: none) -- blomgpu_dia_select"""
         if not isinstance(names, str):
@@ -238,10 +248,10 @@ class BlomGpu:
     def dia_get(self, name):
         """the accumulator as get() would return a field: (1 | kdm | ddm, nj, ni)"""
         if not hasattr(self, "_dia_lyr"):
-            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names()}
+            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names_all()}
         if name not in self._dia_lyr:
             raise KeyError(name)
-        nlev = (1, self.kdm, len(self.dia_levels()))[self._dia_lyr[name]]
+        nlev = (1, self.kdm, len(self.dia_levels()), self.kdm)[self._dia_lyr[name]]
         a = np.empty((nlev, self.nj, self.ni), dtype=np.float64)
         self._chk(self.lib.blomgpu_dia_get(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p)))
         return a
@@ -269,6 +279,22 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_dia_get_levels(self.ctx, None, 0, C.byref(ddm)))
         a = np.empty((ddm.value, 2), dtype=np.float64)
         self._chk(self.lib.blomgpu_dia_get_levels(self.ctx, a.ctypes.data_as(C.c_void_p), ddm, C.byref(ddm)))
+        return a
+
+    def dia_set_sigdia(self, sigdia=None):
+        """the kdm diagnostic density classes of the class names (umfll ...), None to clear the table -- blomgpu_dia_set_sigdia"""
+        if sigdia is None:
+            self._chk(self.lib.blomgpu_dia_set_sigdia(self.ctx, None, 0))
+        else:
+            a = np.ascontiguousarray(sigdia, dtype=np.float64).ravel()
+            self._chk(self.lib.blomgpu_dia_set_sigdia(self.ctx, a.ctypes.data_as(C.c_void_p), C.c_int(a.size)))
+
+    def dia_sigdia(self):
+        """the density classes in force, (kdm,), or an empty array without a table -- blomgpu_dia_get_sigdia"""
+        n = C.c_int(0)
+        self._chk(self.lib.blomgpu_dia_get_sigdia(self.ctx, None, 0, C.byref(n)))
+        a = np.empty(n.value, dtype=np.float64)
+        self._chk(self.lib.blomgpu_dia_get_sigdia(self.ctx, a.ctypes.data_as(C.c_void_p), n, C.byref(n)))
         return a
 
     # -- tile decomposition ---------------------------------------------------------------

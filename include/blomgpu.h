@@ -229,7 +229,21 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  *   contiguous (bnds[d][1] == bnds[d+1][0]), ddm <= 128; otherwise, or while a level name is selected, it fails with a message and
  *   changes nothing.  bnds == NULL with ddm == 0 restores the default, the 35 levels of :111-128.
  * blomgpu_dia_levels_levitus2x: the 70 levels of LEVITUS2X (:130-159); refused while a level name is selected.
- * blomgpu_dia_get_levels: *ddm, and the first min(cap, ddm) rows of the bounds into bnds (may be NULL). */
+ * blomgpu_dia_get_levels: *ddm, and the first min(cap, ddm) rows of the bounds into bnds (may be NULL).
+ *
+ * Density-class names (6, kind 3; :1368-1538): the mass fluxes binned into the diagnostic density classes sigdia with THAT step's
+ *   interface densities and a search index carried down the column -- "umfll umfltdl umflsml" on u (acclyr :1457, :1461, :1465;
+ *   sources uflx, umfltd, umflsm at k + nn) and "vmfll vmfltdl vmflsml" on v (:1530, :1534, :1538; vflx, vmfltd, vmflsm).  kdm
+ *   planes each, unweighted: they add no dependencies (diaini :627-658 adds none), blomgpu_dia_get returns kdm planes and
+ *   blomgpu_dia_finalize leaves them as they are (finlyr's list :2597-2611 does not hold them).  A class name needs a sigdia table
+ *   and is refused without one; it is refused under vcoord_type = 'plevel', where nothing writes sigint.  Under isopyc_bulkml the
+ *   stage writes sigint at the owned p-points (:1372-1390), under cntiso_hybrid it takes the sigint ale_regrid_remap left; both
+ *   exchange its one-point halo (:1392).  blomgpu_dia_name does NOT enumerate these rows:
+ * blomgpu_dia_name_all: the whole table -- the 111 rows of blomgpu_dia_name in their order, then the six class rows with kind 3.
+ * blomgpu_dia_set_sigdia: the kdm class densities (n == kdm; the reference's sigdia, taken as given as mod_vcoord.F90:978-1005
+ *   does).  NULL with n == 0 clears the table.  A wrong n, a non-finite value, or a call while a class name is selected fails with
+ *   a message and changes nothing.
+ * blomgpu_dia_get_sigdia: *n (0: no table), and the first min(cap, n) values into out (may be NULL). */
 int  blomgpu_dia_select(blomgpu_ctx *, const char *names);
 int  blomgpu_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int  blomgpu_dia_nacc(blomgpu_ctx *, int *nacc);
@@ -240,6 +254,9 @@ int  blomgpu_dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
 int  blomgpu_dia_set_levels(blomgpu_ctx *, const double *bnds /* [ddm][2] */, int ddm);
 int  blomgpu_dia_levels_levitus2x(blomgpu_ctx *);
 int  blomgpu_dia_get_levels(blomgpu_ctx *, double *bnds /* [cap][2] */, int cap, int *ddm);
+int  blomgpu_dia_name_all(int index, char *buf, int cap, int *kind, int *grid);
+int  blomgpu_dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
+int  blomgpu_dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
 
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
