@@ -642,6 +642,7 @@ int blomgpu_dia_set_levels(blomgpu_ctx *c, const double *bnds, int ddm) { return
 int blomgpu_dia_levels_levitus2x(blomgpu_ctx *c) { return dia_levels_levitus2x(c); }
 int blomgpu_dia_get_levels(blomgpu_ctx *c, double *bnds, int cap, int *ddm) { return dia_get_levels(c, bnds, cap, ddm); }
 int blomgpu_dia_name_all(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_all(index, buf, cap, kind, grid); }
+int blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_full(index, buf, cap, kind, grid); }
 int blomgpu_dia_set_sigdia(blomgpu_ctx *c, const double *sigdia, int n) { return dia_set_sigdia(c, sigdia, n); }
 int blomgpu_dia_get_sigdia(blomgpu_ctx *c, double *out, int cap, int *n) { return dia_get_sigdia(c, out, cap, n); }
 // sfcstr, phy/mod_sfcstr.F90:33-62: the surface stress of the idealised experiments is set at initialisation
@@ -897,7 +898,7 @@ static int step_sequence(STAGE_ARGS) {
     if (int rc = stage(S_cmnfld1)) return rc;                               // phy/mod_blom_step.F90:233
   // diaacc (:239) with a selection: on the context's stream, behind everything the step put on the second one (the last of it
   // is joined in front of pbcor2).  Its sources are arrays of the finished step; the tmsmt1 that tmsmt_ahead folded into tmsmt2
-  // wrote *old arrays only.  blomgpu_step counts the step (a capture passes here without executing)
+  // wrote *old arrays only (diavfl reads dpold: with its group selected nothing is folded, blomgpu_step).  blomgpu_step counts the step (a capture passes here without executing)
   if (dia_active(c)) return st_diaacc(ALL6);
   return 0;
 }
@@ -917,7 +918,9 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     const int mm = (m - 1) * kk, nn = (n - 1) * kk, k1m = 1 + mm, k1n = 1 + nn;
     c->h.P.nstep = ns + 1;                             // read by host code only: no upload of the view for it
     ctx_sync_view(c);
-    c->tmsmt1_ahead = !c->use_graph && !c->csdiag && it < nsteps - 1 && c->tmsmt_ahead;
+    // (not while diavfl's group is selected: its dp(km) - dpold(km) needs the dpold the PREVIOUS step's tmsmt1 left, and the fold
+    // would have tmsmt2 overwrite it in front of diaacc.  The cost of the launch it brings back: DESIGN 3.13)
+    c->tmsmt1_ahead = !c->use_graph && !c->csdiag && it < nsteps - 1 && c->tmsmt_ahead && !dia_reads_dpold(c);
     // (the hybrid-coordinate sequence too: the engine's status of ale_regrid_remap stays on the device until the check below)
     bool graph = c->use_graph && !c->timing && !c->tiling.multi() && c->steps_warm >= 2;
     hipGraphExec_t &ge = c->step_graph[ns & 1];

@@ -415,9 +415,17 @@ int ctx_locate_ptr(const blomgpu_ctx *c, const double *p, size_t *offset) {
   // the kk-level work space (stages that hand their result to the next one through it update its halos too): id NF_REAL
   const size_t nw = (size_t)c->h.nwk * c->h.kk * c->h.nplane;
   if (c->h.wk && p >= c->h.wk && p < c->h.wk + nw) { *offset = (size_t)(p - c->h.wk); return NF_REAL; }
+  // the accumulators of diaacc (diavfl exchanges uflxlvl / vflxlvl, phy/mod_dia.F90:4681-4684): id NF_REAL + 1.  Tiles that step
+  // together hold the same selection, so a plane has the same number in every tile's allocation
+  size_t na = 0;
+  if (const double *b = dia_acc_span(c, &na))
+    if (p >= b && p < b + na) { *offset = (size_t)(p - b); return NF_REAL + 1; }
   return -1;
 }
-static inline double *located_base(const blomgpu_ctx *c, int fid) { return fid == NF_REAL ? c->h.wk : c->h.f[fid]; }
+static inline double *located_base(const blomgpu_ctx *c, int fid) {
+  size_t na = 0;
+  return fid == NF_REAL + 1 ? dia_acc_span(c, &na) : fid == NF_REAL ? c->h.wk : c->h.f[fid];
+}
 
 // closed / periodic rule of the global domain in each direction (phy/mod_xc.F90:4378,4400)
 static inline bool ew_periodic(int nreg) { return !(nreg == 0 || nreg == 4); }
@@ -444,6 +452,7 @@ static int xctilr_group(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl, i
     for (int q = 0; q < XCT_MAXTILES; q++) {
       const blomgpu_ctx *o = q < T.npx * T.npy ? G->tiles[(size_t)q] : nullptr;
       rt.p[q] = o ? located_base(o, fid) + lev * o->h.nplane : nullptr;
+      if (o && !located_base(o, fid)) return ctx_fail(c, "xctilr: a tile of the group does not hold the array that is exchanged (the same blomgpu_dia_select on every tile)");
       rt.i0[q] = o ? R.i0[q] : 0;
       rt.ii[q] = o ? R.ii[q] : 0;
     }
@@ -468,6 +477,7 @@ static int xctilr_group(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl, i
   for (int q = 0; q < XCT_MAXTILES; q++) {
     if (q >= T.npx * T.npy) { tab.p[q] = nullptr; continue; }
     const blomgpu_ctx *o = G->tiles[(size_t)q];
+    if (!located_base(o, fid)) return ctx_fail(c, "xctilr: a tile of the group does not hold the array that is exchanged (the same blomgpu_dia_select on every tile)");
     tab.p[q] = located_base(o, fid) + lev * o->h.nplane;
   }
   for (int q = 0; q <= XCT_MAXDIM; q++) tab.xoff[q] = tab.yoff[q] = 0;

@@ -18,13 +18,18 @@
 // The mass fluxes binned into the diagnostic density classes sigdia (:1368-1538) are k_diasig at the end of the kernels: one thread
 // per column of the u- or v-grid, the classes' bins of the step in LDS.  The first family that communicates: the one-point halo of
 // sigint is exchanged in front of it (:1392).
+//
+// The vertical mass flux and its square, on the layers and on the depth levels (diavfl, :4633-4733, called at :2279), are k_diavfl_lyr
+// and k_diavfl_lvl: the first family that reads a neighbour of a source, that exchanges accumulators between tiles (uflxlvl, vflxlvl,
+// :4681-4684), and that needs the dpold of the previous step (api.hip keeps tmsmt1 unfolded while it is selected).
 #include "../../include/blomgpu.h"
 #include "blomgpu_internal.h"
 #include <cstring>
 
 namespace {
 enum { G_P = 0, G_U = 1, G_V = 2 };                 // the grid = the bit of mpack that masks it
-enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4, OP_CLS = 5 };   // acclvl with diazlv's weights | weightsflx; the density classes
+enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4, OP_CLS = 5,     // acclvl with diazlv's weights | weightsflx; the density classes
+       OP_VFL = 6, OP_OLD = 7 };    // diavfl's own rows, and the two level slots it keeps last step's uflxlvl / vflxlvl in: no table-driven launch touches them
 enum { W_NONE = 0, W_DP = 1, W_DPU = 2, W_DPV = 3 };       // weight (km); also: the register a source is taken from
 enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src + ub(m) | src + vb(m) | src + a second plane | src*onem
 // the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
@@ -44,6 +49,7 @@ struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; }
 #define LVF(nm, g, f, ln) {#nm, 2, g, OP_LVLFLX, f, LV_NN, W_NONE, A_NONE, ln}
 #define LVP(nm, f, lv, ln) {#nm, 2, G_P, OP_LVL, f, lv, W_NONE, A_NONE, ln}
 #define CLS(nm, g, f, ln) {#nm, 3, g, OP_CLS, f, LV_NN, W_NONE, A_NONE, ln}
+#define VFL(nm, kind, g, op, f, ln) {#nm, kind, g, op, f, LV_NN, W_NONE, A_NONE, ln}
 const DiaRow g_rows[] = {
   // ---- acch2d, :1547-1745 ----
   H2D(ub, G_U, F_ub, LV_M, 1547), H2D(ubflxs, G_U, F_ubflxs, LV_N, 1550), H2D(taux, G_U, F_taux, LV_0, 1556),
@@ -98,14 +104,24 @@ const DiaRow g_rows[] = {
   // ---- the density classes, :1368-1538: acclyr of the step's bins.  Enumerated by blomgpu_dia_name_all only ----
   CLS(umfll, G_U, F_uflx, 1457), CLS(umfltdl, G_U, F_umfltd, 1461), CLS(umflsml, G_U, F_umflsm, 1465),
   CLS(vmfll, G_V, F_vflx, 1530), CLS(vmfltdl, G_V, F_vmfltd, 1534), CLS(vmflsml, G_V, F_vmflsm, 1538),
+  // ---- diavfl, :4633-4733: the vertical mass flux and its square on the layers and on the depth levels; one group (diaini :615-618,
+  // :644-647, :673-680).  Then ACC_UFLXOLD / ACC_VFLXOLD (:1921-1942), slots of the group that no name selects.  Enumerated by
+  // blomgpu_dia_name_full only ----
+  VFL(wflx, 1, G_P, OP_VFL, F_uflx, 4667), VFL(wflx2, 1, G_P, OP_VFL, F_uflx, 4669),
+  VFL(wflxlvl, 2, G_P, OP_VFL, F_uflx, 4722), VFL(wflx2lvl, 2, G_P, OP_VFL, F_uflx, 4724),
+  VFL(uflxold, 2, G_U, OP_OLD, F_uflx, 1928), VFL(vflxold, 2, G_V, OP_OLD, F_vflx, 1934),
 };
 #undef H2D
 #undef LYR
 #undef LVF
 #undef LVP
 #undef CLS
+#undef VFL
 constexpr int NROW = (int)(sizeof(g_rows) / sizeof(g_rows[0]));
-constexpr int NROW_CLS = 6, NROW_NAMED = NROW - NROW_CLS;      // blomgpu_dia_name stops in front of the class rows
+constexpr int NROW_CLS = 6, NROW_VFL = 6;
+constexpr int NROW_ALL = NROW - NROW_VFL;          // blomgpu_dia_name_all stops in front of diavfl's rows,
+constexpr int NROW_NAMED = NROW_ALL - NROW_CLS;    // blomgpu_dia_name in front of the class rows
+constexpr int KIND_INTERNAL = 4;                   // what blomgpu_dia_name_full reports for uflxold / vflxold: ddm levels, selected by the group only
 
 // depthslev_bnds as its ddm + 1 edges: bnds(1,d) = edge[d-1], bnds(2,d) = edge[d] (:119-128; with LEVITUS2X :142-159)
 const double g_edges35[] = {0., 5., 15., 25., 40., 62.5, 87.5, 112.5, 137.5, 175., 225., 275., 350., 450., 550., 650., 750., 850., 950., 1050.,
@@ -134,6 +150,7 @@ struct DiaState {
   int ddm = 0;                  // levels of a depth-level slot; 0: none selected.  Their ddm + 1 edges lie behind the last plane of `acc`
   double *edges() const { return acc + nplanes * np; }
   int ncls = 0;                 // selected density-class slots; their kk class densities lie behind the edges
+  bool vfl = false;             // diavfl's group is selected: wflx wflx2 wflxlvl wflx2lvl uflx vflx uflxlvl vflxlvl uflxold vflxold
   double *sigdia() const { return edges() + (ddm ? ddm + 1 : 0); }
   size_t np = 0;
   int slot_of(int row) const {
@@ -546,6 +563,114 @@ static void launch_diasig(blomgpu_ctx *c, DiaState *S, const SigTab &T) {
   else hipLaunchKernelGGL((k_diasig<G, DSG_MAXK>), grid, dim3(DSG_W), 0, c->stream, c->d, S->acc, S->sigdia(), T);
 }
 
+// ---- the vertical mass flux: diavfl, :4633-4733 -------------------------------------------------------------------------------------
+// Both kernels: one thread per owned wet p-column, i on the lanes, the sources of the next VFL_KB layers | levels requested ahead in
+// a queue of registers, every accumulator element read and written once.
+// k_diavfl_lyr (:4647-4676): wflx carried from k = kk up to k = 1,
+//   wflx = wflx - (uflx(i+1,kn) - uflx(i,kn) + vflx(j+1,kn) - vflx(j,kn)) - (dp(km) - dpold(km))*scp2      (km in the last term, as written)
+// evaluated left to right, then acc(k) = acc(k) + wflx and acc2(k) = acc2(k) + wflx**2 (a product).  uflx(ii+1) and vflx(jj+1) are
+// halo values that the step leaves equal to the neighbour's owned ones.
+// Algorithmic bytes: (4 + 4) kk planes (uflx, vflx, dp, dpold -- a face is read by the two columns it separates and comes from memory
+// once; two accumulators read and written).
+#define VFL_KB 2
+__global__ __launch_bounds__(256) void k_diavfl_lyr(const DevView *__restrict__ Vp, double *__restrict__ accp, int pw, int pw2, int mm, int nn) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj || !(V.m[I_mpack][t] & 1)) return;
+  const size_t np = V.nplane, c = t, ni = V.ni;
+  const int kk = V.kk;
+  gcd_t uf = V.f[F_uflx] + (c + (size_t)nn * np), vf = V.f[F_vflx] + (c + (size_t)nn * np);
+  gcd_t dp = V.f[F_dp] + (c + (size_t)mm * np), dpo = V.f[F_dpold] + (c + (size_t)mm * np);
+  gd_t a1 = global_ptr(accp) + (c + (size_t)pw * np), a2 = global_ptr(accp) + (c + (size_t)pw2 * np);
+  const double scp2 = V.f[F_scp2][c];
+  double ue[VFL_KB], uw[VFL_KB], vn[VFL_KB], vs[VFL_KB], dn[VFL_KB], dold[VFL_KB], q1[VFL_KB], q2[VFL_KB];
+#pragma unroll
+  for (int u = 0; u < VFL_KB; u++) {
+    const size_t o = (size_t)(kk - 1 - u > 0 ? kk - 1 - u : 0) * np;
+    ue[u] = uf[o + 1]; uw[u] = uf[o]; vn[u] = vf[o + ni]; vs[u] = vf[o];
+    dn[u] = dp[o]; dold[u] = dpo[o]; q1[u] = a1[o]; q2[u] = a2[o];
+  }
+  double wflx = 0.;
+  for (int k = kk - 1; k >= 0; k--) {
+    const double e = ue[0], w = uw[0], n_ = vn[0], s_ = vs[0], d = dn[0], dd = dold[0], x1 = q1[0], x2 = q2[0];
+#pragma unroll
+    for (int u = 0; u + 1 < VFL_KB; u++) {
+      ue[u] = ue[u + 1]; uw[u] = uw[u + 1]; vn[u] = vn[u + 1]; vs[u] = vs[u + 1];
+      dn[u] = dn[u + 1]; dold[u] = dold[u + 1]; q1[u] = q1[u + 1]; q2[u] = q2[u + 1];
+    }
+    {
+      const size_t o = (size_t)(k - VFL_KB > 0 ? k - VFL_KB : 0) * np;       // (layer 0 again at the end: in bounds, unused)
+      ue[VFL_KB - 1] = uf[o + 1]; uw[VFL_KB - 1] = uf[o]; vn[VFL_KB - 1] = vf[o + ni]; vs[VFL_KB - 1] = vf[o];
+      dn[VFL_KB - 1] = dp[o]; dold[VFL_KB - 1] = dpo[o];
+      if (k - VFL_KB >= 0) { q1[VFL_KB - 1] = a1[o]; q2[VFL_KB - 1] = a2[o]; }
+    }
+    wflx = (wflx - (((e - w) + n_) - s_)) - (d - dd) * scp2;
+    const size_t ok = (size_t)k * np;
+    a1[ok] = x1 + wflx;
+    a2[ok] = x2 + wflx * wflx;
+  }
+}
+
+// k_diavfl_lvl (:4693-4730): ucum(i), ucum(i+1), vcum(j), vcum(j+1) carried from d = ddm up to 1, each ucum = ucum + uflxlvl(d) -
+// uflxold(d) where the face's iu | iv is set (the loops over isu / isv to ii+1 | jj+1) and 0 otherwise; then
+//   q = -(ucum(i+1) - ucum(i) + vcum(j+1) - vcum(j)),  acc(d) = acc(d) + q,  acc2(d) = acc2(d) + q**2.
+// A column forms its eastern and northern neighbours' face sums itself: the same operations on the same values in the same
+// order, so the bits agree with what the neighbour forms.  The faces at ii+1 | jj+1 are the halo the exchange in front of the
+// launch gave uflxlvl | vflxlvl, and the halo the copy in front of the level launches took along into uflxold | vflxold.
+// Algorithmic bytes: (4 + 4) ddm planes.
+__global__ __launch_bounds__(256) void k_diavfl_lvl(const DevView *__restrict__ Vp, double *__restrict__ accp, int pu, int pv, int puo, int pvo, int pw, int pw2, int ddm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;
+  const int mc = V.m[I_mpack][t];
+  if (!(mc & 1)) return;
+  const size_t np = V.nplane, c = t, ni = V.ni;
+  const bool bw = (mc >> G_U) & 1, be = (V.m[I_mpack][t + 1] >> G_U) & 1, bs = (mc >> G_V) & 1, bn = (V.m[I_mpack][t + V.ni] >> G_V) & 1;
+  gd_t acc = global_ptr(accp);
+  gcd_t un = acc + (c + (size_t)pu * np), uo = acc + (c + (size_t)puo * np), vn = acc + (c + (size_t)pv * np), vo = acc + (c + (size_t)pvo * np);
+  gd_t a1 = acc + (c + (size_t)pw * np), a2 = acc + (c + (size_t)pw2 * np);
+  double une[VFL_KB], unw[VFL_KB], uoe[VFL_KB], uow[VFL_KB], vnn[VFL_KB], vns[VFL_KB], von[VFL_KB], vos[VFL_KB], q1[VFL_KB], q2[VFL_KB];
+#pragma unroll
+  for (int u = 0; u < VFL_KB; u++) {
+    const size_t o = (size_t)(ddm - 1 - u > 0 ? ddm - 1 - u : 0) * np;
+    une[u] = un[o + 1]; unw[u] = un[o]; uoe[u] = uo[o + 1]; uow[u] = uo[o];
+    vnn[u] = vn[o + ni]; vns[u] = vn[o]; von[u] = vo[o + ni]; vos[u] = vo[o];
+    q1[u] = a1[o]; q2[u] = a2[o];
+  }
+  double ucw = 0., uce = 0., vcs = 0., vcn = 0.;
+  for (int d = ddm - 1; d >= 0; d--) {
+    const double ne = une[0], nw = unw[0], oe = uoe[0], ow = uow[0], nn_ = vnn[0], ns = vns[0], on = von[0], os = vos[0], x1 = q1[0], x2 = q2[0];
+#pragma unroll
+    for (int u = 0; u + 1 < VFL_KB; u++) {
+      une[u] = une[u + 1]; unw[u] = unw[u + 1]; uoe[u] = uoe[u + 1]; uow[u] = uow[u + 1];
+      vnn[u] = vnn[u + 1]; vns[u] = vns[u + 1]; von[u] = von[u + 1]; vos[u] = vos[u + 1];
+      q1[u] = q1[u + 1]; q2[u] = q2[u + 1];
+    }
+    {
+      const size_t o = (size_t)(d - VFL_KB > 0 ? d - VFL_KB : 0) * np;
+      une[VFL_KB - 1] = un[o + 1]; unw[VFL_KB - 1] = un[o]; uoe[VFL_KB - 1] = uo[o + 1]; uow[VFL_KB - 1] = uo[o];
+      vnn[VFL_KB - 1] = vn[o + ni]; vns[VFL_KB - 1] = vn[o]; von[VFL_KB - 1] = vo[o + ni]; vos[VFL_KB - 1] = vo[o];
+      if (d - VFL_KB >= 0) { q1[VFL_KB - 1] = a1[o]; q2[VFL_KB - 1] = a2[o]; }
+    }
+    ucw = bw ? (ucw + nw) - ow : ucw;
+    uce = be ? (uce + ne) - oe : uce;
+    vcs = bs ? (vcs + ns) - os : vcs;
+    vcn = bn ? (vcn + nn_) - on : vcn;
+    const double q = -(((uce - ucw) + vcn) - vcs);
+    const size_t od = (size_t)d * np;
+    a1[od] = x1 + q;
+    a2[od] = x2 + q * q;
+  }
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 static int dia_init(blomgpu_ctx *c, DiaState *S) {
   DiaIni T;
@@ -575,6 +700,14 @@ void dia_free(blomgpu_ctx *c) {
 }
 
 bool dia_active(const blomgpu_ctx *c) { return c->dia != nullptr; }
+// diavfl reads dpold(km) as the previous step's tmsmt1 left it: blomgpu_step must not fold this step's tmsmt1 into its tmsmt2
+bool dia_reads_dpold(const blomgpu_ctx *c) { return c->dia && c->dia->vfl; }
+// the accumulators as a halo update sees them (xctilr of uflxlvl / vflxlvl inside diavfl): base and number of doubles in whole planes
+double *dia_acc_span(const blomgpu_ctx *c, size_t *n) {
+  if (!c->dia) return nullptr;
+  *n = c->dia->nplanes * c->dia->np;
+  return c->dia->acc;
+}
 void dia_count(blomgpu_ctx *c) { if (c->dia) c->dia->nacc++; }
 
 // z and dz are cmnfld1's: a step that does not run it would accumulate whatever the arrays hold
@@ -613,6 +746,8 @@ int dia_select(blomgpu_ctx *c, const char *names) {
     pos = end;
     const int r = find_row(nm);
     if (r < 0) return ctx_fail(c, "blomgpu_dia_select: unknown accumulator " + nm);
+    if (g_rows[r].op == OP_OLD)
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + " is a slot of diavfl's group (ACC_UFLXOLD / ACC_VFLXOLD), selected with wflx wflx2 wflxlvl wflx2lvl and not by name");
     if (g_rows[r].lev == LV_TKE && c->h.P.itrtke < 1)
       return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the TKE tracers (itrtke >= 1, phy/mod_dia.F90:1907)");
     if (g_rows[r].lev == LV_GLS && !(c->h.P.itrtke >= 1 && c->h.P.gls && c->h.P.itrgls >= 1))
@@ -635,9 +770,19 @@ int dia_select(blomgpu_ctx *c, const char *names) {
   // diaini's dependencies (:598-608): a dp-weighted row needs dp, uvel needs dpu, vvel needs dpv
   for (int r = 0; r < NROW; r++)
     if (want[r] && g_rows[r].wgt) want[find_row(g_rows[r].wgt == W_DP ? "dp" : g_rows[r].wgt == W_DPU ? "dpu" : "dpv")] = 1;
+  // diavfl's group (diaini :615-618, :644-647, :673-680): any of its four names selects all four, the fluxes and the level fluxes
+  // they are formed from, and the two slots that keep last step's level fluxes
+  bool vfl = false;
+  for (int r = 0; r < NROW; r++) vfl = vfl || (want[r] && g_rows[r].op == OP_VFL);
+  if (vfl) {
+    for (int r = 0; r < NROW; r++)
+      if (g_rows[r].op == OP_VFL || g_rows[r].op == OP_OLD) want[r] = 1;
+    for (const char *nm : {"uflx", "vflx", "uflxlvl", "vflxlvl"}) want[find_row(nm)] = 1;
+  }
   DiaState *S = nullptr;
   if (any) {
     S = new DiaState;
+    S->vfl = vfl;
     int n2d = 0, nly = 0, nlv = 0;
     for (int r = 0; r < NROW; r++)
       if (want[r] && g_rows[r].lyr == 2) nlv++;
@@ -702,13 +847,16 @@ int dia_get(blomgpu_ctx *c, const char *name, double *out) {
   return 0;
 }
 
-int dia_name_all(int index, char *buf, int cap, int *kind, int *grid) {
+int dia_name_full(int index, char *buf, int cap, int *kind, int *grid) {
   if (index < 0 || index >= NROW || !buf || cap < 2) return 1;
   snprintf(buf, cap, "%s", g_rows[index].name);
-  if (kind) *kind = g_rows[index].lyr;
+  if (kind) *kind = g_rows[index].op == OP_OLD ? KIND_INTERNAL : g_rows[index].lyr;
   if (grid) *grid = g_rows[index].grid;
   return 0;
 }
+
+// (the rows up to the density classes: where the table ended before diavfl's)
+int dia_name_all(int index, char *buf, int cap, int *kind, int *grid) { return index >= NROW_ALL ? 1 : dia_name_full(index, buf, cap, kind, grid); }
 
 // (the 2-D, layer and depth-level rows: where the table ended before the density classes)
 int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid) { return index >= NROW_NAMED ? 1 : dia_name_all(index, buf, cap, is_lyr, grid); }
@@ -728,7 +876,7 @@ int dia_finalize(blomgpu_ctx *c) {
   MskTab M;
   M.n = 0; M.ddm = S->ddm;
   for (size_t s = 0; s < S->rows.size(); s++)
-    if (g_rows[S->rows[s]].lyr == 2) { M.d[M.n][0] = S->plane0[s]; M.d[M.n][1] = g_rows[S->rows[s]].grid; M.n++; }
+    if (g_rows[S->rows[s]].lyr == 2 && g_rows[S->rows[s]].op != OP_OLD) { M.d[M.n][0] = S->plane0[s]; M.d[M.n][1] = g_rows[S->rows[s]].grid; M.n++; }   // (wflxlvl, wflx2lvl on p: :2676-2677)
   if (M.n) hipLaunchKernelGGL(k_dia_msklvl, plane_grid(c->h, S->ddm), dim3(256), 0, c->stream, c->d, S->acc, S->edges(), M);
   HIPCHK(c, hipGetLastError());
   return 0;
@@ -828,7 +976,7 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     T.n = 0; T.need = 0; T.lyr = pass; T.mlev = m - 1;
     for (size_t s = 0; s < S->rows.size(); s++) {
       const DiaRow &r = g_rows[S->rows[s]];
-      if (r.lyr != pass) continue;
+      if (r.lyr != pass || r.op >= OP_VFL) continue;
       int src = r.src, aux = r.aux, f2 = 0, l2 = 0, lev = 0, sreg = 0;
       switch (r.lev) {
         case LV_0: lev = 0; break;
@@ -858,6 +1006,15 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     TimeScope ts(c, pass ? "diaacc_lyr" : "diaacc_h2d");
     hipLaunchKernelGGL(k_diaacc, plane_grid(h, pass ? h.kk : 1), dim3(256), 0, c->stream, c->d, S->acc, T, mm);
   }
+  // diavfl's group, part 1 (:1921-1942, in front of the level launches): uflxold = uflxlvl, vflxold = vflxlvl -- the whole padded
+  // planes, so that the halo column and row of the last exchange go along (the reference copies out to ii+1 | jj+1)
+  const auto plane_of = [&](const char *nm) { return (size_t)S->plane0[S->slot_of(find_row(nm))]; };
+  if (S->vfl) {
+    TimeScope ts(c, "diavfl_copy");
+    const size_t nb = sizeof(double) * (size_t)S->ddm * S->np;
+    HIPCHK(c, hipMemcpyAsync(S->acc + plane_of("uflxold") * S->np, S->acc + plane_of("uflxlvl") * S->np, nb, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(S->acc + plane_of("vflxold") * S->np, S->acc + plane_of("vflxlvl") * S->np, nb, hipMemcpyDeviceToDevice, c->stream));
+  }
   // the depth levels: one launch per grid that has a selected name, in the reference's order u, v, p
   static const int order[3] = {G_U, G_V, G_P};
   for (int o = 0; S->ddm && o < 3; o++) {
@@ -869,7 +1026,7 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     T.clev = g == G_P ? mm : nn;
     for (size_t s = 0; s < S->rows.size(); s++) {
       const DiaRow &r = g_rows[S->rows[s]];
-      if (r.lyr != 2 || r.grid != g) continue;
+      if (r.lyr != 2 || r.grid != g || r.op >= OP_VFL) continue;
       int *d = T.d[T.n++];
       d[0] = r.src;
       d[1] = r.lev == LV_MM ? mm : r.lev == LV_NN ? nn : r.lev == LV_TKE ? (h.P.itrtke - 1) * 2 * h.kk + mm : r.lev == LV_GLS ? (h.P.itrgls - 1) * 2 * h.kk + mm : 0;
@@ -885,5 +1042,22 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     else hipLaunchKernelGGL((k_dialvl<G_V>), grid, dim3(256), 0, c->stream, c->d, S->acc, S->edges(), T, mm);
   }
   HIPCHK(c, hipGetLastError());
+  // diavfl's group, part 2 (:2279 -> :4633-4733), behind every other accumulation of the step
+  if (S->vfl) {
+    {
+      TimeScope ts(c, "diavfl_lyr");
+      hipLaunchKernelGGL(k_diavfl_lyr, plane_grid(h), dim3(256), 0, c->stream, c->d, S->acc, (int)plane_of("wflx"), (int)plane_of("wflx2"), mm, nn);
+      HIPCHK(c, hipGetLastError());
+    }
+    {
+      TimeScope ts(c, "diavfl_xctilr");
+      if (int rc = st_xctilr(c, S->acc + plane_of("uflxlvl") * S->np, 1, S->ddm, 1, 1, 13)) return rc;      // halo_uv, :4681
+      if (int rc = st_xctilr(c, S->acc + plane_of("vflxlvl") * S->np, 1, S->ddm, 1, 1, 14)) return rc;      // halo_vv, :4683
+    }
+    TimeScope ts(c, "diavfl_lvl");
+    hipLaunchKernelGGL(k_diavfl_lvl, plane_grid(h), dim3(256), 0, c->stream, c->d, S->acc, (int)plane_of("uflxlvl"), (int)plane_of("vflxlvl"),
+                       (int)plane_of("uflxold"), (int)plane_of("vflxold"), (int)plane_of("wflxlvl"), (int)plane_of("wflx2lvl"), S->ddm);
+    HIPCHK(c, hipGetLastError());
+  }
   return 0;
 }

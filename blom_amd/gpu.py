@@ -231,6 +231,17 @@ class BlomGpu:
             k += 1
         return rows
 
+    def dia_names_full(self):
+        """the whole table: the rows of dia_names_all() in their order, then diavfl's -- wflx wflx2 (kind 1), wflxlvl wflx2lvl
+        (kind 2) and the group's internal slots uflxold vflxold (kind 4: ddm depth levels, not selectable by name) --
+        blomgpu_dia_name_full"""
+        rows, buf, k = [], C.create_string_buffer(32), 0
+        kind, grid = C.c_int(0), C.c_int(0)
+        while self.lib.blomgpu_dia_name_full(k, buf, 32, C.byref(kind), C.byref(grid)) == 0:
+            rows.append((buf.value.decode(), kind.value, "puv"[grid.value]))
+            k += 1
+        return rows
+
     def dia_select(self, names):
         """replace the selection (a blank-separated string or a list of names; empty: none) -- blomgpu_dia_select"""
         if not isinstance(names, str):
@@ -248,10 +259,10 @@ class BlomGpu:
     def dia_get(self, name):
         """the accumulator as get() would return a field: (1 | kdm | ddm, nj, ni)"""
         if not hasattr(self, "_dia_lyr"):
-            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names_all()}
+            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names_full()}
         if name not in self._dia_lyr:
             raise KeyError(name)
-        nlev = (1, self.kdm, len(self.dia_levels()), self.kdm)[self._dia_lyr[name]]
+        nlev = (1, self.kdm, len(self.dia_levels()), self.kdm, len(self.dia_levels()))[self._dia_lyr[name]]
         a = np.empty((nlev, self.nj, self.ni), dtype=np.float64)
         self._chk(self.lib.blomgpu_dia_get(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p)))
         return a

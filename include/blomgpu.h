@@ -224,7 +224,7 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  *   reference forms "uvellvl vvellvl salnlvl templvl" inside ale_regrid_remap (:1944, :2059, :2174 leave them out): those four
  *   are refused there.  blomgpu_dia_get returns ddm planes for a level name; blomgpu_dia_finalize applies msklvl (:6659-6738) to
  *   them: at every owned point the levels whose upper bound is not above the bottom become nf90_fill_double.  Not built:
- *   accilv (difvmolvl difvholvl difvsolvl), pvlvl, wflxlvl / wflx2lvl (diavfl), the tracer levels (:3688-3788).
+ *   accilv (difvmolvl difvholvl difvsolvl), pvlvl, the tracer levels (:3688-3788).
  * blomgpu_dia_set_levels: the depth levels as bnds[ddm][2] = (upper, lower) bound of each level in metres, increasing and
  *   contiguous (bnds[d][1] == bnds[d+1][0]), ddm <= 128; otherwise, or while a level name is selected, it fails with a message and
  *   changes nothing.  bnds == NULL with ddm == 0 restores the default, the 35 levels of :111-128.
@@ -243,7 +243,22 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  * blomgpu_dia_set_sigdia: the kdm class densities (n == kdm; the reference's sigdia, taken as given as mod_vcoord.F90:978-1005
  *   does).  NULL with n == 0 clears the table.  A wrong n, a non-finite value, or a call while a class name is selected fails with
  *   a message and changes nothing.
- * blomgpu_dia_get_sigdia: *n (0: no table), and the first min(cap, n) values into out (may be NULL). */
+ * blomgpu_dia_get_sigdia: *n (0: no table), and the first min(cap, n) values into out (may be NULL).
+ *
+ * Vertical mass flux (diavfl, :4633-4733, called at :2279): "wflx wflx2" (kdm layers, p-grid, unweighted) and "wflxlvl wflx2lvl"
+ *   (ddm depth levels, p-grid) -- the flux through the layer interfaces, carried from the bottom up out of THAT step's uflx, vflx
+ *   and dp - dpold, the same on the depth levels out of the step's increments of uflxlvl / vflxlvl, and the squares of both.  The
+ *   four are one group (diaini :615-618, :644-647, :673-680): any of them selects all four, "uflx vflx uflxlvl vflxlvl", and two
+ *   internal ddm-level slots "uflxold" (u) and "vflxold" (v) (ACC_UFLXOLD / ACC_VFLXOLD, :1921-1942) that hold last step's uflxlvl /
+ *   vflxlvl.  blomgpu_dia_select refuses the two internal names; blomgpu_dia_get hands them out while the group is selected.  The
+ *   group uses and freezes the level table like every level name, and is admitted under every vertical coordinate.  Each step the
+ *   stage exchanges the one-point halo of uflxlvl and vflxlvl (xctilr, halo_uv / halo_vv, :4681-4684; on the arctic patch the
+ *   sign flips across the seam and the second half of row jj of vflxlvl is the seam's mirror, as the reference's).  While the
+ *   group is selected blomgpu_step keeps tmsmt1 a launch of its own (the option tmsmt_ahead has no effect): diavfl needs the
+ *   dpold of the previous step.  blomgpu_dia_finalize applies msklvl to "wflxlvl wflx2lvl" (:2676-2677) and leaves "wflx wflx2"
+ *   alone.  Neither blomgpu_dia_name nor blomgpu_dia_name_all enumerates these rows:
+ * blomgpu_dia_name_full: the whole table -- the 117 rows of blomgpu_dia_name_all in their order, then "wflx wflx2" (kind 1),
+ *   "wflxlvl wflx2lvl" (kind 2), "uflxold vflxold" (kind 4: ddm depth levels, internal -- not selectable by name). */
 int  blomgpu_dia_select(blomgpu_ctx *, const char *names);
 int  blomgpu_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int  blomgpu_dia_nacc(blomgpu_ctx *, int *nacc);
@@ -257,6 +272,7 @@ int  blomgpu_dia_get_levels(blomgpu_ctx *, double *bnds /* [cap][2] */, int cap,
 int  blomgpu_dia_name_all(int index, char *buf, int cap, int *kind, int *grid);
 int  blomgpu_dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
 int  blomgpu_dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
+int  blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid);
 
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
