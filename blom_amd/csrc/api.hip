@@ -643,6 +643,7 @@ int blomgpu_dia_levels_levitus2x(blomgpu_ctx *c) { return dia_levels_levitus2x(c
 int blomgpu_dia_get_levels(blomgpu_ctx *c, double *bnds, int cap, int *ddm) { return dia_get_levels(c, bnds, cap, ddm); }
 int blomgpu_dia_name_all(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_all(index, buf, cap, kind, grid); }
 int blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_full(index, buf, cap, kind, grid); }
+int blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_ext(index, buf, cap, kind, grid); }
 int blomgpu_dia_set_sigdia(blomgpu_ctx *c, const double *sigdia, int n) { return dia_set_sigdia(c, sigdia, n); }
 int blomgpu_dia_get_sigdia(blomgpu_ctx *c, double *out, int cap, int *n) { return dia_get_sigdia(c, out, cap, n); }
 // sfcstr, phy/mod_sfcstr.F90:33-62: the surface stress of the idealised experiments is set at initialisation

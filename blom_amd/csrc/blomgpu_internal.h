@@ -550,6 +550,8 @@ int dia_get(blomgpu_ctx *, const char *name, double *out);
 int dia_name(int index, char *buf, int cap, int *is_lyr, int *grid);
 int dia_name_all(int index, char *buf, int cap, int *kind, int *grid);
 int dia_name_full(int index, char *buf, int cap, int *kind, int *grid);
+int dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
+bool dia_reads_mldl82(const blomgpu_ctx *);  // one of the four mldl82 names is selected: st_cmnfld1 forms the field under isopyc_bulkml too
 bool dia_reads_dpold(const blomgpu_ctx *);   // diavfl's group is selected: a step's tmsmt1 stays a launch of its own (api.hip, blomgpu_step)
 double *dia_acc_span(const blomgpu_ctx *, size_t *n);   // the accumulators' planes, for halo updates inside diaacc (halo.hip, ctx_locate_ptr)
 int dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);

@@ -570,9 +570,11 @@ int st_cmnfld_bfsqi_ale(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
 }
 
 // cmnfld_mldl82, :933-995 (mixed layer depth after Levitus 1982) and the selection mld = mldl82, dpml = dpmll82 of cmnfld1 for
-// the vertical coordinates other than isopyc_bulkml with mldmth = 'lev82' (:1121-1131)
+// the vertical coordinates other than isopyc_bulkml with mldmth = 'lev82' (:1121-1131).  DIAG: the form cmnfld1 runs under
+// isopyc_bulkml for the diagnostics mldl82 mldl82mn mldl82mx mldl82sq (:1109-1113; :1124 does not apply): it writes mldl82 only
 #define DBCL82 .0003
 #define ONECM 98.06
+template <bool DIAG>
 __global__ __launch_bounds__(64) void k_cmn_mldl82(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
   COLUMN_IJ(V);
@@ -606,8 +608,10 @@ __global__ __launch_bounds__(64) void k_cmn_mldl82(const DevView *__restrict__ V
   }
 #undef L
   V.f[F_mldl82][c] = mld;
-  V.f[F_mld][c] = mld;
-  V.f[F_dpml][c] = dpml;
+  if (!DIAG) {
+    V.f[F_mld][c] = mld;
+    V.f[F_dpml][c] = dpml;
+  }
 }
 
 int st_cmnfld1(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
@@ -616,7 +620,11 @@ int st_cmnfld1(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   TimeScope ts(c, "cmnfld");
   hipLaunchKernelGGL(k_cmn_z, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, mm);
   // the other vertical coordinates also need the mixed layer depth (mldmth = 'lev82', the default; 'boy04' is not built)
-  if (h.P.vcoord_tag != 1) hipLaunchKernelGGL(k_cmn_mldl82, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, mm);
+  if (h.P.vcoord_tag != 1) hipLaunchKernelGGL(k_cmn_mldl82<false>, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, mm);
+  else if (dia_reads_mldl82(c)) {
+    TimeScope tm(c, "cmn_mldl82");
+    hipLaunchKernelGGL(k_cmn_mldl82<true>, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, mm);
+  }
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -22,6 +22,10 @@
 // The vertical mass flux and its square, on the layers and on the depth levels (diavfl, :4633-4733, called at :2279), are k_diavfl_lyr
 // and k_diavfl_lvl: the first family that reads a neighbour of a source, that exchanges accumulators between tiles (uflxlvl, vflxlvl,
 // :4681-4684), and that needs the dpold of the previous step (api.hip keeps tmsmt1 unfolded while it is selected).
+//
+// The diagnostics diaacc derives from the step's water column before it accumulates them -- sbot tbot (:1251-1294), t20d t17d
+// (:1296-1366), the Levitus-82 mixed layer depth mldl82 with its minimum, maximum and square (:1706, :1755, :1758, :1773; the field is
+// cmnfld1's, stage_cmnfld.hip) -- are k_diacol; the layer potential vorticity pair avdsg dpvor (:1203-1249) is k_diapv.
 #include "../../include/blomgpu.h"
 #include "blomgpu_internal.h"
 #include <cstring>
@@ -29,14 +33,19 @@
 namespace {
 enum { G_P = 0, G_U = 1, G_V = 2 };                 // the grid = the bit of mpack that masks it
 enum { OP_SUM = 0, OP_MAX = 1, OP_SQ = 2, OP_LVL = 3, OP_LVLFLX = 4, OP_CLS = 5,     // acclvl with diazlv's weights | weightsflx; the density classes
-       OP_VFL = 6, OP_OLD = 7 };    // diavfl's own rows, and the two level slots it keeps last step's uflxlvl / vflxlvl in: no table-driven launch touches them
+       OP_VFL = 6, OP_OLD = 7,      // diavfl's own rows, and the two level slots it keeps last step's uflxlvl / vflxlvl in: no table-driven launch touches them
+       OP_COL = 8, OP_PV = 9 };     // k_diacol's and k_diapv's rows: likewise
+// what a row of k_diacol is (DiaRow::src of an OP_COL row): the two bottom values, the two isotherm depths, mldl82 summed | min | max | squared
+enum { C_SBOT = 0, C_TBOT, C_T20D, C_T17D, C_ML, C_MLMN, C_MLMX, C_MLSQ, C_N };
 enum { W_NONE = 0, W_DP = 1, W_DPU = 2, W_DPV = 3 };       // weight (km); also: the register a source is taken from
 enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src + ub(m) | src + vb(m) | src + a second plane | src*onem
 // the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
 enum { LV_0, LV_M, LV_N, LV_KK, LV_MM, LV_NN, LV_TKE, LV_GLS };
 enum { SRC_DPML = -1 };                             // dpml as :1148-1171 forms it
 constexpr double ONEM = 9806.;                      // phy/mod_constants.F90
-constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948)
+constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948) and mldl82mx (:5901); +spval: of mldl82mn (:5900)
+constexpr double ONECM = 98.06, ONEMM = 9.806;      // phy/mod_constants.F90:51-52
+constexpr double DPBOT = ONEM;                      // phy/mod_dia.F90:196
 constexpr double EPSIL = 1.e-11, NF90_FILL_DOUBLE = 9.9692099683868690e+36;   // finlyr, :6126, :6140
 constexpr double EPSILP = 1.e-12;                   // phy/mod_constants.F90:43
 constexpr double SIGEPS = 1.e-9;                    // phy/mod_dia.F90:1120
@@ -50,6 +59,7 @@ struct DiaRow { const char *name; int lyr, grid, op, src, lev, wgt, aux, line; }
 #define LVP(nm, f, lv, ln) {#nm, 2, G_P, OP_LVL, f, lv, W_NONE, A_NONE, ln}
 #define CLS(nm, g, f, ln) {#nm, 3, g, OP_CLS, f, LV_NN, W_NONE, A_NONE, ln}
 #define VFL(nm, kind, g, op, f, ln) {#nm, kind, g, op, f, LV_NN, W_NONE, A_NONE, ln}
+#define COL(nm, what, ln) {#nm, 0, G_P, OP_COL, what, LV_0, W_NONE, A_NONE, ln}
 const DiaRow g_rows[] = {
   // ---- acch2d, :1547-1745 ----
   H2D(ub, G_U, F_ub, LV_M, 1547), H2D(ubflxs, G_U, F_ubflxs, LV_N, 1550), H2D(taux, G_U, F_taux, LV_0, 1556),
@@ -110,7 +120,14 @@ const DiaRow g_rows[] = {
   VFL(wflx, 1, G_P, OP_VFL, F_uflx, 4667), VFL(wflx2, 1, G_P, OP_VFL, F_uflx, 4669),
   VFL(wflxlvl, 2, G_P, OP_VFL, F_uflx, 4722), VFL(wflx2lvl, 2, G_P, OP_VFL, F_uflx, 4724),
   VFL(uflxold, 2, G_U, OP_OLD, F_uflx, 1928), VFL(vflxold, 2, G_V, OP_OLD, F_vflx, 1934),
+  // ---- the column-derived diagnostics (k_diacol): acch2d :1697-1715, minh2d :1755, maxh2d :1758, sqh2d :1773 of fields that diaacc
+  // (:1251-1366) and cmnfld1 (phy/mod_cmnfld_routines.F90:933-995) form from the step's column; then the layer pair of :1203-1249
+  // (k_diapv; acclyr :1244, :1247), one group (diaini :681-682).  Enumerated by blomgpu_dia_name_ext only ----
+  COL(sbot, C_SBOT, 1697), COL(tbot, C_TBOT, 1700), COL(t20d, C_T20D, 1712), COL(t17d, C_T17D, 1715),
+  COL(mldl82, C_ML, 1706), COL(mldl82mn, C_MLMN, 1755), COL(mldl82mx, C_MLMX, 1758), COL(mldl82sq, C_MLSQ, 1773),
+  {"avdsg", 1, G_P, OP_PV, F_absvor, LV_0, W_NONE, A_NONE, 1244}, {"dpvor", 1, G_P, OP_PV, F_dpvor, LV_0, W_NONE, A_NONE, 1247},
 };
+#undef COL
 #undef H2D
 #undef LYR
 #undef LVF
@@ -118,8 +135,9 @@ const DiaRow g_rows[] = {
 #undef CLS
 #undef VFL
 constexpr int NROW = (int)(sizeof(g_rows) / sizeof(g_rows[0]));
-constexpr int NROW_CLS = 6, NROW_VFL = 6;
-constexpr int NROW_ALL = NROW - NROW_VFL;          // blomgpu_dia_name_all stops in front of diavfl's rows,
+constexpr int NROW_CLS = 6, NROW_VFL = 6, NROW_COL = 10;
+constexpr int NROW_FULL = NROW - NROW_COL;         // blomgpu_dia_name_full stops in front of the column-derived rows,
+constexpr int NROW_ALL = NROW_FULL - NROW_VFL;     // blomgpu_dia_name_all in front of diavfl's,
 constexpr int NROW_NAMED = NROW_ALL - NROW_CLS;    // blomgpu_dia_name in front of the class rows
 constexpr int KIND_INTERNAL = 4;                   // what blomgpu_dia_name_full reports for uflxold / vflxold: ddm levels, selected by the group only
 
@@ -151,6 +169,7 @@ struct DiaState {
   double *edges() const { return acc + nplanes * np; }
   int ncls = 0;                 // selected density-class slots; their kk class densities lie behind the edges
   bool vfl = false;             // diavfl's group is selected: wflx wflx2 wflxlvl wflx2lvl uflx vflx uflxlvl vflxlvl uflxold vflxold
+  bool col = false, ml82 = false, pv = false;   // a row of k_diacol is selected; one of mldl82 mldl82mn mldl82mx mldl82sq; avdsg dpvor
   double *sigdia() const { return edges() + (ddm ? ddm + 1 : 0); }
   size_t np = 0;
   int slot_of(int row) const {
@@ -229,8 +248,10 @@ __global__ __launch_bounds__(256) void k_diaacc(const DevView *__restrict__ Vp, 
   }
 }
 
-// inih2d / inilyr (:5001-5113): inival*mask over the WHOLE padded plane (so land is -0.0 under maxbld's -spval)
-struct DiaIni { int n; int d[3 * DIA_MAXSLOT][3]; };            // per slot: first plane, levels, grid | is_max << 2
+// inih2d / inilyr (:5001-5113): inival*mask over the WHOLE padded plane (so land is -0.0 under maxbld's -spval, +0.0 under mldl82mn's +spval)
+#define DIA_MAXINI 136
+static_assert(NROW <= DIA_MAXINI, "k_dia_init carries one entry per selected row");
+struct DiaIni { int n; int d[DIA_MAXINI][3]; };                 // per slot: first plane, levels, grid | inival << 2 (0: 0., 1: -spval, 2: +spval)
 __global__ __launch_bounds__(256) void k_dia_init(const DevView *__restrict__ Vp, double *__restrict__ accp, const DiaIni T) {
   const DevView &V = *Vp;
   unsigned bx, by;
@@ -241,7 +262,8 @@ __global__ __launch_bounds__(256) void k_dia_init(const DevView *__restrict__ Vp
   gd_t acc = global_ptr(accp);
   for (int s = 0; s < T.n; s++) {
     if (k >= T.d[s][1]) continue;
-    const double inival = (T.d[s][2] >> 2) ? -SPVAL : 0.;
+    const int iv = T.d[s][2] >> 2;
+    const double inival = iv == 1 ? -SPVAL : iv == 2 ? SPVAL : 0.;
     acc[(size_t)t + ((size_t)T.d[s][0] + k) * V.nplane] = inival * (double)((msk >> (T.d[s][2] & 3)) & 1);
   }
 }
@@ -671,7 +693,166 @@ __global__ __launch_bounds__(256) void k_diavfl_lvl(const DevView *__restrict__ 
   }
 }
 
+// ---- the column-derived diagnostics: :1251-1366, and the mldl82 family ---------------------------------------------------------------
+// k_diacol: one thread per owned wet p-column, i on the lanes, ONE downward pass over the layers for the names that are selected
+// (wave-uniform flags: T.p[x] < 0 skips name x and the loads only it needs).  p(kk+1) first; p(k+1), temp, saln and dp of the next
+// COL_KB layers wait in a queue of registers; z and dz are read behind the pass, at the two layers an interpolation needs and nowhere
+// else.  Every value is added straight into its slot: no temporary plane.
+//   sbot, tbot (:1264-1292): q = max(0., p(k+1) - max(p(kk+1) - dpbot, p(k))); the sums start at 0. and take all kk terms in
+//     ascending k, those with q = 0. too; then *(1./dps) where dps > onemm, the layer-1 value otherwise.
+//   t20d, t17d (:1301-1325 | :1337-1361): kup moves on the layers with dp(km) > onecm and temp(km) > T only, the walk ends at the
+//     first layer with dp(km) > onecm and temp(km) <= T (k = 1: 0.; never: z(kk+1); otherwise the interpolation between the centres
+//     of kup and k with tlo = min(temp(km), tup - epsilp)).  The reference leaves kup undefined when the walk ends at k > 1 with
+//     nothing but massless layers above: here kup = 1 then (no case of this library has a massless top layer).
+//   mldl82 mldl82mn mldl82mx mldl82sq (:1706, :1755, :1758, :1773): acc + fld, min(acc, fld), max(acc, fld), acc + fld*fld of the
+//     device field mldl82 that cmnfld1 left (stage_cmnfld.hip; under isopyc_bulkml st_cmnfld1 forms it for these four names only).
+// Algorithmic bytes: ((sbot | tbot: 2) + (t20d | t17d: 1) + 1 (temp)) kk planes + p(kk+1) + <= 4 planes of z / dz + mldl82 + 2 n_acc.
+#define COL_KB 2
+struct ColTab { int p[C_N]; };                // first plane of each name's slot, -1: not selected
+__global__ __launch_bounds__(256) void k_diacol(const DevView *__restrict__ Vp, double *__restrict__ accp, const ColTab T, int mm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj || !(V.m[I_mpack][t] & 1)) return;
+  const size_t np = V.nplane, c = t;
+  const int kk = V.kk;
+  gd_t acc = global_ptr(accp);
+  const bool bot = T.p[C_SBOT] >= 0 || T.p[C_TBOT] >= 0, iso = T.p[C_T20D] >= 0 || T.p[C_T17D] >= 0;       // wave-uniform
+  if (bot || iso) {
+    gcd_t p = V.f[F_p] + c, z = V.f[F_z] + c, dz = V.f[F_dz] + c;
+    gcd_t temp = V.f[F_temp] + (c + (size_t)mm * np), saln = V.f[F_saln] + (c + (size_t)mm * np), dp = V.f[F_dp] + (c + (size_t)mm * np);
+    const double plim = bot ? p[(size_t)kk * np] - DPBOT : 0.;          // p(kk+1) - dpbot
+    double pk = bot ? p[0] : 0.;
+    double pq[COL_KB], tq[COL_KB], sq[COL_KB], dq[COL_KB];
+#pragma unroll
+    for (int u = 0; u < COL_KB; u++) {
+      const size_t o = (size_t)(u < kk ? u : kk - 1) * np;
+      tq[u] = temp[o];
+      pq[u] = bot ? p[o + np] : 0.;
+      sq[u] = bot ? saln[o] : 0.;
+      dq[u] = iso ? dp[o] : 0.;
+    }
+    double sb = 0., tb = 0., dps = 0., s1 = 0., t1 = 0.;
+    // the two walks: ke = 0 while the walk goes on, else the layer it ended at (1-based); kup, tup as the reference carries them
+    int ke20 = 0, ke17 = 0, ku20 = 1, ku17 = 1;
+    double tu20 = 0., tu17 = 0., te20 = 0., te17 = 0.;
+    for (int k = 0; k < kk; k++) {
+      const double pk1 = pq[0], tk = tq[0], sk = sq[0], dk = dq[0];
+#pragma unroll
+      for (int u = 0; u + 1 < COL_KB; u++) { pq[u] = pq[u + 1]; tq[u] = tq[u + 1]; sq[u] = sq[u + 1]; dq[u] = dq[u + 1]; }
+      {
+        const size_t o = (size_t)(k + COL_KB < kk ? k + COL_KB : kk - 1) * np;
+        tq[COL_KB - 1] = temp[o];
+        if (bot) { pq[COL_KB - 1] = p[o + np]; sq[COL_KB - 1] = saln[o]; }
+        if (iso) dq[COL_KB - 1] = dp[o];
+      }
+      if (k == 0) { s1 = sk; t1 = tk; tu20 = tu17 = tk; }
+      if (bot) {
+        const double q = fmax2(0., pk1 - fmax2(plim, pk));
+        sb = sb + sk * q;
+        tb = tb + tk * q;
+        dps = dps + q;
+        pk = pk1;
+      }
+      if (iso && dk > ONECM) {
+        if (!ke20) {
+          if (tk > 20.) { ku20 = k + 1; tu20 = tk; }
+          else { ke20 = k + 1; te20 = tk; }
+        }
+        if (!ke17) {
+          if (tk > 17.) { ku17 = k + 1; tu17 = tk; }
+          else { ke17 = k + 1; te17 = tk; }
+        }
+      }
+    }
+    if (bot) {
+      if (dps > ONEMM) {
+        const double q = 1. / dps;
+        sb = sb * q;
+        tb = tb * q;
+      } else {
+        sb = s1;
+        tb = t1;
+      }
+      if (T.p[C_SBOT] >= 0) { const size_t o = c + (size_t)T.p[C_SBOT] * np; acc[o] = acc[o] + sb; }
+      if (T.p[C_TBOT] >= 0) { const size_t o = c + (size_t)T.p[C_TBOT] * np; acc[o] = acc[o] + tb; }
+    }
+#pragma unroll
+    for (int w = 0; w < 2; w++) {
+      const int slot = T.p[w ? C_T17D : C_T20D];
+      if (slot < 0) continue;
+      const int ke = w ? ke17 : ke20, ku = w ? ku17 : ku20;
+      const double tx = w ? 17. : 20., tup = w ? tu17 : tu20, te = w ? te17 : te20;
+      double d;
+      if (ke == 1) d = 0.;
+      else if (ke == 0) d = z[(size_t)kk * np];
+      else {
+        const double zup = z[(size_t)(ku - 1) * np] + .5 * dz[(size_t)(ku - 1) * np];
+        const double zlo = z[(size_t)(ke - 1) * np] + .5 * dz[(size_t)(ke - 1) * np];
+        const double tlo = fmin2(te, tup - EPSILP);
+        d = (zup * (tlo - tx) + zlo * (tx - tup)) / (tlo - tup);
+      }
+      const size_t o = c + (size_t)slot * np;
+      acc[o] = acc[o] + d;
+    }
+  }
+  if (T.p[C_ML] >= 0 || T.p[C_MLMN] >= 0 || T.p[C_MLMX] >= 0 || T.p[C_MLSQ] >= 0) {
+    const double f = V.f[F_mldl82][c];
+    if (T.p[C_ML] >= 0) { const size_t o = c + (size_t)T.p[C_ML] * np; acc[o] = acc[o] + f; }                 // acch2d, :5256
+    if (T.p[C_MLMN] >= 0) { const size_t o = c + (size_t)T.p[C_MLMN] * np; acc[o] = fmin2(acc[o], f); }       // minh2d, :5392
+    if (T.p[C_MLMX] >= 0) { const size_t o = c + (size_t)T.p[C_MLMX] * np; acc[o] = fmax2(acc[o], f); }       // maxh2d, :5330
+    if (T.p[C_MLSQ] >= 0) { const size_t o = c + (size_t)T.p[C_MLSQ] * np; acc[o] = acc[o] + f * f; }         // sqh2d, :5454
+  }
+}
+
+// k_diapv (:1208-1247): one thread per owned wet p-point and layer.  The corner masks min(1, iu + iv) from the mask bits of the
+// point and of its eastern and northern neighbours; dsig in its three cases with the .5* outside the max; the corner sums left to
+// right, every product with a 0/1 mask performed (a q-point momtum never wrote holds spval, and spval*0. is +0.); absvor and dpvor
+// at plane k, not km: momtum writes planes 1..kk of their 2*kdm.  Then acclyr (:5500), unweighted.
+// Algorithmic bytes: (3 + 4) kk planes (absvor, dpvor: a q-point is read by the four p-points around it and comes from memory
+// once; sigma: a thread reads up to three planes, each plane once from memory; two accumulators read and written).
+__global__ __launch_bounds__(256) void k_diapv(const DevView *__restrict__ Vp, double *__restrict__ accp, int pa, int pd, int mm) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, k = by;            // k: 0-based layer
+  if (t >= V.nplane || k >= V.kk) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;
+  const int mc = V.m[I_mpack][t];
+  if (!(mc & 1)) return;
+  const size_t np = V.nplane, c = t, ni = V.ni;
+  const int kk = V.kk;
+  const int iuw = (mc >> G_U) & 1, iue = (V.m[I_mpack][t + 1] >> G_U) & 1, ivs = (mc >> G_V) & 1, ivn = (V.m[I_mpack][t + V.ni] >> G_V) & 1;
+  const double sw = (double)(iuw | ivs), se = (double)(iue | ivs), nw = (double)(iuw | ivn), ne = (double)(iue | ivn);     // min(1, iu + iv)
+  gcd_t sg = V.f[F_sigma] + (c + (size_t)mm * np);
+  gcd_t av = V.f[F_absvor] + (c + (size_t)k * np), dv = V.f[F_dpvor] + (c + (size_t)k * np);
+  gd_t a1 = global_ptr(accp) + (c + ((size_t)pa + k) * np), a2 = global_ptr(accp) + (c + ((size_t)pd + k) * np);
+  const double x1 = a1[0], x2 = a2[0];
+  const double a00 = av[0], a10 = av[1], a01 = av[ni], a11 = av[ni + 1];
+  const double d00 = dv[0], d10 = dv[1], d01 = dv[ni], d11 = dv[ni + 1];
+  const double s2 = sg[kk > 1 ? np : 0];                                  // sigma(2+mm)
+  double dsig;
+  if (k + 1 <= 2) dsig = fmax2(0., s2 - sg[0]);
+  else if (k + 1 == kk) dsig = fmax2(0., sg[(size_t)k * np] - fmax2(sg[(size_t)(k - 1) * np], s2));
+  else dsig = .5 * fmax2(0., sg[(size_t)(k + 1) * np] - fmax2(sg[(size_t)(k - 1) * np], s2));
+  const double f1 = (((a00 * sw + a10 * se) + a01 * nw) + a11 * ne) * dsig;
+  const double f2 = ((d00 * sw + d10 * se) + d01 * nw) + d11 * ne;
+  a1[0] = x1 + f1;
+  a2[0] = x2 + f2;
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
+// inifld's initial values (:5864-5960): -spval under a maximum, +spval under a minimum, 0. otherwise
+static int ini_of(const DiaRow &r) {
+  if (r.op == OP_MAX || (r.op == OP_COL && r.src == C_MLMX)) return 1;
+  if (r.op == OP_COL && r.src == C_MLMN) return 2;
+  return 0;
+}
+
 static int dia_init(blomgpu_ctx *c, DiaState *S) {
   DiaIni T;
   T.n = 0;
@@ -679,7 +860,7 @@ static int dia_init(blomgpu_ctx *c, DiaState *S) {
   for (size_t s = 0; s < S->rows.size(); s++) {
     const DiaRow &r = g_rows[S->rows[s]];
     const int nl = r.lyr == 2 ? S->ddm : r.lyr ? c->h.kk : 1;          // (kk for the layers and the density classes)
-    T.d[T.n][0] = S->plane0[s]; T.d[T.n][1] = nl; T.d[T.n][2] = r.grid | (r.op == OP_MAX) << 2;
+    T.d[T.n][0] = S->plane0[s]; T.d[T.n][1] = nl; T.d[T.n][2] = r.grid | ini_of(r) << 2;
     T.n++;
     if (nl > maxlev) maxlev = nl;
   }
@@ -703,6 +884,8 @@ bool dia_active(const blomgpu_ctx *c) { return c->dia != nullptr; }
 // diavfl reads dpold(km) as the previous step's tmsmt1 left it: blomgpu_step must not fold this step's tmsmt1 into its tmsmt2
 bool dia_reads_dpold(const blomgpu_ctx *c) { return c->dia && c->dia->vfl; }
 // the accumulators as a halo update sees them (xctilr of uflxlvl / vflxlvl inside diavfl): base and number of doubles in whole planes
+// one of mldl82 mldl82mn mldl82mx mldl82sq is selected: cmnfld1 forms mldl82 under isopyc_bulkml too (phy/mod_cmnfld_routines.F90:1109-1113)
+bool dia_reads_mldl82(const blomgpu_ctx *c) { return c->dia && c->dia->ml82; }
 double *dia_acc_span(const blomgpu_ctx *c, size_t *n) {
   if (!c->dia) return nullptr;
   *n = c->dia->nplanes * c->dia->np;
@@ -711,6 +894,10 @@ double *dia_acc_span(const blomgpu_ctx *c, size_t *n) {
 void dia_count(blomgpu_ctx *c) { if (c->dia) c->dia->nacc++; }
 
 // z and dz are cmnfld1's: a step that does not run it would accumulate whatever the arrays hold
+static bool reads_z(const DiaRow &r) {     // z or dz directly, or through mldl82 (:950-976) and the isotherms' interpolation (:1318-1321)
+  if (r.op == OP_COL) return r.src != C_SBOT && r.src != C_TBOT;
+  return r.op < OP_VFL && (r.src == F_z || r.src == F_dz);
+}
 static bool hybrid_remapped(int r) {       // the level rows the hybrid coordinate forms inside ale_regrid_remap (:1944, :2059, :2174 leave them out)
   const std::string nm = g_rows[r].name;
   return nm == "uvellvl" || nm == "vvellvl" || nm == "salnlvl" || nm == "templvl";
@@ -727,7 +914,7 @@ int dia_step_check(blomgpu_ctx *c) {
   if (c->h.P.vcoord_tag != 1 || c->cmnfld1 || c->full_physics) return 0;
   std::string names;
   for (int r : c->dia->rows)
-    if (g_rows[r].src == F_z || g_rows[r].src == F_dz) names += std::string(names.empty() ? "" : " ") + g_rows[r].name;
+    if (reads_z(g_rows[r])) names += std::string(names.empty() ? "" : " ") + g_rows[r].name;
   return ctx_fail(c, "blomgpu_step: the selected accumulators " + names + " read z / dz, which this step sequence does not compute (set cmnfld1 = 1 or full_physics = 1)");
 }
 
@@ -779,6 +966,13 @@ int dia_select(blomgpu_ctx *c, const char *names) {
       if (g_rows[r].op == OP_VFL || g_rows[r].op == OP_OLD) want[r] = 1;
     for (const char *nm : {"uflx", "vflx", "uflxlvl", "vflxlvl"}) want[find_row(nm)] = 1;
   }
+  // avdsg and dpvor come as a pair (diaini :681-682)
+  if (want[find_row("avdsg")] || want[find_row("dpvor")]) want[find_row("avdsg")] = want[find_row("dpvor")] = 1;
+  // z and dz are cmnfld1's: the names that need them are refused here already where the step sequence would not run it
+  if (c->h.P.vcoord_tag == 1 && !c->cmnfld1 && !c->full_physics)
+    for (int r = 0; r < NROW; r++)
+      if (want[r] && g_rows[r].op == OP_COL && reads_z(g_rows[r]))
+        return ctx_fail(c, std::string("blomgpu_dia_select: ") + g_rows[r].name + " reads z / dz, which this step sequence does not compute (set cmnfld1 = 1 or full_physics = 1)");
   DiaState *S = nullptr;
   if (any) {
     S = new DiaState;
@@ -795,9 +989,11 @@ int dia_select(blomgpu_ctx *c, const char *names) {
           S->rows.push_back(r);
           S->plane0.push_back((int)S->nplanes);
           S->nplanes += pass == 2 ? S->ddm : pass ? c->h.kk : 1;
-          if (pass < 2) (pass ? nly : n2d)++;
+          if (pass < 2 && g_rows[r].op < OP_VFL) (pass ? nly : n2d)++;          // (the slots a launch of k_diaacc carries)
           if (pass == 3) S->ncls++;
-          if (g_rows[r].src == F_z || g_rows[r].src == F_dz) S->needs_z = true;
+          if (reads_z(g_rows[r])) S->needs_z = true;
+          if (g_rows[r].op == OP_COL) { S->col = true; if (g_rows[r].src >= C_ML) S->ml82 = true; }
+          if (g_rows[r].op == OP_PV) S->pv = true;
         }
     if (n2d > DIA_MAXSLOT || nly > DIA_MAXSLOT) { delete S; return ctx_fail(c, "blomgpu_dia_select: more slots than a launch carries"); }
     (void)hipSetDevice(c->device);
@@ -847,13 +1043,16 @@ int dia_get(blomgpu_ctx *c, const char *name, double *out) {
   return 0;
 }
 
-int dia_name_full(int index, char *buf, int cap, int *kind, int *grid) {
+int dia_name_ext(int index, char *buf, int cap, int *kind, int *grid) {
   if (index < 0 || index >= NROW || !buf || cap < 2) return 1;
   snprintf(buf, cap, "%s", g_rows[index].name);
   if (kind) *kind = g_rows[index].op == OP_OLD ? KIND_INTERNAL : g_rows[index].lyr;
   if (grid) *grid = g_rows[index].grid;
   return 0;
 }
+
+// (the rows up to diavfl's: where the table ended before the column-derived rows)
+int dia_name_full(int index, char *buf, int cap, int *kind, int *grid) { return index >= NROW_FULL ? 1 : dia_name_ext(index, buf, cap, kind, grid); }
 
 // (the rows up to the density classes: where the table ended before diavfl's)
 int dia_name_all(int index, char *buf, int cap, int *kind, int *grid) { return index >= NROW_ALL ? 1 : dia_name_full(index, buf, cap, kind, grid); }
@@ -872,6 +1071,10 @@ int dia_finalize(blomgpu_ctx *c) {
     const int ws = S->slot_of(find_row(r.wgt == W_DP ? "dp" : r.wgt == W_DPU ? "dpu" : "dpv"));
     hipLaunchKernelGGL(k_dia_finlyr, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, S->acc, S->plane0[s], S->plane0[ws], r.grid);
   }
+  // finlyr(ACC_AVDSG, ACC_DPVOR, 'p'), :2608: avdsg / dpvor where dpvor > epsil; dpvor itself stays
+  if (S->pv)
+    hipLaunchKernelGGL(k_dia_finlyr, plane_grid(c->h, c->h.kk), dim3(256), 0, c->stream, c->d, S->acc, S->plane0[S->slot_of(find_row("avdsg"))],
+                       S->plane0[S->slot_of(find_row("dpvor"))], (int)G_P);
   // msklvl for every depth-level slot (:2642-2679)
   MskTab M;
   M.n = 0; M.ddm = S->ddm;
@@ -971,6 +1174,23 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
       HIPCHK(c, hipGetLastError());
     }
   }
+  // the layer potential vorticity pair, in the reference's position (:1203-1249)
+  const auto plane_of = [&](const char *nm) { return (size_t)S->plane0[S->slot_of(find_row(nm))]; };
+  if (S->pv) {
+    TimeScope ts(c, "diapv");
+    hipLaunchKernelGGL(k_diapv, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, S->acc, (int)plane_of("avdsg"), (int)plane_of("dpvor"), mm);
+    HIPCHK(c, hipGetLastError());
+  }
+  // the column-derived 2-D diagnostics (:1251-1366) and the mldl82 family, in front of the 2-D accumulation
+  if (S->col) {
+    ColTab T;
+    for (int x = 0; x < C_N; x++) T.p[x] = -1;
+    for (size_t s = 0; s < S->rows.size(); s++)
+      if (g_rows[S->rows[s]].op == OP_COL) T.p[g_rows[S->rows[s]].src] = S->plane0[s];
+    TimeScope ts(c, "diacol");
+    hipLaunchKernelGGL(k_diacol, plane_grid(h), dim3(256), 0, c->stream, c->d, S->acc, T, mm);
+    HIPCHK(c, hipGetLastError());
+  }
   for (int pass = 1; pass >= 0; pass--) {
     DiaTab T;
     T.n = 0; T.need = 0; T.lyr = pass; T.mlev = m - 1;
@@ -1008,7 +1228,6 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   }
   // diavfl's group, part 1 (:1921-1942, in front of the level launches): uflxold = uflxlvl, vflxold = vflxlvl -- the whole padded
   // planes, so that the halo column and row of the last exchange go along (the reference copies out to ii+1 | jj+1)
-  const auto plane_of = [&](const char *nm) { return (size_t)S->plane0[S->slot_of(find_row(nm))]; };
   if (S->vfl) {
     TimeScope ts(c, "diavfl_copy");
     const size_t nb = sizeof(double) * (size_t)S->ddm * S->np;

@@ -105,6 +105,12 @@ module mod_blomgpu
       import :: c_ptr, c_int
       type(c_ptr), value :: c
     end function
+    integer(c_int) function blomgpu_dia_name_ext(index, buf, cap, kind, grid) bind(C, name='blomgpu_dia_name_ext')
+      import :: c_int, c_char
+      integer(c_int), value :: index, cap
+      character(kind=c_char), intent(out) :: buf(*)
+      integer(c_int), intent(out) :: kind, grid
+    end function
     integer(c_int) function blomgpu_dia_set_levels(c, bnds, ddm) bind(C, name='blomgpu_dia_set_levels')
       import :: c_ptr, c_int
       type(c_ptr), value :: c, bnds
@@ -245,7 +251,7 @@ module mod_blomgpu
             diapfl, barotp, eddtra, convec, sfcstr, updtrc, init_cppm, halo_cmnfld2, halo_difest, mxlayr_tail, &
             cmnfld1, cmnfld2, ale_regrid_remap, ale_vdifft, ale_vdiffm, ale_forcing, &
             cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc
-  public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc
+  public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
@@ -570,6 +576,29 @@ contains
     real(8), intent(out) :: a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,nlev)
     call gpu_check(blomgpu_dia_get(ctx, cz(name), a), 'gpu_dia_get')
   end subroutine
+  ! row `index` (0-based) of the whole accumulator table, the column-derived rows included (blomgpu_dia_name_ext): the name, its
+  ! kind (0 2-D, 1 kdm layers, 2 ddm depth levels, 3 kdm density classes, 4 internal) and grid (0 p, 1 u, 2 v); found = .false.
+  ! behind the last row
+  subroutine gpu_dia_name_ext(index, name, kind, grid, found)
+    integer, intent(in) :: index
+    character(len=*), intent(out) :: name
+    integer, intent(out) :: kind, grid
+    logical, intent(out) :: found
+    character(kind=c_char) :: buf(32)
+    integer(c_int) :: k, g
+    integer :: q
+    name = ' '
+    kind = -1
+    grid = -1
+    found = blomgpu_dia_name_ext(int(index, c_int), buf, 32_c_int, k, g) == 0
+    if (.not. found) return
+    kind = k
+    grid = g
+    do q = 1, min(32, len(name))
+      if (buf(q) == c_null_char) exit
+      name(q:q) = buf(q)
+    end do
+  end subroutine gpu_dia_name_ext
   subroutine gpu_dia_finalize()                 ! finlyr for the weighted layer pairs, phy/mod_dia.F90:2597-2611
     call gpu_check(blomgpu_dia_finalize(ctx), 'gpu_dia_finalize')
   end subroutine

@@ -242,6 +242,16 @@ class BlomGpu:
             k += 1
         return rows
 
+    def dia_names_ext(self):
+        """the whole table: the rows of dia_names_full() in their order, then the column-derived rows -- sbot tbot t20d t17d mldl82
+        mldl82mn mldl82mx mldl82sq (kind 0) and avdsg dpvor (kind 1) -- blomgpu_dia_name_ext"""
+        rows, buf, k = [], C.create_string_buffer(32), 0
+        kind, grid = C.c_int(0), C.c_int(0)
+        while self.lib.blomgpu_dia_name_ext(k, buf, 32, C.byref(kind), C.byref(grid)) == 0:
+            rows.append((buf.value.decode(), kind.value, "puv"[grid.value]))
+            k += 1
+        return rows
+
     def dia_select(self, names):
         """replace the selection (a blank-separated string or a list of names; empty: none) -- blomgpu_dia_select"""
         if not isinstance(names, str):
@@ -259,7 +269,7 @@ class BlomGpu:
     def dia_get(self, name):
         """the accumulator as get() would return a field: (1 | kdm | ddm, nj, ni)"""
         if not hasattr(self, "_dia_lyr"):
-            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names_full()}
+            self._dia_lyr = {nm: lyr for nm, lyr, _ in self.dia_names_ext()}
         if name not in self._dia_lyr:
             raise KeyError(name)
         nlev = (1, self.kdm, len(self.dia_levels()), self.kdm, len(self.dia_levels()))[self._dia_lyr[name]]

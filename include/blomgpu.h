@@ -258,7 +258,28 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  *   dpold of the previous step.  blomgpu_dia_finalize applies msklvl to "wflxlvl wflx2lvl" (:2676-2677) and leaves "wflx wflx2"
  *   alone.  Neither blomgpu_dia_name nor blomgpu_dia_name_all enumerates these rows:
  * blomgpu_dia_name_full: the whole table -- the 117 rows of blomgpu_dia_name_all in their order, then "wflx wflx2" (kind 1),
- *   "wflxlvl wflx2lvl" (kind 2), "uflxold vflxold" (kind 4: ddm depth levels, internal -- not selectable by name). */
+ *   "wflxlvl wflx2lvl" (kind 2), "uflxold vflxold" (kind 4: ddm depth levels, internal -- not selectable by name).
+ *
+ * Column-derived names (10; all on the p-grid, owned masked points): what diaacc derives from THAT step's water column before it
+ *   accumulates it -- a search or a nonlinear function of the column, so no time mean of the state gives it.
+ *   "sbot tbot" (2-D; :1251-1294, acch2d :1697, :1700): salinity and temperature averaged over the lowest dpbot = onem (:196) of the
+ *     column; where that is thinner than onemm, the values of layer 1.
+ *   "t20d t17d" (2-D; :1296-1366, acch2d :1712, :1715): depth of the 20 and 17 degC isotherms -- 0. where the first layer thicker
+ *     than onecm is colder, z(kk+1) where no layer thicker than onecm is, the interpolation between two layer centres otherwise.
+ *   "mldl82 mldl82mn mldl82mx mldl82sq" (2-D; acch2d :1706, minh2d :1755 / :5347-5405, maxh2d :1758, sqh2d :1773): the mixed layer
+ *     depth after Levitus (1982), phy/mod_cmnfld_routines.F90:933-995, its minimum (initial value +1e33*mask, :5900), maximum
+ *     (-1e33*mask, :5901) and square.  The field is cmnfld1's: under cntiso_hybrid / plevel it is the mixed layer depth cmnfld1
+ *     forms anyway, under isopyc_bulkml cmnfld1 forms it while one of the four is selected (:1109-1113), writing mldl82 only.
+ *   "t20d t17d" and the four mldl82 names read z / dz: under isopyc_bulkml a step sequence that does not run cmnfld1 (options
+ *     cmnfld1 = 0 and full_physics = 0) refuses them at blomgpu_dia_select and again at blomgpu_step.  A host that drives the
+ *     stages itself calls blomgpu_cmnfld1 in front of blomgpu_diaacc (phy/mod_blom_step.F90:233-239) and sets cmnfld1 = 1.
+ *   "avdsg dpvor" (kdm layers, unweighted; :1203-1247): absolute vorticity at the four corners of the p-point, masked and summed,
+ *     times the layer's potential density difference, and the thickness momtum used for the vorticity (mod_momtum.F90:477-496)
+ *     summed likewise.  Either name selects both (diaini :681-682).  blomgpu_dia_finalize divides "avdsg" by "dpvor" where dpvor >
+ *     1e-11, else nf90_fill_double (finlyr(ACC_AVDSG, ACC_DPVOR, 'p'), :2608), and leaves "dpvor" alone.
+ *   blomgpu_dia_name, _name_all and _name_full do NOT enumerate these rows:
+ * blomgpu_dia_name_ext: the whole table -- the 123 rows of blomgpu_dia_name_full in their order, then "sbot tbot t20d t17d mldl82
+ *   mldl82mn mldl82mx mldl82sq" (kind 0) and "avdsg dpvor" (kind 1): 133 rows.  Not built: mldb04 and its kin, pvlvl. */
 int  blomgpu_dia_select(blomgpu_ctx *, const char *names);
 int  blomgpu_diaacc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int  blomgpu_dia_nacc(blomgpu_ctx *, int *nacc);
@@ -273,6 +294,7 @@ int  blomgpu_dia_name_all(int index, char *buf, int cap, int *kind, int *grid);
 int  blomgpu_dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
 int  blomgpu_dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
 int  blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid);
+int  blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
 
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
