@@ -633,6 +633,7 @@ int blomgpu_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
   return st_diaacc(c, m, n, mm, nn, k1m, k1n);
 }
 int blomgpu_dia_select(blomgpu_ctx *c, const char *names) { return dia_select(c, names); }
+int blomgpu_dia_alarm(blomgpu_ctx *c, int alarm) { return dia_alarm(c, alarm); }
 int blomgpu_dia_nacc(blomgpu_ctx *c, int *nacc) { return dia_nacc(c, nacc); }
 int blomgpu_dia_get(blomgpu_ctx *c, const char *name, double *out) { return dia_get(c, name, out); }
 int blomgpu_dia_finalize(blomgpu_ctx *c) { return dia_finalize(c); }
@@ -715,6 +716,10 @@ int blomgpu_mxlayr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
 int blomgpu_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {   // phy/mod_ale_regrid_remap.F90:1486
   ctx_sync_view(c);
   return st_ale_regrid_remap(c, m, n, mm, nn, k1m, k1n);
+}
+int blomgpu_ale_remap_diazlv(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {   // phy/mod_ale_regrid_remap.F90:1986
+  ctx_sync_view(c);
+  return st_ale_remap_diazlv(c, m, n, mm, nn, k1m, k1n);
 }
 int blomgpu_cmnfld_bfsqi_ale(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {  // phy/mod_cmnfld_routines.F90:352
   ctx_sync_view(c);
@@ -801,7 +806,7 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
   X(mxlayr_tail, blomgpu_mxlayr_tail(c, nn, k1n)) X(mxlayr, blomgpu_mxlayr(ALL6)) X(thermf, blomgpu_thermf(ALL6))                 \
   X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
   X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6)) \
-  X(diaacc, blomgpu_diaacc(ALL6))
+  X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6))
 enum StageId {
 #define X(nm, call) S_##nm,
   BLOM_STAGES(X)

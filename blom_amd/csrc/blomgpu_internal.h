@@ -456,6 +456,7 @@ struct blomgpu_ctx {
   DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
   std::vector<double> dia_edges;               // blomgpu_dia_set_levels: the ddm + 1 edges of the depth levels; empty: the 35-level table
   std::vector<double> dia_sigdia;              // blomgpu_dia_set_sigdia: the kk diagnostic density classes; empty: none (a class name is refused)
+  int dia_alarm = -1;                          // blomgpu_dia_alarm: alarm_phy(1) as the host declared it, 0 | 1; -1: undeclared
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space
@@ -536,6 +537,7 @@ int st_ale_vdiffm(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n)
 int st_ale_forcing(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);         // stage_ale_vdiff.hip
 int st_cmnfld_bfsqi_ale(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);    // stage_cmnfld.hip
 int st_ale_regrid_remap(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_ale.hip
+int st_ale_remap_diazlv(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_ale.hip: phy/mod_ale_regrid_remap.F90:1986-2201
 void ale_free(blomgpu_ctx *);
 int ale_check_deferred(blomgpu_ctx *);      // stage_ale.hip: the engine's status of the steps since the last check
 int st_mxlayr(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_mxlayr.hip
@@ -559,6 +561,11 @@ int dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
 int dia_set_levels(blomgpu_ctx *, const double *bnds, int ddm);
 int dia_levels_levitus2x(blomgpu_ctx *);
 int dia_get_levels(blomgpu_ctx *, double *bnds, int cap, int *ddm);
+int dia_alarm(blomgpu_ctx *, int alarm);     // alarm_phy(1) of the one output group, declared by the host
+// templvl salnlvl uvellvl vvellvl under cntiso_hybrid / plevel (stage_ale.hip forms them: phy/mod_ale_regrid_remap.F90:1059-1151, :1817-1853,
+// :1913-1949, :1986-2201): the level table on the device and the first plane of each selected slot in the accumulators, -1: not selected
+struct DiaHyb { int ddm; double *acc; const double *edges; int temp, saln, uvel, vvel; };
+bool dia_hybrid_slots(const blomgpu_ctx *, DiaHyb *);   // false: none of the four is selected (or the coordinate is isopyc_bulkml)
 int dia_step_check(blomgpu_ctx *);           // a selection that reads z / dz in a sequence without cmnfld1: fails
 bool dia_active(const blomgpu_ctx *);
 void dia_count(blomgpu_ctx *);

@@ -18,7 +18,11 @@
 // targets (a quadratic Bezier curve, :680-728) below the pressure-level range, minimum thicknesses, a bound on the variation of
 // neighbouring layer thicknesses (:848-913), and lateral smoothing of the interfaces where the stratification is weak
 // (regrid_smooth_jslice, :946-1020).
-// Neutral diffusion (ltedtp = 'neutral') is stage_ndiff.hip, called from here.  Not built: the z-level diagnostics (remap_trc_diazlv_jslice).
+// Neutral diffusion (ltedtp = 'neutral') is stage_ndiff.hip, called from here.
+// The z-level diagnostics templvl salnlvl uvellvl vvellvl (remap_trc_diazlv_jslice :1059-1151, the velocities' :1817-1853 and :1913-1949,
+// ale_remap_diazlv :1986-2201) are at the end of this file: a second map of each grid with n_dst = ddm, the reconstructions remapped onto
+// the depth levels and added to diaacc's accumulators -- inside the stage while the host's output alarm is 0, in st_ale_remap_diazlv when it
+// is 1 (blomgpu_dia_alarm).  Not built: the idlage level (:1132-1146).
 // Parity: cross-checked against the reference's REAL module compiled against a stand-in for mod_dia (oracle/Makefile
 // *_xale, tests/test_xcheck_ale.py) -- a cross-check, not a pin.
 #include "blomgpu_internal.h"
@@ -65,6 +69,12 @@ struct AleState {
   size_t nd_nrec = 0;                 // record space per face of the neutral diffusion
   int *nd_ks = nullptr, *nd_reck = nullptr;
   int nd_npc = 0;
+  // the depth levels of templvl salnlvl uvellvl vvellvl (rms_diazlv, :1436, :1477): a map of each grid with n_dst = ddm and their planes --
+  // the p-columns' ddm + 1 target edges and 2 ddm remapped planes (T, S), then the same for the 2 nplane velocity columns.  Allocated
+  // when one of the four names is first accumulated, rebuilt when the level table changes
+  blomgpu_h3m_map *map_zl = nullptr, *map_zl_uv = nullptr;
+  double *zl = nullptr;
+  int zl_ddm = 0;
 };
 
 void ale_free(blomgpu_ctx *c) {
@@ -88,6 +98,7 @@ void ale_free(blomgpu_ctx *c) {
   if (a->nd_rec) (void)hipFree(a->nd_rec);
   if (a->nd_recg) (void)hipFree(a->nd_recg);
   if (a->nd_reck) (void)hipFree(a->nd_reck);
+  if (a->zl) (void)hipFree(a->zl);
   delete a;
   c->ale = nullptr;
 }
@@ -875,14 +886,128 @@ __global__ void k_ale_uv_back(const DevView *__restrict__ Vp, int nn, const doub
   (isv ? V.f[F_v] : V.f[F_u])[c + (size_t)(k + nn) * V.nplane] = rm[c + (size_t)isv * V.nplane + (size_t)k * 2 * V.nplane];
 }
 
+// ---- templvl salnlvl uvellvl vvellvl on the depth levels ------------------------------------------------------------------------------
+// the maps with n_dst = ddm and their planes (AleState::zl)
+static int ale_zl_prepare(blomgpu_ctx *c, AleState *a, int ddm) {
+  if (a->zl && a->zl_ddm == ddm) return 0;
+  const DevView &h = c->h;
+  int rc;
+  if (a->map_zl) { blomgpu_h3m_map_free(a->map_zl); a->map_zl = nullptr; }
+  if (a->map_zl_uv) { blomgpu_h3m_map_free(a->map_zl_uv); a->map_zl_uv = nullptr; }
+  if (a->zl) { (void)hipFree(a->zl); a->zl = nullptr; }
+  a->zl_ddm = 0;
+  if ((rc = blomgpu_h3m_map_create(a->grid, &a->map_zl, ddm))) return ale_fail(c, "initialize_rms (diazlv)", rc);
+  if ((rc = blomgpu_h3m_map_create(a->grid_uv, &a->map_zl_uv, ddm))) return ale_fail(c, "initialize_rms (diazlv)", rc);
+  HIPCHK(c, hipMalloc((void **)&a->zl, sizeof(double) * ((size_t)3 * (ddm + 1) + (size_t)4 * ddm) * h.nplane));
+  a->zl_ddm = ddm;
+  return 0;
+}
+
+// The target edges of the depth levels, :1082-1088 | :1820-1826 | :1916-1922: p_dst(1) = p_src(1), p_dst(kd) = min(bnds(1,kd)*q, 1)*(p_src(kk+1) -
+// p_src(1)) + p_src(1) for kd = 2..ddm, p_dst(ddm+1) = p_src(kk+1), with q = 1/pbath | ubath | vbath (phy/mod_dia.F90:1078-1088).  uv = 0: the
+// p-columns (nplane of them); uv = 1: the u- (blockIdx.y = 0) and the v-columns (1) side by side, as grid_uv holds them.  A column the
+// engine leaves out gets unit edges.
+__global__ __launch_bounds__(256) void k_ale_zl_edges(const DevView *__restrict__ Vp, int uv, const double *__restrict__ psrcp, const int *__restrict__ activep,
+                                                      const double *__restrict__ edgep, int ddm, double *__restrict__ pdzp) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x;
+  if (t >= V.nplane) return;
+  const size_t np = V.nplane, nc = uv ? 2 * np : np, cc = (size_t)t + (size_t)by * np;
+  gcd_t psrc = global_ptr(psrcp) + cc, edge = global_ptr(edgep);
+  gd_t pdz = global_ptr(pdzp) + cc;
+  if (!global_ptr(activep)[cc]) {
+    for (int d = 0; d <= ddm; d++) pdz[(size_t)d * nc] = (double)d;
+    return;
+  }
+  double bath = V.f[F_depths][t];
+  if (uv) bath = fmin2(bath, V.f[F_depths][by ? t - V.ni : t - 1]);
+  const double q = 1. / bath, p1 = psrc[0], pb = psrc[(size_t)V.kk * nc];
+  pdz[0] = p1;
+  for (int d = 1; d < ddm; d++) pdz[(size_t)d * nc] = fmin2(edge[d] * q, 1.) * (pb - p1) + p1;
+  pdz[(size_t)ddm * nc] = pb;
+}
+
+// acc = acc + rm(kd) at the owned wet p-points (:1107-1110, :1124-1127); acc = acc + rm(kd) + ub | vb, added in that order, at the owned wet
+// u- | v-points (:1846-1848, :1942-1944; :2114-2116, :2187-2189).  blockIdx.y = level, blockIdx.z = field (T, S | u, v).
+struct ZlAdd { int pl[2], uv, blev; };      // first plane of each field's slot (-1: not selected); velocities; the plane of ub / vb (n - 1 | m - 1)
+__global__ __launch_bounds__(256) void k_ale_zl_add(const DevView *__restrict__ Vp, double *__restrict__ accp, const double *__restrict__ rmp, int ddm, const ZlAdd T) {
+  const DevView &V = *Vp;
+  unsigned bx, by;
+  xcd_block(bx, by);
+  const int t = bx * blockDim.x + threadIdx.x, d = by, f = blockIdx.z;
+  if (t >= V.nplane || T.pl[f] < 0) return;
+  const int i = t % V.ni - (NBDY - 1), j = t / V.ni - (NBDY - 1);
+  if (i < 1 || i > V.ii || j < 1 || j > V.jj) return;
+  if (!(T.uv ? (f ? V.m[I_iv][t] : V.m[I_iu][t]) : V.m[I_ip][t])) return;
+  const size_t np = V.nplane;
+  gd_t acc = global_ptr(accp) + ((size_t)t + (size_t)(T.pl[f] + d) * np);
+  gcd_t rm = global_ptr(rmp);
+  double a = acc[0];
+  if (T.uv) {
+    a = a + rm[(size_t)t + (size_t)f * np + (size_t)d * 2 * np];
+    a = a + (f ? V.f[F_vb] : V.f[F_ub])[(size_t)t + (size_t)T.blev * np];
+  } else a = a + rm[(size_t)t + ((size_t)f * ddm + d) * np];
+  acc[0] = a;
+}
+
+// remap_trc_diazlv_jslice (:1059-1151) for the whole tile: T's and S's reconstructions (a->trc[0..1], on the grid prepared with psrc) onto
+// the depth levels, added to templvl | salnlvl
+static int ale_zl_tracers(blomgpu_ctx *c, AleState *a, const DiaHyb &Z, const double *psrc) {
+  const DevView &h = c->h;
+  const size_t np = h.nplane;
+  const int ddm = Z.ddm;
+  TimeScope ts(c, "ale_diazlv_trc");
+  double *pdz = a->zl, *rmz = pdz + (size_t)(ddm + 1) * np;
+  hipLaunchKernelGGL(k_ale_zl_edges, plane_grid(h), dim3(256), 0, c->stream, c->d, 0, psrc, (const int *)a->active, Z.edges, ddm, pdz);
+  int rc;
+  if ((rc = blomgpu_h3m_prepare_remapping(a->grid, a->map_zl, pdz))) return ale_fail(c, "prepare_remapping (diazlv)", rc);
+  blomgpu_h3m_src *ss[2];
+  double *ud[2];
+  int nf = 0;
+  if (Z.temp >= 0) { ss[nf] = a->trc[0]; ud[nf++] = rmz; }
+  if (Z.saln >= 0) { ss[nf] = a->trc[1]; ud[nf++] = rmz + (size_t)ddm * np; }
+  if ((rc = blomgpu_h3m_remap_many(nf, ss, a->map_zl, ud))) return ale_fail(c, "remap (diazlv)", rc);
+  ZlAdd T;
+  T.pl[0] = Z.temp; T.pl[1] = Z.saln; T.uv = 0; T.blev = 0;
+  hipLaunchKernelGGL(k_ale_zl_add, dim3(plane_grid(h).x, ddm, 2), dim3(256), 0, c->stream, c->d, Z.acc, (const double *)rmz, ddm, T);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// :1817-1853 and :1913-1949 (:2087-2119, :2160-2192) for the whole tile: the velocities' reconstruction (a->vel, on grid_uv prepared with
+// ps2, the rescaled source interfaces of the u- and the v-columns) onto the depth levels, added to uvellvl | vvellvl with ub | vb of plane blev
+static int ale_zl_velocities(blomgpu_ctx *c, AleState *a, const DiaHyb &Z, const double *ps2, int blev) {
+  const DevView &h = c->h;
+  const size_t np = h.nplane;
+  const int ddm = Z.ddm;
+  TimeScope ts(c, "ale_diazlv_vel");
+  double *pdz = a->zl + (size_t)((ddm + 1) + 2 * ddm) * np, *rmz = pdz + (size_t)2 * (ddm + 1) * np;
+  hipLaunchKernelGGL(k_ale_zl_edges, plane_grid(h, 2), dim3(256), 0, c->stream, c->d, 1, ps2, (const int *)(a->active + np), Z.edges, ddm, pdz);
+  int rc;
+  if ((rc = blomgpu_h3m_prepare_remapping(a->grid_uv, a->map_zl_uv, pdz))) return ale_fail(c, "prepare_remapping (velocity, diazlv)", rc);
+  if ((rc = blomgpu_h3m_remap(a->vel, a->map_zl_uv, rmz))) return ale_fail(c, "remap (velocity, diazlv)", rc);
+  ZlAdd T;
+  T.pl[0] = Z.uvel; T.pl[1] = Z.vvel; T.uv = 1; T.blev = blev;
+  hipLaunchKernelGGL(k_ale_zl_add, dim3(plane_grid(h).x, ddm, 2), dim3(256), 0, c->stream, c->d, Z.acc, (const double *)rmz, ddm, T);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
 int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
-  (void)m; (void)n; (void)mm; (void)k1m;
+  (void)m; (void)mm; (void)k1m;
   const DevView &h = c->h;
   if (h.P.vcoord_tag == 1) return ctx_fail(c, "ale_regrid_remap: vcoord_type = 'isopyc_bulkml' has no ALE step (phy/mod_blom_step.F90:138-149)");
   if (h.P.vcoord_tag != 2 && h.P.vcoord_tag != 3) return ctx_fail(c, "ale_regrid_remap: unknown vertical coordinate");
   if (h.P.ltedtp_opt != 1 && h.P.ltedtp_opt != 2) return ctx_fail(c, "ale_regrid_remap: unknown ltedtp_opt");
   if (!c->ale_plevel) return ctx_fail(c, "ale_regrid_remap: the pressure levels are not set (blomgpu_set_vector \"plevel\", phy/mod_vcoord.F90:99)");
   if (int rc = ale_prepare(c)) return rc;
+  // the depth-level samples of this step are taken here while the alarm the previous step's diaout_alarms left is 0 (:1524-1531)
+  DiaHyb Z;
+  const bool zl = c->dia_alarm == 0 && dia_hybrid_slots(c, &Z);
+  if (zl)
+    if (int rc = ale_zl_prepare(c, (AleState *)c->ale, Z.ddm)) return rc;
   TimeScope ts(c, "ale_regrid_remap");
   AleState *a = (AleState *)c->ale;
   const size_t np = h.nplane, per = (size_t)h.kk * np;
@@ -1027,6 +1152,9 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
     c->seq.fluxes_zeroed = false;                   // utflx .. vsflx carry the diffusive fluxes now: advect must add to them
   }
   if ((rc = blomgpu_h3m_prepare_remapping(a->grid, a->map, pdst))) return ale_fail(c, "prepare_remapping", rc);
+  // T and S on the depth levels, from the reconstructions the layer remap is about to use (:1674-1677)
+  if (zl && (Z.temp >= 0 || Z.saln >= 0))
+    if (int rc2 = ale_zl_tracers(c, a, Z, psrc)) return rc2;
   const double *flx = ndiff ? a->nd_col + (size_t)8 * per : nullptr;
   // ---- velocities, :1692-1900 -------------------------------------------------------------------------------------------------
   // uvp: their scratch planes (where the tracers' scratch was, unless the neutral diffusion is still reading that)
@@ -1050,6 +1178,9 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
     if (int rc2 = join()) return rc2;
     if ((rc = blomgpu_h3m_remap(a->vel, a->map_uv, rm2))) return ale_fail(c, "remap (velocity)", rc);
     hipLaunchKernelGGL(k_ale_uv_back, dim3((unsigned)((np + 255) / 256), h.kk, 2), b, 0, c->stream, c->d, nn, (const double *)rm2);
+    // u and v on the depth levels, plus ub | vb (n) (:1817-1853, :1913-1949)
+    if (zl && (Z.uvel >= 0 || Z.vvel >= 0))
+      if (int rc2 = ale_zl_velocities(c, a, Z, ps2, n - 1)) return rc2;
     return 0;
   };
   bool vel_done = false;
@@ -1086,6 +1217,106 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
     if ((rc = h3m_sequence_end_deferred(a->grid)) || (rc = h3m_sequence_end_deferred(a->grid_uv))) return ale_fail(c, "sequence", rc);
     return 0;
   }
+  if ((rc = h3m_sequence_end(a->grid)) || (rc = h3m_sequence_end(a->grid_uv))) return ale_fail(c, "a column failed", rc);
+  return 0;
+}
+
+// ---- ale_remap_diazlv, :1986-2201: the sample of an output step, from the fields of time level m as the step left them -----------------
+// source interfaces of the owned wet p-columns from dp(k+mm) (reconstruct_trc_jslice with ilb = 1, iub = ii, :2031-2033, :207-210); the other
+// columns take no part
+__global__ __launch_bounds__(256) void k_ale_zl_p_src(const DevView *__restrict__ Vp, int mm, double *__restrict__ psrcp, int *__restrict__ activep) {
+  const DevView &V = *Vp;
+  PLANE_T(V);
+  const size_t np = V.nplane;
+  const bool col = j >= 1 && j <= V.jj && i >= 1 && i <= V.ii && V.m[I_ip][c];
+  global_ptr(activep)[c] = col;
+  gd_t psrc = global_ptr(psrcp) + c;
+  if (!col) {
+    for (int k = 0; k <= V.kk; k++) psrc[(size_t)k * np] = (double)k;
+    return;
+  }
+  double acc = V.f[F_p][c];
+  psrc[0] = acc;
+  for (int k = 0; k < V.kk; k++) {
+    acc = acc + V.f[F_dp][c + (size_t)(k + mm) * np];
+    psrc[(size_t)(k + 1) * np] = acc;
+  }
+}
+
+// :2060-2069 | :2133-2142: pu_tmp from pu(1) and dpu(k+mm), rescaled by q = min(p(i-1,j,kk+1), p(i,j,kk+1))/pu_tmp(kk+1) (v: j-1), and the
+// velocities of time level m, as columns c and nplane + c of grid_uv (blockIdx.y = 0: u, 1: v)
+__global__ __launch_bounds__(256) void k_ale_zl_uv_src(const DevView *__restrict__ Vp, int mm, double *__restrict__ psrcp, double *__restrict__ uinp,
+                                                       int *__restrict__ activep) {
+  const DevView &V = *Vp;
+  PLANE_T(V);
+  const int isv = blockIdx.y;
+  const size_t np = V.nplane, nc = 2 * np, cc = c + (size_t)isv * np;
+  const int kk = V.kk;
+  const bool col = j >= 1 && j <= V.jj && i >= 1 && i <= V.ii && (isv ? V.m[I_iv][c] : V.m[I_iu][c]);
+  global_ptr(activep)[cc] = col;
+  if (!col) return;                                              // the engine leaves the column out; k_ale_zl_edges gives it unit edges
+  gcd_t dpz = (isv ? V.f[F_dpv] : V.f[F_dpu]) + (c + (size_t)mm * np), uz = (isv ? V.f[F_v] : V.f[F_u]) + (c + (size_t)mm * np);
+  gcd_t pb = V.f[F_p] + (size_t)kk * np;
+  gd_t psrc = global_ptr(psrcp) + cc, uin = global_ptr(uinp) + cc;
+  const double p1 = (isv ? V.f[F_pv] : V.f[F_pu])[c];
+  double tot = p1;
+  for (int k = 0; k < kk; k++) tot = tot + dpz[(size_t)k * np];
+  const double q = fmin2(pb[isv ? c - V.ni : c - 1], pb[c]) / tot;
+  double a = p1;
+  psrc[0] = a * q;
+  for (int k = 0; k < kk; k++) {
+    a = a + dpz[(size_t)k * np];                                 // the same sums again: pu_tmp(k+1)
+    psrc[(size_t)(k + 1) * nc] = a * q;
+    uin[(size_t)k * nc] = uz[(size_t)k * np];
+  }
+}
+
+int st_ale_remap_diazlv(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
+  (void)n; (void)nn; (void)k1m; (void)k1n;
+  const DevView &h = c->h;
+  if (h.P.vcoord_tag == 1) return ctx_fail(c, "ale_remap_diazlv: vcoord_type = 'isopyc_bulkml' has no ALE step (phy/mod_blom_step.F90:271-273); its templvl salnlvl uvellvl vvellvl are diaacc's");
+  if (h.P.vcoord_tag != 2 && h.P.vcoord_tag != 3) return ctx_fail(c, "ale_remap_diazlv: unknown vertical coordinate");
+  // the sample of an output step: taken when this step's alarm is 1 (:2014-2017)
+  DiaHyb Z;
+  if (c->dia_alarm != 1 || !dia_hybrid_slots(c, &Z)) return 0;
+  if (int rc = ale_prepare(c)) return rc;
+  if (int rc = ale_zl_prepare(c, (AleState *)c->ale, Z.ddm)) return rc;
+  TimeScope ts(c, "ale_remap_diazlv");
+  AleState *a = (AleState *)c->ale;
+  const size_t np = h.nplane, per = (size_t)h.kk * np;
+  const dim3 g1((unsigned)((np + 255) / 256)), b(256);
+  int rc;
+  struct Unwind {
+    AleState *a; bool armed = true;
+    ~Unwind() {
+      if (!armed) return;
+      (void)h3m_sequence_end_deferred(a->grid);
+      (void)h3m_sequence_end_deferred(a->grid_uv);
+    }
+  } unwind{a};
+  if ((rc = h3m_sequence_begin(a->grid)) || (rc = h3m_sequence_begin(a->grid_uv))) return ale_fail(c, "sequence", rc);
+  if (Z.temp >= 0 || Z.saln >= 0) {                                    // :2026-2043
+    double *psrc = a->plane;
+    hipLaunchKernelGGL(k_ale_zl_p_src, g1, b, 0, c->stream, c->d, mm, psrc, a->active);
+    if ((rc = blomgpu_h3m_prepare_reconstruction(a->grid, psrc))) return ale_fail(c, "prepare_reconstruction (diazlv)", rc);
+    const double *us[2];
+    blomgpu_h3m_src *ss[2];
+    int nf = 0;
+    if (Z.temp >= 0) { us[nf] = h.f[F_temp] + (size_t)mm * np; ss[nf++] = a->trc[0]; }
+    if (Z.saln >= 0) { us[nf] = h.f[F_saln] + (size_t)mm * np; ss[nf++] = a->trc[1]; }
+    if ((rc = blomgpu_h3m_reconstruct_many(a->grid, nf, ss, us))) return ale_fail(c, "reconstruct (diazlv)", rc);
+    if (int rc2 = ale_zl_tracers(c, a, Z, psrc)) return rc2;
+  }
+  if (Z.uvel >= 0 || Z.vvel >= 0) {                                    // :2049-2199
+    double *ps2 = a->plane, *ui2 = ps2 + (size_t)2 * (h.kk + 1) * np;
+    hipLaunchKernelGGL(k_ale_zl_uv_src, dim3((unsigned)((np + 255) / 256), 2), b, 0, c->stream, c->d, mm, ps2, ui2, a->active + np);
+    if ((rc = blomgpu_h3m_prepare_reconstruction(a->grid_uv, ps2))) return ale_fail(c, "prepare_reconstruction (velocity, diazlv)", rc);
+    if ((rc = blomgpu_h3m_reconstruct(a->grid_uv, a->vel, ui2))) return ale_fail(c, "reconstruct (velocity, diazlv)", rc);
+    if (int rc2 = ale_zl_velocities(c, a, Z, ps2, m - 1)) return rc2;
+  }
+  (void)per;
+  HIPCHK(c, hipGetLastError());
+  unwind.armed = false;
   if ((rc = h3m_sequence_end(a->grid)) || (rc = h3m_sequence_end(a->grid_uv))) return ale_fail(c, "a column failed", rc);
   return 0;
 }

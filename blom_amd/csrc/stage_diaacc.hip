@@ -14,6 +14,9 @@
 //
 // The z-level (Levitus) accumulators -- diazlv (:4737-4993) + acclvl (:5709-5781), called per layer from diaacc (:2000-2053,
 // :2119-2168, :2222-2271) -- are k_dialvl further down: one thread per column of a grid, one launch per grid with a selected name.
+// Under cntiso_hybrid / plevel four of them -- templvl salnlvl uvellvl vvellvl -- are not diaacc's (:1944, :2059, :2174): stage_ale.hip remaps
+// the step's vertical reconstructions onto the levels and adds them to these slots (dia_hybrid_slots), at the start or at the end of a step
+// as the output alarm the host declares says (dia_alarm; phy/mod_ale_regrid_remap.F90:1524-1531, :2014-2017).
 //
 // The mass fluxes binned into the diagnostic density classes sigdia (:1368-1538) are k_diasig at the end of the kernels: one thread
 // per column of the u- or v-grid, the classes' bins of the step in LDS.  The first family that communicates: the one-point halo of
@@ -906,10 +909,11 @@ static bool hybrid_remapped(int r) {       // the level rows the hybrid coordina
 int dia_step_check(blomgpu_ctx *c) {
   if (c->dia && c->dia->ncls && c->h.P.vcoord_tag == 3)
     return ctx_fail(c, "blomgpu_step: a density-class accumulator is selected, which reads sigint; vcoord_type = 'plevel' never writes it");
-  if (c->dia && c->h.P.vcoord_tag != 1)
+  if (c->dia && c->h.P.vcoord_tag != 1 && c->dia_alarm < 0)
     for (int r : c->dia->rows)
       if (hybrid_remapped(r))
-        return ctx_fail(c, std::string("blomgpu_step: ") + g_rows[r].name + " is selected, which cntiso_hybrid / plevel form inside ale_regrid_remap (not built)");
+        return ctx_fail(c, std::string("blomgpu_step: ") + g_rows[r].name + " is selected, which cntiso_hybrid / plevel form inside ale_regrid_remap while the output alarm is 0 "
+                           "and in ale_remap_diazlv when it is 1 (phy/mod_ale_regrid_remap.F90:1524-1531, :2014-2017): the output alarm has not been declared (blomgpu_dia_alarm)");
   if (!c->dia || !c->dia->needs_z) return 0;
   if (c->h.P.vcoord_tag != 1 || c->cmnfld1 || c->full_physics) return 0;
   std::string names;
@@ -941,8 +945,9 @@ int dia_select(blomgpu_ctx *c, const char *names) {
       return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the two-equation closure (itrtke >= 1, gls = 1)");
     if ((g_rows[r].lev == LV_TKE || g_rows[r].lev == LV_GLS) && (c->h.P.itrtke > c->h.ntr || c->h.P.itrgls > c->h.ntr))
       return ctx_fail(c, "blomgpu_dia_select: " + nm + ": itrtke / itrgls outside 1..ntr");
-    if (c->h.P.vcoord_tag != 1 && hybrid_remapped(r))
-      return ctx_fail(c, "blomgpu_dia_select: " + nm + " is formed inside ale_regrid_remap under cntiso_hybrid / plevel (phy/mod_dia.F90:1944, :2059, :2174 leave it out): not built");
+    if (c->h.P.vcoord_tag != 1 && hybrid_remapped(r) && c->dia_alarm < 0)
+      return ctx_fail(c, "blomgpu_dia_select: " + nm + " is formed inside ale_regrid_remap under cntiso_hybrid / plevel (phy/mod_dia.F90:1944, :2059, :2174 leave it out), "
+                         "at the start or at the end of a step as the output alarm says (phy/mod_ale_regrid_remap.F90:1524-1531, :2014-2017): the output alarm has not been declared (blomgpu_dia_alarm)");
     if (g_rows[r].lyr == 3) {
       if (c->dia_sigdia.empty())
         return ctx_fail(c, "blomgpu_dia_select: " + nm + " needs the diagnostic density classes sigdia (blomgpu_dia_set_sigdia)");
@@ -1025,6 +1030,26 @@ int dia_select(blomgpu_ctx *c, const char *names) {
 }
 
 int dia_reset(blomgpu_ctx *c) { return c->dia ? dia_init(c, c->dia) : 0; }       // inifld, :5864
+
+// alarm_phy(1) (phy/mod_dia.F90: diaout_alarms) as the host declares it.  Under cntiso_hybrid / plevel it decides where templvl salnlvl
+// uvellvl vvellvl take their sample: inside ale_regrid_remap while it is 0 (phy/mod_ale_regrid_remap.F90:1524-1531), in ale_remap_diazlv
+// when it is 1 (:2014-2017).  A captured step sequence holds the launches of one value: a change drops the graphs, as a selection does.
+int dia_alarm(blomgpu_ctx *c, int alarm) {
+  if (alarm != 0 && alarm != 1) return ctx_fail(c, "blomgpu_dia_alarm: alarm = " + std::to_string(alarm) + ": alarm_phy is 0 or 1");
+  if (c->dia_alarm == alarm) return 0;
+  c->dia_alarm = alarm;
+  ctx_drop_graphs(c);
+  return 0;
+}
+
+bool dia_hybrid_slots(const blomgpu_ctx *c, DiaHyb *Z) {
+  const DiaState *S = c->dia;
+  if (!S || !S->ddm || c->h.P.vcoord_tag == 1) return false;
+  const auto plane = [&](const char *nm) { const int s = S->slot_of(find_row(nm)); return s < 0 ? -1 : S->plane0[s]; };
+  Z->ddm = S->ddm; Z->acc = S->acc; Z->edges = S->edges();
+  Z->temp = plane("templvl"); Z->saln = plane("salnlvl"); Z->uvel = plane("uvellvl"); Z->vvel = plane("vvellvl");
+  return Z->temp >= 0 || Z->saln >= 0 || Z->uvel >= 0 || Z->vvel >= 0;
+}
 
 int dia_nacc(blomgpu_ctx *c, int *nacc) {
   if (!nacc) return ctx_fail(c, "blomgpu_dia_nacc: null argument");
@@ -1246,6 +1271,7 @@ int st_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     for (size_t s = 0; s < S->rows.size(); s++) {
       const DiaRow &r = g_rows[S->rows[s]];
       if (r.lyr != 2 || r.grid != g || r.op >= OP_VFL) continue;
+      if (h.P.vcoord_tag != 1 && hybrid_remapped(S->rows[s])) continue;      // :1944, :2059, :2174 leave them out: stage_ale.hip forms them
       int *d = T.d[T.n++];
       d[0] = r.src;
       d[1] = r.lev == LV_MM ? mm : r.lev == LV_NN ? nn : r.lev == LV_TKE ? (h.P.itrtke - 1) * 2 * h.kk + mm : r.lev == LV_GLS ? (h.P.itrgls - 1) * 2 * h.kk + mm : 0;

@@ -4,9 +4,10 @@
 //   niw_ke_tendency, phy/mod_niw.F90:121-217: energy input by near-inertial waves from the change of the mixed layer's
 //   kinetic energy over a step, of the velocity deviations from a running time average (averaging time: the inertial period
 //   times 2, the period limited to the one at 10 N/S) -> idkedt, which mxlayr's turbulent kinetic energy balance reads.
-// NOT built: difest_common_iso, difest_vertical_iso, difest_lateral_iso (:353-586, :2040-3084: Richardson numbers, the
-// Eden-Greatbatch lateral and the shear / tidal / background vertical diffusivities): difint, difiso, difdia, difwgt stay as
-// uploaded.  Their module needs the CVMix library at module level, so nothing of them can be cross-checked in this image.
+// The diffusivity estimates themselves -- difest_common_iso, difest_vertical_iso, difest_lateral_iso (:353-586, :2040-3084: Richardson
+// numbers, the Eden-Greatbatch lateral and the shear / tidal / background vertical diffusivities) -- are stage_difest_iso.hip
+// (st_difest_isobml; option difest_live), cross-checked against the real module behind an interface-only CVMix stand-in
+// (tests/test_xcheck_difest.py).  Without that option difint, difiso, difdia, difwgt stay as uploaded.
 // Roofline: HBM; ~16 two-dimensional planes + 8 three-dimensional levels.
 #include "blomgpu_internal.h"
 #include "../../include/blomgpu.h"

@@ -105,6 +105,11 @@ module mod_blomgpu
       import :: c_ptr, c_int
       type(c_ptr), value :: c
     end function
+    integer(c_int) function blomgpu_dia_alarm(c, alarm) bind(C, name='blomgpu_dia_alarm')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), value :: alarm
+    end function
     integer(c_int) function blomgpu_dia_name_ext(index, buf, cap, kind, grid) bind(C, name='blomgpu_dia_name_ext')
       import :: c_int, c_char
       integer(c_int), value :: index, cap
@@ -250,8 +255,8 @@ module mod_blomgpu
   public :: init_fluxes, tmsmt1, tmsmt2, advect, pbcor1, pbcor2, diffus, pgforc, momtum, &
             diapfl, barotp, eddtra, convec, sfcstr, updtrc, init_cppm, halo_cmnfld2, halo_difest, mxlayr_tail, &
             cmnfld1, cmnfld2, ale_regrid_remap, ale_vdifft, ale_vdiffm, ale_forcing, &
-            cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc
-  public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext
+            cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc, ale_remap_diazlv
+  public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext, gpu_dia_alarm
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
@@ -605,6 +610,12 @@ contains
   subroutine gpu_dia_reset()                    ! inifld, phy/mod_dia.F90:5864
     call gpu_check(blomgpu_dia_reset(ctx), 'gpu_dia_reset')
   end subroutine
+  ! alarm_phy(1) of the one output group, 0 or 1: under cntiso_hybrid / plevel templvl salnlvl uvellvl vvellvl take their sample inside
+  ! ale_regrid_remap while it is 0 (phy/mod_ale_regrid_remap.F90:1524-1531), in ale_remap_diazlv when it is 1 (:2014-2017)
+  subroutine gpu_dia_alarm(alarm)
+    integer, intent(in) :: alarm
+    call gpu_check(blomgpu_dia_alarm(ctx, int(alarm, c_int)), 'gpu_dia_alarm')
+  end subroutine
   ! the depth levels of the *lvl names as depthslev_bnds(2,ddm) (phy/mod_dia.F90:119-128); refused while a *lvl name is selected
   subroutine gpu_dia_set_levels(bnds, ddm)
     integer, intent(in) :: ddm
@@ -683,6 +694,10 @@ contains
   subroutine ale_regrid_remap(m,n,mm,nn,k1m,k1n)   ! phy/mod_ale_regrid_remap.F90:1486 (vcoord 'plevel', 'cntiso_hybrid'/'direct')
     integer, intent(in) :: m,n,mm,nn,k1m,k1n
     call stage6('ale_regrid_remap',m,n,mm,nn,k1m,k1n)
+  end subroutine
+  subroutine ale_remap_diazlv(m,n,mm,nn,k1m,k1n)   ! phy/mod_ale_regrid_remap.F90:1986; called where blom_step does, phy/mod_blom_step.F90:271-273
+    integer, intent(in) :: m,n,mm,nn,k1m,k1n
+    call stage6('ale_remap_diazlv',m,n,mm,nn,k1m,k1n)
   end subroutine
   subroutine ale_vdifft(m,n,mm,nn,k1m,k1n)          ! phy/mod_ale_vdiff.F90:50
     integer, intent(in) :: m,n,mm,nn,k1m,k1n

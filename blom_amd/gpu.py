@@ -283,6 +283,17 @@ class BlomGpu:
     def dia_reset(self):
         self._chk(self.lib.blomgpu_dia_reset(self.ctx))
 
+    def dia_alarm(self, alarm):
+        """declare the reference's output alarm alarm_phy(1), 0 or 1: under cntiso_hybrid / plevel templvl salnlvl uvellvl vvellvl take
+        their sample inside ale_regrid_remap while it is 0 (phy/mod_ale_regrid_remap.F90:1524-1531) and in ale_remap_diazlv when it
+        is 1 (:2014-2017) -- blomgpu_dia_alarm"""
+        self._chk(self.lib.blomgpu_dia_alarm(self.ctx, C.c_int(int(alarm))))
+
+    def ale_remap_diazlv(self, m, n, mm, nn, k1m, k1n):
+        """the end-of-step sample of an output step (phy/mod_ale_regrid_remap.F90:1986-2201; phy/mod_blom_step.F90:271-273), with the
+        indices of the step that has just returned -- blomgpu_ale_remap_diazlv"""
+        self._chk(self.lib.blomgpu_ale_remap_diazlv(self.ctx, m, n, mm, nn, k1m, k1n))
+
     def dia_set_levels(self, bnds=None, levitus2x=False):
         """the depth levels of the *lvl names: bnds[ddm][2] (upper, lower bound in metres; increasing, contiguous), None for the
         default 35 levels, levitus2x=True for the reference's 70 -- blomgpu_dia_set_levels / blomgpu_dia_levels_levitus2x"""

@@ -36,6 +36,9 @@ FULL_STAGES_LIVE = tuple("difest_isobml" if s == "difest_isobml_pre" else s for 
 # list above: a host that steps stage by stage appends it (stages=FULL_STAGES + DIAG_STAGES); BlomGpu.step runs it by itself
 # whenever a selection exists.
 DIAG_STAGES = ("diaacc",)
+# ale_remap_diazlv (phy/mod_blom_step.F90:271-273; cntiso_hybrid / plevel only): the end-of-step sample of templvl salnlvl uvellvl
+# vvellvl on an output step.  Part of no step: the host calls it after the step while its output alarm (BlomGpu.dia_alarm) is 1.
+DIAG_OUTPUT_STAGES = ("ale_remap_diazlv",)
 
 STAGES_FROZEN_EDDY_FLUXES = tuple(s for s in DYNCORE_STAGES if s != "eddtra")    # umfltd.. stay as uploaded
 

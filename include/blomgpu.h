@@ -221,8 +221,8 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  *   usflxlvl umfltdlvl umflsmlvl utfltdlvl utflsmlvl utflldlvl usfltdlvl usflsmlvl usflldlvl", the same twelve on v, and on p
  *   "salnlvl templvl bfsqlvl difintlvl difisolvl difdialvl tkelvl gls_psilvl dzlvl".  They add no dependencies; "tkelvl" /
  *   "gls_psilvl" need what "tke" / "gls_psi" need; "dzlvl" reads cmnfld1's dz like "dz".  Under cntiso_hybrid / plevel the
- *   reference forms "uvellvl vvellvl salnlvl templvl" inside ale_regrid_remap (:1944, :2059, :2174 leave them out): those four
- *   are refused there.  blomgpu_dia_get returns ddm planes for a level name; blomgpu_dia_finalize applies msklvl (:6659-6738) to
+ *   reference forms "uvellvl vvellvl salnlvl templvl" inside ale_regrid_remap (:1944, :2059, :2174 leave them out): see
+ *   blomgpu_dia_alarm below; until the alarm has been declared those four are refused there.  blomgpu_dia_get returns ddm planes for a level name; blomgpu_dia_finalize applies msklvl (:6659-6738) to
  *   them: at every owned point the levels whose upper bound is not above the bottom become nf90_fill_double.  Not built:
  *   accilv (difvmolvl difvholvl difvsolvl), pvlvl, the tracer levels (:3688-3788).
  * blomgpu_dia_set_levels: the depth levels as bnds[ddm][2] = (upper, lower) bound of each level in metres, increasing and
@@ -230,6 +230,32 @@ int  blomgpu_set_vector(blomgpu_ctx *, const char *name, const double *v, int nv
  *   changes nothing.  bnds == NULL with ddm == 0 restores the default, the 35 levels of :111-128.
  * blomgpu_dia_levels_levitus2x: the 70 levels of LEVITUS2X (:130-159); refused while a level name is selected.
  * blomgpu_dia_get_levels: *ddm, and the first min(cap, ddm) rows of the bounds into bnds (may be NULL).
+ *
+ * "templvl salnlvl uvellvl vvellvl" under cntiso_hybrid / plevel: not diazlv's weights but a REMAP of that step's vertical
+ *   reconstructions (PLM / PPM / PQM, the ALE options) onto the depth levels, a second prepare_remapping + remap with n_dst = ddm
+ *   (phy/mod_ale_regrid_remap.F90:1059-1151 remap_trc_diazlv_jslice; u :1817-1853, v :1913-1949).  Target edges of a column:
+ *   p_dst(1) = p_src(1), p_dst(kd) = min(depthslev_bnds(1,kd)/bath, 1)*(p_src(kk+1) - p_src(1)) + p_src(1), p_dst(ddm+1) = p_src(kk+1),
+ *   bath = pbath | ubath | vbath.  acc = acc + rm(kd) for T and S, acc = acc + rm(kd) + ub | vb for u | v, at the owned wet points.
+ *   A step takes ONE sample, and which one depends on the reference's output alarm alarm_phy:
+ *     - while the alarm the previous step's diaout_alarms left is 0, ale_regrid_remap takes it (:1524-1531): time level n at the
+ *       START of the step, from the reconstructions the layer remap uses, plus ub | vb (n);
+ *     - when this step's alarm is 1, ale_remap_diazlv takes it (:2014-2017, phy/mod_blom_step.F90:271-273): time level m at the END
+ *       of the step, reconstructed afresh, plus ub | vb (m).
+ *   So a window of N steps holds N - 1 start-of-step samples and one end-of-step sample; the step after an output takes none at its
+ *   start.  The library cannot know the output schedule: the host declares it.
+ * blomgpu_dia_alarm: alarm_phy(1) of the one output group, 0 or 1 (anything else is refused); it holds until set again.  A fresh
+ *   context is UNDECLARED, and while it is, the four names stay refused under cntiso_hybrid / plevel at blomgpu_dia_select and at
+ *   blomgpu_step (without a declared alarm the sums would not be the reference's).  With alarm 0 the stage ale_regrid_remap (inside
+ *   blomgpu_step and through blomgpu_stage) accumulates the selected ones of the four; with alarm 1 it does not.  blomgpu_step never
+ *   changes the alarm.  A change drops captured step graphs (option "use_graph"), as a selection does.  Under isopyc_bulkml the
+ *   alarm is ignored: the four names are diaacc's (k_dialvl) as before.
+ * blomgpu_ale_remap_diazlv: phy/mod_ale_regrid_remap.F90:1986-2201 with its arguments (also blomgpu_stage "ale_remap_diazlv").
+ *   Accumulates the selected ones of the four names when the alarm is 1; does nothing when it is 0 or undeclared or none is
+ *   selected; refused under isopyc_bulkml.  The host calls it where blom_step does: after blomgpu_step has returned, with the
+ *   indices of that last step, before blomgpu_dia_finalize.  blomgpu_step never calls it.  The reference's window of N steps:
+ *     blomgpu_dia_alarm(1); step(1); blomgpu_dia_alarm(0); step(N-1); blomgpu_dia_alarm(1); blomgpu_ale_remap_diazlv(..); finalize
+ *   nacc counts as before (diaacc, once per step); blomgpu_dia_finalize's msklvl and blomgpu_dia_reset treat the four like every
+ *   level row.  Not built: the idlage level (:1132-1146).
  *
  * Density-class names (6, kind 3; :1368-1538): the mass fluxes binned into the diagnostic density classes sigdia with THAT step's
  *   interface densities and a search index carried down the column -- "umfll umfltdl umflsml" on u (acclyr :1457, :1461, :1465;
@@ -295,6 +321,8 @@ int  blomgpu_dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
 int  blomgpu_dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);
 int  blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid);
 int  blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
+int  blomgpu_dia_alarm(blomgpu_ctx *, int alarm);
+int  blomgpu_ale_remap_diazlv(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
