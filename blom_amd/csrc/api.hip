@@ -191,6 +191,8 @@ struct Opt {
 #define CI(nm) {#nm, O_INT, IN_C(nm), 0}
 #define CB(nm) {#nm, O_BOOL, IN_C(nm), 0}
 #define ONE_OR_TWO(msg) [](double &v) -> const char * { return v != 1 && v != 2 ? msg : nullptr; }
+// (a declared context allocates the option's 48-level array when the option is switched on, outside the step: stage_thermf_cesm.hip)
+#define RLX(nm, fid) {#nm, O_BOOL, IN_C(nm), 0, nullptr, [](blomgpu_ctx *c) { if (c->nm && c->cesm_declared) (void)cesm_field(c, fid); }}
 #define LMI(n) {"l" #n "mi", O_INT, [](blomgpu_ctx *c) { return Slot(c->lmi[n - 1]); }, 0, \
                 [](double &v) -> const char * { return v < 1 || v > 12 ? "blomgpu_set_int: l" #n "mi is a month, 1..12" : nullptr; }}
 static const Opt g_opts[] = {
@@ -222,7 +224,7 @@ static const Opt g_opts[] = {
   {"edwmth_opt", O_INT, IN_C(edwmth_opt), 0, ONE_OR_TWO(" readnml_diffusion: edwmth is unsupported!")},
   {"full_physics", O_BOOL, IN_C(full_physics), 0, nullptr, [](blomgpu_ctx *c) { if (c->full_physics) c->live_slopes = true; }},
   // thermf: mod_forcing's switches (phy/mod_forcing.F90:43-47), mod_time's months of the interpolation, mod_ben02's ntda
-  CB(aptflx), CB(apsflx), CB(ditflx), CB(disflx), CB(srxbal), LMI(1), LMI(2), LMI(3), LMI(4), LMI(5), CI(ntda),
+  RLX(aptflx, F_tflxap), RLX(apsflx, F_sflxap), RLX(ditflx, F_tflxdi), RLX(disflx, F_sflxdi), CB(srxbal), LMI(1), LMI(2), LMI(3), LMI(4), LMI(5), CI(ntda),
   // (the stage timers select nothing: a step with them runs plain launches beside the graphs, which stay)
   {"timing", O_BOOL, IN_C(timing), KEEP_GRAPHS},
   CI(barotp_fused),
@@ -271,6 +273,13 @@ static const Opt g_opts[] = {
   {"ale_velocity_limiting", O_STR, IN_C(ale_velocity_limiting), ALE_RESET, nullptr, nullptr, " readnml_ale_regrid_remap: velocity_limiting = ",
    {{"monotonic", 201}, {"non_oscillatory", 203}}},
 };
+// The coupled experiment's options (stage_thermf_cesm.hip), a table of their own behind the same setters: mod_cesm's smtfrc, nstep_in_cpl,
+// l1ci, l2ci (cesm/mod_cesm.F90:55-103), mod_forcing's use_stream_relaxation, mod_time's nstep_in_day and nday_of_year (nstep and
+// nday_in_year stand in the table above), and the A/B switch of thermf_cesm's sums.  blomgpu_option_name lists the table above only:
+// its rows are pinned name by name (tests/test_option_table.py), and these names mean nothing until blomgpu_inifrc_cesm has been called.
+static const Opt g_cesm_opts[] = {
+  CB(smtfrc), CB(use_stream_relaxation), CI(nstep_in_cpl), CI(l1ci), CI(l2ci), CI(nstep_in_day), CI(nday_of_year), CI(cesm_single_sums),
+};
 #undef IN_P
 #undef IN_C
 #undef PR
@@ -281,8 +290,11 @@ static const Opt g_opts[] = {
 #undef CB
 #undef ONE_OR_TWO
 #undef LMI
+#undef RLX
 static const Opt *find_opt(std::string_view name, unsigned kinds) {      // kinds: bit per OptKind
   for (const Opt &o : g_opts)
+    if (name == o.name && (kinds >> o.kind & 1)) return &o;
+  for (const Opt &o : g_cesm_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   return nullptr;
 }
@@ -360,6 +372,10 @@ int blomgpu_create(const blomgpu_dims *d, blomgpu_ctx **out) {
   id++;
   BLOM_REAL_FIELDS(X)
 #undef X
+  // (the coupled experiment's fields: level counts only -- no name and no memory until blomgpu_inifrc_cesm)
+#define X(name, lev) c->nlev_real[id++] = (lev);
+  BLOM_CESM_REAL_FIELDS(X)
+#undef X
   id = 0;
 #define X(name, lev)                                                                   \
   c->nlev_int[id] = (lev);                                                             \
@@ -367,12 +383,15 @@ int blomgpu_create(const blomgpu_dims *d, blomgpu_ctx **out) {
   id++;
   BLOM_INT_FIELDS(X)
 #undef X
-  for (int f = 0; f < NF_REAL; f++) {
+#define X(name, lev) c->nlev_int[id++] = (lev);
+  BLOM_CESM_INT_FIELDS(X)
+#undef X
+  for (int f = 0; f < NF_BASE_REAL; f++) {
     size_t bytes = sizeof(double) * (size_t)c->nlev_real[f] * h.nplane;
     HIPCHK(c, hipMalloc((void **)&h.f[f], bytes));
     HIPCHK(c, hipMemsetAsync(h.f[f], 0, bytes, c->stream));
   }
-  for (int f = 0; f < NF_INT; f++) {
+  for (int f = 0; f < NF_BASE_INT; f++) {
     size_t bytes = sizeof(int) * (size_t)c->nlev_int[f] * h.nplane;
     HIPCHK(c, hipMalloc((void **)&h.m[f], bytes));
     HIPCHK(c, hipMemsetAsync(h.m[f], 0, bytes, c->stream));
@@ -437,6 +456,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   if (c->bt_flags) (void)hipFree(c->bt_flags);
   ale_free(c);
   dia_free(c);
+  cesm_free(c);
   if (c->ale_plevel) (void)hipFree(c->ale_plevel);
   if (c->arc_strip) (void)hipFree(c->arc_strip);
   if (c->xcsum_buf) (void)hipFree(c->xcsum_buf);
@@ -484,6 +504,16 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   // sequence on plain launches: correct, and a few per cent slower -- a caller that times steps wants to know)
   if (s == "graph_steps") { *v = c->graph_steps; return 0; }
   if (s == "graph_failures") { *v = c->graph_failures; return 0; }
+  // thermf_cesm's correction of the virtual salt flux (cesm/mod_thermf_cesm.F90:342-343), from the sum the last thermf left on the device
+  if (s == "thermf_cesm_launches") { *v = (double)c->cesm_launches; return 0; }      // (counted where they are issued, single tile)
+  if (s == "sflxc") {
+    if (!c->cesm_declared) return ctx_fail(c, "blomgpu_get_real: sflxc exists once blomgpu_inifrc_cesm has been called");
+    double sum = 0.;
+    HIPCHK(c, hipMemcpyAsync(&sum, c->cesm_sums, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *v = sum / c->area;
+    return 0;
+  }
   // diagnostic counters of mxlayr (stage_mxlayr.hip): columns whose iteration for the mixed layer depth ended at its limit since the last
   // query, named by the message the reference prints for such a column: "mxlayr_maxitr_detrain" = the first iteration
   // (phy/mod_mxlayr.F90:437-449, 'reached maxitr when detraining', :440; word 5), "mxlayr_maxitr_entrain" = the second
@@ -525,6 +555,20 @@ int blomgpu_field_info(blomgpu_ctx *c, const char *name, int *nlev, int *is_int)
   return ctx_fail(c, std::string("unknown field ") + name);
 }
 
+// The device pointer of level lev0 (1-based) of a named real field, nlev levels of which must exist -- the one place where the entry points
+// that take a field by name resolve it.  A 48-level array of the coupled experiment that has no memory yet gets it here (cesm_field).
+static int real_levels(blomgpu_ctx *c, const char *who, const char *name, int lev0, int nlev, double **ptr) {
+  if (!c || !name) return ctx_fail(c, std::string(who) + ": null argument");
+  auto it = c->real_ids.find(name);
+  if (it == c->real_ids.end()) return ctx_fail(c, std::string(who) + ": unknown field " + name);
+  if (lev0 < 1 || nlev < 1 || lev0 - 1 + nlev > c->nlev_real[it->second])
+    return ctx_fail(c, std::string(who) + ": levels out of range for field " + name + " (lev0 is 1-based)");
+  if (int rc = cesm_field(c, it->second)) return rc;
+  if (!c->h.f[it->second]) return ctx_fail(c, std::string(who) + ": field " + name + " has no memory");
+  *ptr = c->h.f[it->second] + (size_t)(lev0 - 1) * c->h.nplane;
+  return 0;
+}
+
 static int locate(blomgpu_ctx *c, const char *name, int nlev, void **ptr, size_t *bytes) {
   int nl, isint;
   if (blomgpu_field_info(c, name, &nl, &isint)) return 1;
@@ -533,6 +577,7 @@ static int locate(blomgpu_ctx *c, const char *name, int nlev, void **ptr, size_t
     *ptr = c->h.m[c->int_ids[name]];
     *bytes = sizeof(int) * (size_t)nlev * c->h.nplane;
   } else {
+    if (int rc = cesm_field(c, c->real_ids[name])) return rc;      // (a 48-level array of the coupled experiment, on first use)
     *ptr = c->h.f[c->real_ids[name]];
     *bytes = sizeof(double) * (size_t)nlev * c->h.nplane;
   }
@@ -546,6 +591,16 @@ int blomgpu_upload(blomgpu_ctx *c, const char *name, const void *host, int nlev)
   HIPCHK(c, hipStreamSynchronize(c->stream));
   const std::string s(name);
   if (s == "ip" || s == "iu" || s == "iv" || s == "iq") return ctx_pack_masks(c);
+  return 0;
+}
+
+// one level (1-based) of a real field from a host plane: a coupling interval refreshes level l2ci of the _da pairs alone
+int blomgpu_upload_level(blomgpu_ctx *c, const char *name, const void *host, int lev) {
+  if (!host) return ctx_fail(c, "blomgpu_upload_level: null argument");
+  double *base = nullptr;
+  if (int rc = real_levels(c, "blomgpu_upload_level", name, lev, 1, &base)) return rc;
+  HIPCHK(c, hipMemcpyAsync(base, host, sizeof(double) * (size_t)c->h.nplane, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return 0;
 }
 
@@ -564,30 +619,25 @@ int blomgpu_set_masks(blomgpu_ctx *c, const int *ip, const int *iu, const int *i
 }
 
 int blomgpu_xctilr(blomgpu_ctx *c, const char *name, int lev0, int l1, int ld, int mh, int nh, int itype) {
-  auto it = c->real_ids.find(name);
-  if (it == c->real_ids.end()) return ctx_fail(c, std::string("xctilr: unknown field ") + name);
-  int nl = c->nlev_real[it->second];
-  if (lev0 < 1 || l1 < 1 || lev0 - 1 + ld > nl) return ctx_fail(c, "xctilr: level range outside field");
+  if (l1 < 1) return ctx_fail(c, "xctilr: level range outside field");
+  double *base = nullptr;
+  if (int rc = real_levels(c, "xctilr", name, lev0, ld, &base)) return rc;
   ctx_sync_view(c);
-  return st_xctilr(c, c->h.f[it->second] + (size_t)(lev0 - 1) * c->h.nplane, l1, ld, mh, nh, itype);
+  return st_xctilr(c, base, l1, ld, mh, nh, itype);
 }
 
 int blomgpu_crc(blomgpu_ctx *c, const char *name, int lev0, int nlev, int itype, unsigned *crc) {
-  auto it = c->real_ids.find(name);
-  if (it == c->real_ids.end()) return ctx_fail(c, std::string("crc: unknown field ") + name);
-  if (lev0 < 1 || nlev < 1 || lev0 - 1 + nlev > c->nlev_real[it->second])
-    return ctx_fail(c, std::string("crc: levels out of range for field ") + name + " (lev0 is 1-based)");
+  double *base = nullptr;
+  if (int rc = real_levels(c, "crc", name, lev0, nlev, &base)) return rc;
   ctx_sync_view(c);
-  return st_crc(c, c->h.f[it->second] + (size_t)(lev0 - 1) * c->h.nplane, nlev, itype, crc);
+  return st_crc(c, base, nlev, itype, crc);
 }
 
 int blomgpu_crc_strips(blomgpu_ctx *c, const char *name, int lev0, int nlev, int itype, unsigned *out, int cap, int *l0, int *ns) {
-  auto it = c->real_ids.find(name);
-  if (it == c->real_ids.end()) return ctx_fail(c, std::string("crc_strips: unknown field ") + name);
-  if (lev0 < 1 || nlev < 1 || lev0 - 1 + nlev > c->nlev_real[it->second])
-    return ctx_fail(c, std::string("crc_strips: levels out of range for field ") + name);
+  double *base = nullptr;
+  if (int rc = real_levels(c, "crc_strips", name, lev0, nlev, &base)) return rc;
   ctx_sync_view(c);
-  return st_crc_strips(c, c->h.f[it->second] + (size_t)(lev0 - 1) * c->h.nplane, nlev, itype, out, cap, l0, ns);
+  return st_crc_strips(c, base, nlev, itype, out, cap, l0, ns);
 }
 
 // names of the registered fields, in registry order (reals first): lets a host scatter a whole state over tiles
@@ -652,11 +702,10 @@ int blomgpu_dia_get_sigdia(blomgpu_ctx *c, double *out, int cap, int *n) { retur
 // not part of this path.
 // xcsum of level `lev` (1-based) of a named field, mask by grid type as in xctilr/xccrc (p-grid: ips)
 int blomgpu_xcsum(blomgpu_ctx *c, const char *name, int lev, int itype, double *sum) {
+  double *base = nullptr;
+  if (int rc = real_levels(c, "blomgpu_xcsum", name, lev, 1, &base)) return rc;
   ctx_sync_view(c);
-  auto it = c->real_ids.find(name);
-  if (it == c->real_ids.end()) return ctx_fail(c, std::string("blomgpu_xcsum: unknown field ") + name);
-  if (lev < 1 || lev > c->nlev_real[it->second]) return ctx_fail(c, "blomgpu_xcsum: level out of range");
-  return st_xcsum(c, c->h.f[it->second] + (size_t)(lev - 1) * c->h.nplane, itype, sum);
+  return st_xcsum(c, base, itype, sum);
 }
 // exp(), pow(), sin() and atan2() as the kernels evaluate them (exp_libm.h, pow_libm.h, sin_libm.h, atan2_libm.h), elementwise on
 // host arrays: lets a caller check that the device returns the bits of its own libm (tests/test_exp_libm.py, test_pow_libm.py,
@@ -705,13 +754,57 @@ int blomgpu_sfcstr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
   (void)m; (void)n; (void)mm; (void)nn; (void)k1m; (void)k1n;
   const std::string &e = c->expcnf;
   if (e == "noforcing" || e == "fuk95" || e == "channel") return 0;
-  if (e == "cesm" || e == "ben02clim" || e == "ben02syn" || e == "single_column")
+  if (cesm_on(c)) return st_sfcstr_cesm(c);
+  if (e == "cesm")
+    return ctx_fail(c, " sfcstr: expcnf = " + e + " is not built on the device (sfcstr_cesm / sfcstr_ben02) until blomgpu_inifrc_cesm has been called");
+  if (e == "ben02clim" || e == "ben02syn" || e == "single_column")
     return ctx_fail(c, " sfcstr: expcnf = " + e + " is not built on the device (sfcstr_cesm / sfcstr_ben02)");
   return ctx_fail(c, " sfcstr: expcnf = " + e + " is unsupported!");          // :54-60
 }
 int blomgpu_init_cppm(blomgpu_ctx *c) { ctx_sync_view(c); return st_init_cppm(c); }   // phy/mod_cppm.F90:2504
 int blomgpu_mxlayr_tail(blomgpu_ctx *c, int nn, int k1n) { ctx_sync_view(c); return st_mxlayr_tail(c, nn, k1n); }
-int blomgpu_thermf(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) { ctx_sync_view(c); return st_thermf(c, m, n, mm, nn, k1m, k1n); }
+int blomgpu_thermf(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
+  if (cesm_on(c)) {
+    if (int rc = check_tracer_options(c)) return rc;
+    return st_thermf_cesm(c, m, n, mm, nn, k1m, k1n);
+  }
+  if (c->expcnf == "cesm") return ctx_fail(c, "thermf: expcnf = cesm is not built on the device until blomgpu_inifrc_cesm has been called");
+  ctx_sync_view(c);
+  return st_thermf(c, m, n, mm, nn, k1m, k1n);
+}
+// The coupled experiment (expcnf = 'cesm').  blomgpu_inifrc_cesm is inifrc_cesm (cesm/mod_cesm.F90:175-200) and the declaration that the
+// coupler's forcing exists; blomgpu_getfrc_cesm is getfrc_cesm (:202-263); blomgpu_cesm_nflxdi returns mod_forcing's nflxdi(48).
+int blomgpu_inifrc_cesm(blomgpu_ctx *c) { return c ? cesm_inifrc(c) : ctx_fail(c, "blomgpu_inifrc_cesm: null argument"); }
+int blomgpu_getfrc_cesm(blomgpu_ctx *c) { return st_getfrc_cesm(c); }
+int blomgpu_cesm_nflxdi(blomgpu_ctx *c, int *out) {
+  if (!c || !out) return ctx_fail(c, "blomgpu_cesm_nflxdi: null argument");
+  for (int k = 0; k < 48; k++) out[k] = c->nflxdi[k];
+  return 0;
+}
+// xcsum of the levels lev0 .. lev0 + nlev - 1 (1-based) of a named field at once, through the kernels thermf_cesm's sums take
+// (halo.hip: st_xcsum_batch); mask: "ips", or the name of an integer field whose points equal to 1 are summed
+int blomgpu_xcsum_batch(blomgpu_ctx *c, const char *name, int lev0, int nlev, const char *mask, double *sums) {
+  if (!c || !name || !mask || !sums) return ctx_fail(c, "blomgpu_xcsum_batch: null argument");
+  double *base = nullptr;
+  if (int rc = real_levels(c, "blomgpu_xcsum_batch", name, lev0, nlev, &base)) return rc;
+  ctx_sync_view(c);
+  const int *mk = nullptr;
+  if (std::string(mask) != "ips") {
+    auto jt = c->int_ids.find(mask);
+    if (jt == c->int_ids.end() || c->nlev_int[jt->second] != 1) return ctx_fail(c, std::string("blomgpu_xcsum_batch: unknown mask ") + mask);
+    mk = c->h.m[jt->second];
+  }
+  std::vector<const double *> planes;
+  std::vector<const int *> masks(nlev, mk);
+  for (int q = 0; q < nlev; q++) planes.push_back(base + (size_t)q * c->h.nplane);
+  double *dev = nullptr;
+  HIPCHK(c, hipMalloc((void **)&dev, sizeof(double) * (size_t)nlev * (c->h.jtdm + 1)));
+  int rc = st_xcsum_batch(c, nlev, planes.data(), masks.data(), dev + nlev, dev);
+  if (!rc && hipMemcpyAsync(sums, dev, sizeof(double) * nlev, hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = 1;
+  if (hipStreamSynchronize(c->stream) != hipSuccess) rc = 1;
+  (void)hipFree(dev);
+  return rc ? (c->err.empty() ? ctx_fail(c, "blomgpu_xcsum_batch: copy or launch failed") : 1) : 0;
+}
 int blomgpu_mxlayr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) { ctx_sync_view(c); return st_mxlayr(c, m, n, mm, nn, k1m, k1n); }
 int blomgpu_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {   // phy/mod_ale_regrid_remap.F90:1486
   ctx_sync_view(c);
@@ -806,7 +899,7 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
   X(mxlayr_tail, blomgpu_mxlayr_tail(c, nn, k1n)) X(mxlayr, blomgpu_mxlayr(ALL6)) X(thermf, blomgpu_thermf(ALL6))                 \
   X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
   X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6)) \
-  X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6))
+  X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6)) X(getfrc_cesm, blomgpu_getfrc_cesm(c))
 enum StageId {
 #define X(nm, call) S_##nm,
   BLOM_STAGES(X)
@@ -837,6 +930,13 @@ static int step_sequence(STAGE_ARGS) {
                                     S_ale_vdifft, S_ale_vdiffm, S_updtrc, S_barotp, S_pbcor2, S_tmsmt2, S_cmnfld1};
   const auto stage = [&](StageId id) { return g_stages[id].entry(ALL6); };
   const bool ale = c->h.P.vcoord_tag != 1;
+  // The coupled experiment, once its forcing is declared (stage_thermf_cesm.hip): getfrc_cesm behind init_fluxes (phy/mod_blom_step.F90:116),
+  // sfcstr in front of pgforc (:163), and under the hybrid coordinates thermf behind momtum (:188; the isopycnic full-physics
+  // sequence has its thermf already).  None of the three touches the flux arrays the lean init_fluxes leaves for advect, and none
+  // reads or writes what the second stream holds at that point: the viscous chain of momtum reads no wind stress (k_mom_cor_march
+  // does, behind pgforc), and thermf_cesm beside diapfl's momentum mixing reads p, dp, temp, saln, trc and writes surface planes only
+  // (tools/kernel_rw_sets.py: k_diapfl_momentum / k_diapfl_dpudpv write u, v, dpu, dpv).
+  const bool cesm = cesm_on(c);
   c->seq = StepState{};
   c->seq.defer_checks = c->seq.in_sequence = true;
   {
@@ -853,7 +953,13 @@ static int step_sequence(STAGE_ARGS) {
       for (const StageId st : seq_ale) {
         if (c->tmsmt1_done_ahead && st == S_tmsmt1) { c->tmsmt1_done_ahead = false; continue; }
         if (c->eddtra_frozen && st == S_eddtra) continue;
+        if (cesm && st == S_pgforc)
+          if (int rc = stage(S_sfcstr)) return rc;
         if (int rc = stage(st)) return rc;
+        if (cesm && st == S_init_fluxes)
+          if (int rc = stage(S_getfrc_cesm)) return rc;
+        if (cesm && st == S_momtum)
+          if (int rc = stage(S_thermf)) return rc;
       }
     } else for (const StageId st : seq) {
       // live_slopes: cmnfld2 (the halo updates plus buoyancy frequency and neutral slopes) in place of its halo part alone
@@ -885,7 +991,11 @@ static int step_sequence(STAGE_ARGS) {
         c->seq.diapfl_mom_on_side = c->seq.updtrc_on_side = false;
         if (ctx_side_done(c, ev) || ctx_side_join(c, ev)) return 1;
       }
+      if (cesm && st == S_pgforc)
+        if (int rc = stage(S_sfcstr)) return rc;
       if (int rc = stage(run)) return rc;
+      if (cesm && st == S_init_fluxes)
+        if (int rc = stage(S_getfrc_cesm)) return rc;
       // cmnfld2's kernels still alone on the second stream (frozen diffusivities: difest_isobml did not wait for them): eddtra reads the slopes
       if (st == S_halo_difest && c->seq.cmn_on_side) {
         c->seq.cmn_on_side = false;
@@ -918,6 +1028,8 @@ static int step_sequence(STAGE_ARGS) {
 int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
   const int kk = c->h.kk;
   if (int rc = dia_step_check(c)) return rc;
+  if (cesm_on(c) && c->use_graph)
+    return ctx_fail(c, "blomgpu_step: the coupled experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
   for (int it = 0; it < nsteps; it++) {
     const int ns = *nstep;
     const int m = ns % 2 + 1, n = (ns + 1) % 2 + 1;

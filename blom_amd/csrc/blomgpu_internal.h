@@ -100,18 +100,34 @@
   /* (K+1)-level work fields (phip of pgforc_geopotential, ...) */                       \
   X(wkp0, K + 1) X(wkp1, K + 1)
 
+// The coupled experiment's forcing (expcnf = 'cesm': cesm/mod_cesm.F90:61-97, phy/mod_forcing.F90; stage_thermf_cesm.hip).  These arrays do
+// not exist until blomgpu_inifrc_cesm declares the coupler's forcing: they have ids and level counts from the start, but no memory and no
+// name in the registry.  The declaration allocates them -- the four 48-level arrays of the diagnosed relaxation fluxes
+// (phy/mod_forcing.F90:95-100) only when the first of them is uploaded, downloaded or used by thermf (cesm_field).  thermf_util: the area
+// weighted planes the global sums of thermf_cesm run over (the reference's util1: one for salt, then one per tracer).
+#define BLOM_CESM_REAL_FIELDS(X)                                                                                                 \
+  X(ustarw_da, 2) X(lip_da, 2) X(sop_da, 2) X(eva_da, 2) X(rnf_da, 2) X(rfi_da, 2) X(fmltfz_da, 2) X(sfl_da, 2) X(swa_da, 2)     \
+  X(nsf_da, 2) X(hmlt_da, 2) X(ficem_da, 2) X(ztx_da, 2) X(mty_da, 2)                                                            \
+  X(hmlt, 1) X(frzpot, 1) X(mltpot, 1) X(ztx, 1) X(mty, 1) X(sst_stream, 1) X(sss_stream, 1) X(ice_stream, 1)                    \
+  X(tflxap, 48) X(sflxap, 48) X(tflxdi, 48) X(sflxdi, 48) X(thermf_util, NT + 1)
+#define BLOM_CESM_INT_FIELDS(X) X(ipwocn, 1)
+
 #define BLOM_INT_FIELDS(X) X(ip, 1) X(iu, 1) X(iv, 1) X(iq, 1) X(kfpla, 2) X(kming, 1) X(cppm_sti, 1) X(cppm_stj, 1) X(mpack, 1) \
   /* mod_difest: kmax, kfil, msku, mskv (mod_difest.F90:97-100) */ X(dfe_kmax, 1) X(dfe_kfil, 1) X(msku, K) X(mskv, K)
 
 enum FieldId {
 #define X(name, lev) F_##name,
   BLOM_REAL_FIELDS(X)
+      NF_BASE_REAL, F_before_cesm_ = NF_BASE_REAL - 1,      // (the fields below continue the numbering)
+  BLOM_CESM_REAL_FIELDS(X)
 #undef X
       NF_REAL
 };
 enum IFieldId {
 #define X(name, lev) I_##name,
   BLOM_INT_FIELDS(X)
+      NF_BASE_INT, I_before_cesm_ = NF_BASE_INT - 1,
+  BLOM_CESM_INT_FIELDS(X)
 #undef X
       NF_INT
 };
@@ -327,6 +343,11 @@ struct blomgpu_ctx {
   double bdml_logc = 0.;         // log(2 bvf0 / cori30) of the host's libm (set with the plane bdmlq when bdmldp is on)
   int eddf2d = 0, edsprs = 1, edanis = 0, redi3d = 0, rhsctp = 0, edfsmo = 0;   // (rhsctp: topographic Rhines scale, sin_libm.h, atan2_libm.h)
   int edritp_opt = 2, edwmth_opt = 1;   // 1 'shear', 2 'large scale'; 1 'smooth', 2 'step' (phy/mod_diffusion.F90:113-116)
+  // the coupled experiment (expcnf = 'cesm'; stage_thermf_cesm.hip): mod_cesm's smtfrc, nstep_in_cpl, l1ci, l2ci (cesm/mod_cesm.F90:55-103),
+  // mod_forcing's use_stream_relaxation, mod_time's nstep_in_day and nday_of_year (nstep and nday_in_year live in Params)
+  bool smtfrc = false, use_stream_relaxation = false;
+  int nstep_in_cpl = 1, l1ci = 1, l2ci = 1, nstep_in_day = 1, nday_of_year = 1;
+  int cesm_single_sums = 0;      // A/B: thermf_cesm's sums one xcsum at a time, 2 launches each (tools/gpu_thermf_cesm_cost.py); 0: one batch
   // ---- what blomgpu_step's sequence consists of ----
   bool full_physics = false;     // blomgpu_step runs difest_isobml_pre, thermf, mxlayr (+ cmnfld2, cmnfld1): stepper.py FULL_STAGES
   int difest_live = 0;           // blomgpu_step: 1 = difest_isobml estimates difint, difiso, difdia, difwgt every step (full_physics)
@@ -456,6 +477,10 @@ struct blomgpu_ctx {
   DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
   std::vector<double> dia_edges;               // blomgpu_dia_set_levels: the ddm + 1 edges of the depth levels; empty: the 35-level table
   std::vector<double> dia_sigdia;              // blomgpu_dia_set_sigdia: the kk diagnostic density classes; empty: none (a class name is refused)
+  bool cesm_declared = false;                  // blomgpu_inifrc_cesm has been called: the coupler's forcing exists (cesm/mod_cesm.F90:175-200)
+  int nflxdi[48] = {};                         // mod_forcing's nflxdi: how often thermf_cesm has added to level ntld of tflxdi / sflxdi
+  long long cesm_launches = 0;                 // kernel launches of thermf_cesm so far, its batched sums included (blomgpu_get_real "thermf_cesm_launches")
+  double *cesm_sums = nullptr, *cesm_rows = nullptr;   // thermf_cesm's global sums (3 + ntr, on the device) and their row sums
   int dia_alarm = -1;                          // blomgpu_dia_alarm: alarm_phy(1) as the host declared it, 0 | 1; -1: undeclared
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
@@ -509,6 +534,16 @@ int st_updtrc(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int st_xcsum(blomgpu_ctx *, const double *a, int itype, double *sum);
 int st_xcsum_dev(blomgpu_ctx *, const double *a, int itype, int slot, double **sums_dev);   // the sum stays on the device: sums_dev[slot]
 int st_thermf(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_thermf.hip
+// stage_thermf_cesm.hip: the surface forcing of the coupled experiment
+int cesm_inifrc(blomgpu_ctx *);                                                  // cesm/mod_cesm.F90:175-200 + phy/mod_idarlx.F90:89-114
+int cesm_field(blomgpu_ctx *, int fid);                                          // a 48-level array that is about to be used: allocate it
+void cesm_free(blomgpu_ctx *);
+static inline bool cesm_on(const blomgpu_ctx *c) { return c->cesm_declared && c->expcnf == "cesm"; }
+int st_getfrc_cesm(blomgpu_ctx *);                                               // cesm/mod_cesm.F90:202-263
+int st_sfcstr_cesm(blomgpu_ctx *);                                               // cesm/mod_sfcstr_cesm.F90:33-65
+int st_thermf_cesm(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // cesm/mod_thermf_cesm.F90:58-432
+// halo.hip: xcsum of nb planes at once, the sums left on the device in out[0..nb-1]; mask[q] == nullptr: ips
+int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int *const *masks, double *rows, double *out);
 int st_niw_ke_tendency(blomgpu_ctx *, int m, int mm);                           // stage_difest.hip
 int st_difest_isobml_pre(blomgpu_ctx *, int m, int n, int mm, int nn);
 int st_difest_isobml(blomgpu_ctx *, int m, int n, int mm, int nn);               // stage_difest_iso.hip: the whole routine

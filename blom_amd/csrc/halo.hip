@@ -409,6 +409,7 @@ const char *tiletable_build(int npx, int npy, int itdm, int jtdm, const int *i0_
 int ctx_locate_ptr(const blomgpu_ctx *c, const double *p, size_t *offset) {
   for (int f = 0; f < NF_REAL; f++) {
     const double *b = c->h.f[f];
+    if (!b) continue;                                   // (a field of the coupled experiment that has no memory yet)
     const size_t n = (size_t)c->nlev_real[f] * c->h.nplane;
     if (p >= b && p < b + n) { *offset = (size_t)(p - b); return f; }
   }
@@ -1071,6 +1072,57 @@ __global__ __launch_bounds__(256) void k_xcsum_total(const double *__restrict__ 
   }
 }
 
+// Many planes at once (thermf_cesm: one sum for salt, one per tracer, two for the balanced salinity relaxation -- 1 + ntr' + 2 sums
+// that do not depend on each other, cesm/mod_thermf_cesm.F90:342-410): the plane on blockIdx.y, a mask per plane, and for each plane
+// exactly k_xcsum_rows / k_xcsum_total: the same strips of 2*nbdy+1, strip order, row order and seam rule.  skip[q]: the plane's mask
+// is ip and stands for ips (the seam row of an arctic patch is left out); a mask of the caller's own is taken as it is.
+#define XCS_NB 32
+struct XcsBatch {
+  const double *a[XCS_NB];
+  const int *mask[XCS_NB];
+  unsigned char skip[XCS_NB];
+};
+__global__ __launch_bounds__(64) void k_xcsum_rows_batch(const DevView *__restrict__ Vp, XcsBatch B, double *__restrict__ rowsum) {
+  const DevView &V = *Vp;
+  __shared__ double strip[64];
+  const int ii = V.ii, jj = V.jj, j = blockIdx.x + 1, W = 2 * NBDY + 1, q = blockIdx.y;
+  const double *__restrict__ a = B.a[q];
+  const int *__restrict__ mask = B.mask[q];
+  const bool dead = B.skip[q] && j >= jj;
+  const int nstrip = (ii + W - 1) / W;
+  double sum8 = 0.;
+  for (int s0 = 0; s0 < nstrip; s0 += 64) {
+    const int sidx = s0 + (int)threadIdx.x;
+    double sum8p = 0.;
+    if (sidx < nstrip) {
+      const int i1 = 1 + sidx * W, ie = i1 + 2 * NBDY < ii ? i1 + 2 * NBDY : ii;
+      for (int i = i1; i <= ie; i++) {
+        const size_t x = IDX(V, i, j);
+        if (!dead && mask[x] == 1) sum8p = sum8p + a[x];
+      }
+    }
+    strip[threadIdx.x] = sum8p;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      const int n = nstrip - s0 < 64 ? nstrip - s0 : 64;
+      for (int s = 0; s < n; s++) sum8 = sum8 + strip[s];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) rowsum[(size_t)q * jj + j - 1] = sum8;
+}
+__global__ __launch_bounds__(256) void k_xcsum_total_batch(const double *__restrict__ rowsum, int jj, double *__restrict__ out) {
+  HIP_DYNAMIC_SHARED(double, rs)
+  const double *__restrict__ mine = rowsum + (size_t)blockIdx.x * jj;
+  for (int j = threadIdx.x; j < jj; j += blockDim.x) rs[j] = mine[j];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double s = rs[0];
+    for (int j = 1; j < jj; j++) s = s + rs[j];
+    out[blockIdx.x] = s;
+  }
+}
+
 // Tiles of one process: every tile forms the sum of the WHOLE domain itself, reading each point from the tile that owns it --
 // the strips, their order and the order of the rows are those of the global domain (phy/mod_xc.F90:1663-1708: a strip belongs to
 // the tile that owns its centre, so the strip sums do not depend on the tiling), hence the single tile's bits on every tile.
@@ -1220,6 +1272,37 @@ int st_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot, double **
   const int *mask = g == 1 ? h.m[I_ip] : g == 2 ? h.m[I_iq] : g == 3 ? h.m[I_iu] : h.m[I_iv];
   hipLaunchKernelGGL(k_xcsum_rows, dim3(h.jj), dim3(64), 0, c->stream, c->d, a, mask, (g == 1 && h.nreg == 2) ? 1 : 0, c->xcsum_buf + 1);
   hipLaunchKernelGGL(k_xcsum_total, dim3(1), dim3(256), sizeof(double) * (size_t)h.jj, c->stream, c->xcsum_buf + 1, h.jj, c->xcsum_dev + slot);
+  HIPCHK(c, hipGetLastError());
+  return 0;
+}
+
+// nb planes at once: two launches per XCS_NB = 32 planes on a single tile (counted in cesm_launches).  On tile groups and over RCCL the one-plane paths above, once per
+// plane (they know the ip mask only: a mask of the caller's own is refused there).  rows: nb * jtdm doubles of the caller's.
+int st_xcsum_batch(blomgpu_ctx *c, int nb, const double *const *planes, const int *const *masks, double *rows, double *out) {
+  const DevView &h = c->h;
+  if (c->tiling.multi()) {
+    for (int q = 0; q < nb; q++) {
+      if (masks[q]) return ctx_fail(c, "xcsum: a sum with a mask other than ips is built for a single tile");
+      double *sums = nullptr;
+      if (int rc = st_xcsum_dev(c, planes[q], 1, 7, &sums)) return rc;
+      HIPCHK(c, hipMemcpyAsync(out + q, sums + 7, sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    }
+    return 0;
+  }
+  if (h.itdm != h.ii || h.jtdm != h.jj) return ctx_fail(c, "xcsum: this context is one tile of a larger domain but no transport is attached");
+  for (int q0 = 0; q0 < nb; q0 += XCS_NB) {
+    const int n = nb - q0 < XCS_NB ? nb - q0 : XCS_NB;
+    XcsBatch B;
+    for (int q = 0; q < XCS_NB; q++) {
+      const int s = q < n ? q0 + q : q0;
+      B.a[q] = planes[s];
+      B.mask[q] = masks[s] ? masks[s] : h.m[I_ip];
+      B.skip[q] = !masks[s] && h.nreg == 2;
+    }
+    hipLaunchKernelGGL(k_xcsum_rows_batch, dim3(h.jj, n), dim3(64), 0, c->stream, c->d, B, rows + (size_t)q0 * h.jj);
+    hipLaunchKernelGGL(k_xcsum_total_batch, dim3(n), dim3(256), sizeof(double) * (size_t)h.jj, c->stream, rows + (size_t)q0 * h.jj, h.jj, out + q0);
+    c->cesm_launches += 2;
+  }
   HIPCHK(c, hipGetLastError());
   return 0;
 }

@@ -110,6 +110,26 @@ module mod_blomgpu
       type(c_ptr), value :: c
       integer(c_int), value :: alarm
     end function
+    integer(c_int) function blomgpu_upload_level(c, name, host, lev) bind(C, name='blomgpu_upload_level')
+      import :: c_ptr, c_int, c_char, c_double
+      type(c_ptr), value :: c
+      character(kind=c_char), intent(in) :: name(*)
+      real(c_double), intent(in) :: host(*)
+      integer(c_int), value :: lev
+    end function
+    integer(c_int) function blomgpu_inifrc_cesm(c) bind(C, name='blomgpu_inifrc_cesm')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_getfrc_cesm(c) bind(C, name='blomgpu_getfrc_cesm')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_cesm_nflxdi(c, out) bind(C, name='blomgpu_cesm_nflxdi')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), intent(out) :: out(48)
+    end function
     integer(c_int) function blomgpu_dia_name_ext(index, buf, cap, kind, grid) bind(C, name='blomgpu_dia_name_ext')
       import :: c_int, c_char
       integer(c_int), value :: index, cap
@@ -257,6 +277,7 @@ module mod_blomgpu
             cmnfld1, cmnfld2, ale_regrid_remap, ale_vdifft, ale_vdiffm, ale_forcing, &
             cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc, ale_remap_diazlv
   public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext, gpu_dia_alarm
+  public :: inifrc_cesm, getfrc_cesm, gpu_cesm_nflxdi, gpu_upload_level
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
@@ -615,6 +636,26 @@ contains
   subroutine gpu_dia_alarm(alarm)
     integer, intent(in) :: alarm
     call gpu_check(blomgpu_dia_alarm(ctx, int(alarm, c_int)), 'gpu_dia_alarm')
+  end subroutine
+  ! The coupled experiment (expcnf = 'cesm').  inifrc_cesm (cesm/mod_cesm.F90:175-200) is also the declaration that the coupler's forcing
+  ! exists: until it has been called sfcstr and thermf refuse expcnf = 'cesm'.  getfrc_cesm: cesm/mod_cesm.F90:202-263.
+  subroutine inifrc_cesm()
+    call gpu_check(blomgpu_inifrc_cesm(ctx), 'inifrc_cesm')
+  end subroutine
+  subroutine gpu_upload_level(name, a, lev)      ! one level of a field: a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy) into level lev
+    character(len=*), intent(in) :: name
+    integer, intent(in) :: lev
+    real(8), intent(in) :: a(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy)
+    call gpu_check(blomgpu_upload_level(ctx, cz(name), a, int(lev, c_int)), 'gpu_upload_level')
+  end subroutine
+  subroutine getfrc_cesm()
+    call gpu_check(blomgpu_getfrc_cesm(ctx), 'getfrc_cesm')
+  end subroutine
+  subroutine gpu_cesm_nflxdi(nflxdi)            ! mod_forcing's nflxdi
+    integer, intent(out) :: nflxdi(48)
+    integer(c_int) :: n(48)
+    call gpu_check(blomgpu_cesm_nflxdi(ctx, n), 'gpu_cesm_nflxdi')
+    nflxdi = int(n)
   end subroutine
   ! the depth levels of the *lvl names as depthslev_bnds(2,ddm) (phy/mod_dia.F90:119-128); refused while a *lvl name is selected
   subroutine gpu_dia_set_levels(bnds, ddm)

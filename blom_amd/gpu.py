@@ -157,6 +157,34 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_xcsum(self.ctx, name.encode(), lev, itype, C.byref(v)))
         return v.value
 
+    def xcsum_batch(self, name, lev0, nlev, mask="ips"):
+        """xcsum of nlev consecutive levels of a field at once, through the kernels thermf_cesm's sums take -- blomgpu_xcsum_batch"""
+        out = np.zeros(nlev, dtype=np.float64)
+        self._chk(self.lib.blomgpu_xcsum_batch(self.ctx, name.encode(), int(lev0), int(nlev), mask.encode(), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    # -- the coupled experiment (expcnf = 'cesm') --------------------------------------------
+    def inifrc_cesm(self):
+        """inifrc_cesm (cesm/mod_cesm.F90:175-200) and the declaration that the coupler's forcing exists: creates the _da pairs, hmlt
+        frzpot mltpot ztx mty, the stream fields, ipwocn ... -- blomgpu_inifrc_cesm"""
+        self._chk(self.lib.blomgpu_inifrc_cesm(self.ctx))
+        self._info = {}
+
+    def put_level(self, name, plane, lev):
+        """one level (1-based) of a real field from one plane -- blomgpu_upload_level"""
+        a = np.ascontiguousarray(plane, dtype=np.float64).reshape(self.nj, self.ni)
+        self._chk(self.lib.blomgpu_upload_level(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p), int(lev)))
+
+    def getfrc_cesm(self):
+        """getfrc_cesm (cesm/mod_cesm.F90:202-263) -- blomgpu_getfrc_cesm"""
+        self._chk(self.lib.blomgpu_getfrc_cesm(self.ctx))
+
+    def cesm_nflxdi(self):
+        """mod_forcing's nflxdi(48) -- blomgpu_cesm_nflxdi"""
+        out = np.zeros(48, dtype=np.int32)
+        self._chk(self.lib.blomgpu_cesm_nflxdi(self.ctx, out.ctypes.data_as(C.c_void_p)))
+        return out
+
     def exp(self, x):
         """exp() as the kernels evaluate it (blom_amd/csrc/exp_libm.h), elementwise."""
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()

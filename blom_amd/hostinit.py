@@ -492,6 +492,57 @@ def init_forcing(be, case):
         be.set("area", area)
 
 
+CESM_DA = "ustarw lip sop eva rnf rfi fmltfz sfl swa nsf hmlt ficem ztx mty".split()      # the fields getfrc_cesm interpolates
+
+
+def cesm_forcing(case, seed=0):
+    """Synthetic coupler forcing for expcnf = 'cesm', seeded: the _da pairs of cesm/mod_cesm.F90:67-97 with two different coupling
+    intervals, the stream fields, the climatologies, the applied relaxation fluxes (48 levels) and a world-ocean mask that leaves
+    the westernmost eighth of the domain out.  Magnitudes are those of a mid-latitude ocean in SI units (W m-2, kg m-2 s-1, m s-1,
+    N m-2); the values are smooth in space with noise on top, defined on the whole padded plane so that a kernel that reads a land
+    or halo point is seen.  Returns {name: array}; `put_cesm_forcing` uploads it."""
+    rng = np.random.default_rng(seed)
+    nj, ni = case.jdm + 2 * NBDY, case.idm + 2 * NBDY
+    y, x = np.arange(nj)[:, None] / nj, 2 * np.pi * (np.arange(ni)[None, :] - NBDY) / case.idm
+
+    def fld(mean, amp, nlev=1, phase=0.0):
+        a = np.empty((nlev, nj, ni))
+        for l in range(nlev):
+            a[l] = mean + amp * (np.sin(x * (1 + l % 3) + phase + 0.7 * l) * (0.5 + y) + 0.25 * rng.standard_normal((nj, ni)))
+        return a
+    f = dict(ustarw_da=np.abs(fld(0.008, 0.004, 2)), lip_da=np.abs(fld(3e-5, 3e-5, 2, 1.0)), sop_da=np.abs(fld(5e-6, 5e-6, 2, 2.0)),
+             eva_da=-np.abs(fld(4e-5, 3e-5, 2, 3.0)), rnf_da=np.abs(fld(1e-6, 2e-6, 2, 4.0)), rfi_da=np.abs(fld(2e-7, 4e-7, 2, 5.0)),
+             fmltfz_da=fld(0.0, 4e-5, 2, 0.3), sfl_da=fld(0.0, 4e-7, 2, 1.3), swa_da=np.abs(fld(150.0, 100.0, 2, 2.3)),
+             nsf_da=fld(-120.0, 80.0, 2, 3.3), hmlt_da=-np.abs(fld(5.0, 10.0, 2, 4.3)), ficem_da=np.clip(fld(0.2, 0.4, 2, 5.3), 0.0, 1.0),
+             ztx_da=fld(0.05, 0.1, 2, 0.6), mty_da=fld(0.0, 0.05, 2, 1.6))
+    f["sst_stream"] = fld(271.0 + 8.0, 9.0, 1, 2.6)                      # [K]: below the freezing point somewhere
+    f["sss_stream"] = fld(35.0, 1.0, 1, 3.6)
+    f["ice_stream"] = np.clip(fld(0.3, 0.5, 1, 4.6), 0.0, 1.0)
+    f["sstclm"] = fld(271.0 + 8.0, 9.0, 12, 5.6)
+    f["ricclm"] = np.clip(fld(0.3, 0.5, 12, 0.9), 0.0, 1.0)
+    f["sssclm"] = fld(35.0, 1.0, 12, 1.9)
+    f["tflxap"] = fld(0.0, 20.0, 48, 2.9)
+    f["sflxap"] = fld(0.0, 1e-6, 48, 3.9)
+    f["salt_corr"] = np.abs(fld(0.0, 1e-3, 1, 4.9))
+    f["trc_corr"] = np.abs(fld(0.0, 1e-3, max(case.ntr, 1), 5.9))
+    ipw = np.ones((1, nj, ni), np.int32)
+    ipw[:, :, :NBDY + max(1, case.idm // 8)] = 0
+    f["ipwocn"] = ipw
+    return f
+
+
+def put_cesm_forcing(be, case, forcing=None, seed=0):
+    """upload `cesm_forcing` (after be.inifrc_cesm()); ipwocn is cut to the wet points"""
+    f = dict(forcing if forcing is not None else cesm_forcing(case, seed))
+    nj, ni = case.jdm + 2 * NBDY, case.idm + 2 * NBDY
+    f["ipwocn"] = (f["ipwocn"].reshape(1, nj, ni) * (np.asarray(be.masks["ip"]).reshape(1, nj, ni) > 0)).astype(np.int32)
+    for nm, a in f.items():
+        if nm == "trc_corr" and not case.ntr:
+            continue
+        be.put(nm, a)
+    return f
+
+
 def ocean_area(be, case):
     """mod_grid's area: the sum of scp2 over ips (ip without the seam row of an arctic patch) of the WHOLE domain `be` holds"""
     ip = be.masks["ip"] if hasattr(be, "masks") else None

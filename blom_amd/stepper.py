@@ -52,6 +52,27 @@ HYBRID_STAGES = ("init_fluxes", "tmsmt1", "ale_regrid_remap", "cmnfld2", "halo_d
                  "momtum", "cmnfld_bfsqi_ale", "ale_forcing", "halo_difest_vert", "ale_vdifft", "ale_vdiffm", "updtrc", "barotp",
                  "pbcor2", "tmsmt2", "cmnfld1")
 
+# The coupled experiment (expcnf = 'cesm'), once BlomGpu.inifrc_cesm has declared the coupler's forcing: getfrc_cesm behind init_fluxes
+# (phy/mod_blom_step.F90:116), sfcstr in front of pgforc (:163), and thermf at :188 -- which the full-physics tuples hold already and the
+# hybrid step gains (behind momtum: the reference calls it in front of cmnfld_bfsqi_ale).  The dynamical core runs the first two only.
+def _cesm(stages, thermf_after=None):
+    out = []
+    for s in stages:
+        if s == "pgforc":
+            out.append("sfcstr")
+        out.append(s)
+        if s == "init_fluxes":
+            out.append("getfrc_cesm")
+        if s == thermf_after:
+            out.append("thermf")
+    return tuple(out)
+
+
+DYNCORE_STAGES_CESM = _cesm(DYNCORE_STAGES)
+FULL_STAGES_CESM = _cesm(FULL_STAGES)
+FULL_STAGES_LIVE_CESM = _cesm(FULL_STAGES_LIVE)
+HYBRID_STAGES_CESM = _cesm(HYBRID_STAGES, thermf_after="momtum")
+
 
 def dyncore_step(be, nstep, baclin, stages=DYNCORE_STAGES, hook=None):
     """Advance backend `be` from step count nstep to nstep+1.  `hook(stage, sextuple)` is

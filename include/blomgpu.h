@@ -159,6 +159,44 @@ int  blomgpu_mxlayr_tail (blomgpu_ctx *, int nn, int k1n);
  * RCCL ranks need the global context of the replicated barotropic solve (blomgpu_rccl_attach_barotp_global).  PARITY UNPINNED (the module
  * imports the netCDF-bound mod_ben02): cross-checked against the real module behind a stand-in, tests/test_xcheck_thermf.py. */
 int  blomgpu_thermf (blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
+/* The surface forcing of the coupled experiment, expcnf = 'cesm' (BLOM inside NorESM; blom_amd/csrc/stage_thermf_cesm.hip).
+ *
+ * blomgpu_inifrc_cesm: cesm/mod_cesm.F90:175-200 inifrc_cesm -- l1ci = l2ci = 1, and idarlx's zeroing of tflxdi / sflxdi / nflxdi when
+ * "ditflx" / "disflx" are set (phy/mod_idarlx.F90:89-114); the file reads stay the host's (sstclm ricclm sssclm tflxap sflxap are
+ * uploaded by name).  It is also the declaration that the coupler's forcing exists: it creates the fields
+ *   <x>_da (2 levels) for x = ustarw lip sop eva rnf rfi fmltfz sfl swa nsf hmlt ficem ztx mty  (cesm/mod_cesm.F90:67-97)
+ *   hmlt frzpot mltpot (:61-64)   ztx mty sst_stream sss_stream ice_stream (phy/mod_forcing.F90)   thermf_util (1 + ntr planes)
+ *   tflxap sflxap tflxdi sflxdi (48 levels each: allocated when their option -- "aptflx" "apsflx" "ditflx" "disflx" -- is set on a declared
+ *   context or is on at the declaration, or when first named to an entry point)   ipwocn (integer)
+ * Until it has been called nothing of this is allocated, launched or changed, and blomgpu_thermf / blomgpu_sfcstr refuse
+ * expcnf = 'cesm' ("... is not built on the device until blomgpu_inifrc_cesm has been called").  Afterwards, with expcnf = 'cesm':
+ *   blomgpu_getfrc_cesm  cesm/mod_cesm.F90:202-263 getfrc_cesm: x = w1*x_da(l1ci) + w2*x_da(l2ci) for the fourteen fields above, w1 from
+ *                        "smtfrc", "nstep", "nstep_in_cpl" with the C library's cos; stage name "getfrc_cesm"
+ *   blomgpu_sfcstr       cesm/mod_sfcstr_cesm.F90:33-65 sfcstr_cesm: taux = ztx, tauy = mty
+ *   blomgpu_thermf       cesm/mod_thermf_cesm.F90:58-432 thermf_cesm, both vertical coordinates; reads p, dp / temp / saln at both time
+ *                        levels, the tracers, the fields getfrc_cesm fills, sstclm ricclm sssclm or (blomgpu_set_int
+ *                        "use_stream_relaxation") sst_stream sss_stream ice_stream, salt_corr trc_corr; writes surflx sswflx surrlx
+ *                        salflx brnflx salrlx hmltfz trflx ustar frzpot mltpot, t_rs_nonloc s_rs_nonloc (hybrid coordinates), zeroes
+ *                        salt_corr trc_corr; "aptflx" "apsflx" apply tflxap / sflxap, "ditflx" "disflx" add to tflxdi / sflxdi at
+ *                        level ntld, "srxbal" balances the salinity relaxation over ipwocn (single tile).  Time of the year:
+ *                        blomgpu_set_int "nstep", "nstep_in_day", "nday_of_year", "nday_in_year" (:74-84).  The freezing point is
+ *                        the stand-alone driver's swtfrz (drivers/nocoupler/mod_swtfrz.F with phy/mod_eos.F90:133-136).
+ *                        blomgpu_get_real "sflxc" returns the correction of the virtual salt flux (:342-343).
+ *   blomgpu_step         runs getfrc_cesm behind init_fluxes (phy/mod_blom_step.F90:116), sfcstr in front of pgforc (:163), thermf at :188
+ *                        (full_physics and the hybrid sequence).  With "use_graph" = 1 it refuses: the per-step scalars are kernel
+ *                        arguments.
+ * The options of this section ("smtfrc", "nstep_in_cpl", "l1ci", "l2ci", "use_stream_relaxation", "nstep_in_day", "nday_of_year") go through
+ * blomgpu_set_int like every other; blomgpu_option_name does not list them (it lists the table of the options that exist without the declaration).
+ * blomgpu_get_real "thermf_cesm_launches": the kernel launches thermf_cesm has issued so far (four a call up to 32 planes in the batch:
+ * ntr' <= 31, 29 with srxbal; two more per further 32).
+ * blomgpu_cesm_nflxdi: mod_forcing's nflxdi(48).  blomgpu_xcsum_batch: xcsum (phy/mod_xc.F90:4116) of nlev consecutive levels of a
+ * field at once, through the kernels thermf_cesm's 1 + ntr + 2 sums take; mask "ips" or the name of an integer field (single tile). */
+int  blomgpu_inifrc_cesm(blomgpu_ctx *);
+/* one level (1-based) of a real field from one host plane: what a coupling interval uploads of a _da pair is level l2ci alone */
+int  blomgpu_upload_level(blomgpu_ctx *, const char *name, const void *host, int lev);
+int  blomgpu_getfrc_cesm(blomgpu_ctx *);
+int  blomgpu_cesm_nflxdi(blomgpu_ctx *, int out[48]);
+int  blomgpu_xcsum_batch(blomgpu_ctx *, const char *name, int lev0, int nlev, const char *mask, double *sums);
 /* phy/mod_mxlayr.F90:130 mxlayr(m,n,mm,nn,k1m,k1n): the bulk mixed layer of vcoord_type = 'isopyc_bulkml' (turbulent kinetic
  * energy balance, detrainment / entrainment, surface forcing, the new layer structure at the velocity points), called after
  * thermf (phy/mod_blom_step.F90:188-192).  Reads the surface fluxes surflx, surrlx, sswflx, salflx, brnflx, salrlx, trflx, the
