@@ -464,26 +464,41 @@ def default_grid(grid):
         _default_grid = old
 
 
-def make_case(name, ntr=None, carve=None, *, grid=None, **overrides):
+def make_case(name, ntr=None, carve=None, *, grid=None, dims=None, **overrides):
     """`<grid>_tke`: the grid with the reference's default tracer set (meson_options.txt:17-21: turbclo = oneeq +
     advection, iage => -DTKE -DTKEADV -DIDLAGE): ntr = 3 = TKE, the generic-length-scale slot, ideal age
     (trc/mod_tracers.F90:85-127).  Without the suffix: the -DTRC -DIDLAGE build, ntr = 1.
     grid: "uniform" (Cartesian f-plane) | "warped" | "warped_eq" (warped_grid above; every case but fuk95_ref, which restates the
-    reference's own generator); None: "uniform", or what an enclosing default_grid block names."""
+    reference's own generator); None: "uniform", or what an enclosing default_grid block names.
+    dims: (idm, jdm, kdm) in place of the family's three sizes in _DIMS; topology, dx, time steps, bathymetry rule and the suffixes
+    stay the family's.  The case is then named `<family>@<idm>x<jdm>x<kdm><suffix>` (chan_s@33x17x3_tke), and make_case takes
+    that name too: the kernels choose tile shapes and k chunks by these numbers, and a test reaches the ones no family has by
+    naming its own sizes (every case but fuk95_ref)."""
     grid = _default_grid if grid is None else grid
     assert grid in GRIDS, grid
     if name == "fuk95_ref":
         assert grid == "uniform", "fuk95_ref is the reference's own f-plane case"
+        assert dims is None, "fuk95_ref has the sizes of the reference's own case"
         return fuk95_ref_case(ntr=1 if ntr is None else ntr, **overrides)
     full_name = name
     tk2 = name.endswith("_tk2")          # turbclo = twoeq, advection, isodif: -DTKE -DGLS -DTKEADV -DTKEIDF
     tk0 = name.endswith("_tk0")          # turbclo = oneeq: -DTKE alone, TKE tracers not advected
     tke = name.endswith("_tke") or tk2 or tk0
+    suffix = ""
     if tke:
-        name = name[:-4]
+        name, suffix = name[:-4], name[-4:]
+    if "@" in name:
+        name, _, size = name.partition("@")
+        named = tuple(int(x) for x in size.split("x"))
+        assert dims is None or tuple(dims) == named, (full_name, dims)
+        dims = named
     if ntr is None:
         ntr = 3 if tke else 1
     idm, jdm, kdm, nreg, dx, baclin, batrop = _DIMS[name]
+    if dims is not None:
+        idm, jdm, kdm = (int(x) for x in dims)
+        assert idm >= 1 and jdm >= 1 and kdm >= 3, dims      # two mixed-layer layers and one isopycnic layer at least
+        full_name = f"{name}@{idm}x{jdm}x{kdm}{suffix}"
     ni, nj = idm + 2 * NBDY, jdm + 2 * NBDY
     p = default_params(baclin, batrop)
     if tke:

@@ -334,6 +334,7 @@ static int libm_probe(blomgpu_ctx *c, int n, const double *a, const double *b, d
 }
 
 int bt_block_mode(blomgpu_ctx *c);       // stage_barotp_pair.hip
+int bt_shape_code(blomgpu_ctx *c);
 extern "C" {
 
 const char *blomgpu_last_error(const blomgpu_ctx *ctx) {
@@ -500,6 +501,8 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   // which form of the barotropic substep kernel this context runs with its present options: 1 four substeps per hand-off
   // (k_bt_steps4, persistent), 2 the same kernel with a launch per four substeps, 0 the forms of stage_barotp_pair.hip's head
   if (s == "barotp_block_mode") { *v = bt_block_mode(c); return 0; }
+  // ... and with which tile shape, 100 * ti + tj: a test that means to reach one instantiation of the kernel asserts both
+  if (s == "barotp_shape") { *v = bt_shape_code(c); return 0; }
   // how many steps of this context blomgpu_step has replayed as HIP graphs / how many captures failed (a capture that fails leaves the
   // sequence on plain launches: correct, and a few per cent slower -- a caller that times steps wants to know)
   if (s == "graph_steps") { *v = c->graph_steps; return 0; }

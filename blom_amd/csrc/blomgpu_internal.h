@@ -463,6 +463,7 @@ struct blomgpu_ctx {
   bool bt_restart = true;        // the next persistent barotp launch zeroes the completion counts and starts at epoch 0
   unsigned bt_epoch = 0;         // completion count every tile has reached after the launches so far
   unsigned *bt_flags = nullptr;  // abort word + per-tile completion counts of the persistent barotp kernel
+  int bt_flags_words = 0;        // words bt_flags holds (the persistent forms differ in their tile counts: it grows on demand)
   int num_cus = 0;
   int bt4_blocks_per_cu[2] = {-1, -1};          // the same for the temporally blocked kernel (k_bt_steps4)
   int bt_blocks_per_cu[4] = {-1, -1, -1, -1};   // occupancy query results for the persistent barotp kernel's shapes (-1: not asked yet)

@@ -51,7 +51,12 @@ __global__ void k_xctilr_gather(const DevView *__restrict__ Vp, double *__restri
 // u-grid, from j = 0: row jj itself is a copy) or jj-j (q-, v-grid, where only the second half of row
 // jj is a copy), vector fields change sign.  The reference's three sweeps only move data, so every
 // target (south rows, rows jj.., E/W strips of all those rows) is one composite gather; no source is
-// itself a target.
+// itself a target -- with one exception on an odd ii, arctic_seam_kept.
+// The q-grid's seam row, do i = ii/2+1,ii: a(i,jj) = [-]a(ii+2-i,jj) (:4285-4288, :4328-4331), is a sequential loop, and on an odd ii
+// its second target i = ii/2+2 reads the first, ii/2+1, which the iteration before it overwrote with [-]a(ii/2+2,jj): the point gets its own
+// value back (the sign twice).  As a gather it would read a cell another thread writes.  It is no target here.  (An even ii has no
+// such pair: the first target is its own source.  The v-grid's pivot on an odd ii is its own source too, one thread.)
+__device__ __forceinline__ bool arctic_seam_kept(int g, int d, int iw, int ii) { return g == 2 && d == 0 && (ii & 1) && iw == ii / 2 + 2; }
 __global__ void k_xctilr_arctic(const DevView *__restrict__ Vp, double *__restrict__ a, int nlev, int mhl, int nhl, int itype) {
   const DevView &V = *Vp;
   const int ii = V.ii, jj = V.jj;
@@ -83,7 +88,7 @@ __global__ void k_xctilr_arctic(const DevView *__restrict__ Vp, double *__restri
       is = g == 1 ? ii - (iw - 1) % ii : (ii - (iw - 1)) % ii + 1;
       js = jj - 1 - d;
       flip = true;
-    } else if (d > 0 || iw > ii / 2) {                        // q-, v-grid
+    } else if ((d > 0 || iw > ii / 2) && !arctic_seam_kept(g, d, iw, ii)) {      // q-, v-grid
       is = g == 2 ? (ii - (iw - 1)) % ii + 1 : ii - (iw - 1) % ii;
       js = jj - d;
       flip = true;
@@ -700,7 +705,7 @@ __global__ void k_xctilr_arctic_multi(const DevView *__restrict__ Vp, ArcticMult
       is = g == 1 ? ii - (iw - 1) % ii : (ii - (iw - 1)) % ii + 1;
       js = jj - 1 - d;
       flip = true;
-    } else if (d > 0 || iw > ii / 2) {
+    } else if ((d > 0 || iw > ii / 2) && !arctic_seam_kept(g, d, iw, ii)) {
       is = g == 2 ? (ii - (iw - 1)) % ii + 1 : ii - (iw - 1) % ii;
       js = jj - d;
       flip = true;

@@ -118,7 +118,7 @@ __global__ void __launch_bounds__(bt_threads(TI, TJ)) k_bt_steps(const DevView *
   // itself is a target on the p- and u-grid and in its second half on the v-grid.
   size_t cs = c, cs_u = c, cs_v = c;
   double sg_u = 1., sg_v = 1.;
-  bool land = false;
+  bool land = false, fold_v = false;     // fold_v: the arctic rule rewrites this v-point
   if (a.fold_halo && inarr) {
     const bool oi = gi < 1 || gi > ii, oj = gj < 1 || gj > jj;
     if (V.nreg == 2) {
@@ -129,7 +129,7 @@ __global__ void __launch_bounds__(bt_threads(TI, TJ)) k_bt_steps(const DevView *
         cs = (size_t)IDX(V, ii - (iw - 1) % ii, jj - 1 - d);
         cs_u = (size_t)IDX(V, (ii - (iw - 1)) % ii + 1, jj - 1 - d);
         sg_u = -1.;
-        if (d > 0 || iw > ii / 2) { cs_v = (size_t)IDX(V, ii - (iw - 1) % ii, jj - d); sg_v = -1.; }
+        if (d > 0 || iw > ii / 2) { cs_v = (size_t)IDX(V, ii - (iw - 1) % ii, jj - d); sg_v = -1.; fold_v = true; }
         else cs_v = (size_t)IDX(V, iw, gj);
       } else if (oi) cs = cs_u = cs_v = (size_t)IDX(V, iw, gj);
     } else if (oi || oj) {
@@ -157,7 +157,9 @@ __global__ void __launch_bounds__(bt_threads(TI, TJ)) k_bt_steps(const DevView *
   const size_t rb_i = from_buf ? (size_t)(gj + HB - 1) * HB + (size_t)(gi < 1 ? gi + HB - 1 : gi - ii - 1) : 0;
   // arctic patch, persistent form: the fold also rewrites cells of the tile itself -- the seam row jj (on the p- and u-grid all
   // of it, on the v-grid its second half) takes the mirror image at every halo update, i.e. before every odd substep
-  const bool seam_pb = PERSIST && mine && cs != c, seam_ub = PERSIST && mine && cs_u != c, seam_vb = PERSIST && mine && cs_v != c;
+  // (on the v-grid by the rule, not by cs_v != c: with an odd ii the pivot i = (ii + 1) / 2 of the seam row is its own mirror image, and
+  // the reference's a(i,jj) = -a(ii+1-i,jj), phy/mod_xc.F90:4348-4351, changes its sign at every update)
+  const bool seam_pb = PERSIST && mine && cs != c, seam_ub = PERSIST && mine && cs_u != c, seam_vb = PERSIST && mine && fold_v;
   auto load_state = [&](bool rim_only) {
     if (!act) return;
     const double *g_pb = b_pb[src], *g_ub = b_ub[src], *g_vb = b_vb[src];
@@ -1041,6 +1043,28 @@ static BtShape bt_phase_shape(blomgpu_ctx *c) {
 }
 bool bt_phase_usable(blomgpu_ctx *c) { return bt_phase_shape(c).ti != 0; }
 
+// The abort word and the completion counts of the persistent forms, zeroed for the first launch of a barotp call.  The forms
+// differ in their tile counts (jj = 261: 17 tile rows of 16 in the pair form, 18 of 15 in the blocked one) and an option can
+// switch the form between two calls, so the buffer grows when the form in front of it needs more words than it holds.  Only
+// reached behind bt_restart, in a plain step (an option change drops the step graphs): nothing in flight reads the old buffer
+// once the stream has drained.
+static int bt_flags_restart(blomgpu_ctx *c, int ntiles) {
+  const int nwords = ntiles + 16;
+  if (nwords > c->bt_flags_words) {
+    if (c->bt_flags) {
+      HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, hipFree(c->bt_flags));
+      c->bt_flags = nullptr; c->bt_flags_words = 0;
+    }
+    HIPCHK(c, hipMalloc((void **)&c->bt_flags, sizeof(unsigned) * nwords));
+    c->bt_flags_words = nwords;
+  }
+  HIPCHK(c, hipMemsetAsync(c->bt_flags, 0, sizeof(unsigned) * nwords, c->stream));
+  c->bt_epoch = 0;
+  c->bt_restart = false;
+  return 0;
+}
+
 // one launch for the substeps lll0..last of a phase; `src` as in bt_pair_launch; returns the buffer set
 // that holds the state afterwards in *src_out and the level indices in *ml_out, *nl_out
 int bt_phase_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, double woa, double wob, double wna, double wnb, int lll0,
@@ -1053,12 +1077,8 @@ int bt_phase_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, double woa, do
   for (int lll = lll0; lll <= last; niter++) lll += (lll % 2 == 1 && lll + 1 <= last) ? 2 : 1;
   // the completion counters start at 0 with the first launch of every barotp call (st_barotp sets bt_restart): the
   // launches of a step then carry the same epochs every step, which lets blomgpu_step replay them as a graph
-  if (!c->bt_flags || c->bt_restart) {
-    if (!c->bt_flags) HIPCHK(c, hipMalloc((void **)&c->bt_flags, sizeof(unsigned) * (nbx * nby + 16)));
-    HIPCHK(c, hipMemsetAsync(c->bt_flags, 0, sizeof(unsigned) * (nbx * nby + 16), c->stream));
-    c->bt_epoch = 0;
-    c->bt_restart = false;
-  }
+  if (!c->bt_flags || c->bt_restart)
+    if (int rc = bt_flags_restart(c, nbx * nby)) return rc;
   PairArgs a;
   a.m = m; a.n = n; a.ml = ml; a.nl = nl;
   for (int x = 0; x < 2; x++) { a.wo[x] = a.wm[x] = a.wn[x] = 0.; }
@@ -1129,6 +1149,14 @@ int bt_block_mode(blomgpu_ctx *c) {
   if (c->barotp_block == 1) return c->barotp_persist && bt_block_shape(c, true).ti ? 1 : 0;
   return bt_block_shape(c, false).ti ? 2 : 0;
 }
+// 100 * ti + tj of the tile shape that serves this context's next barotp call (blomgpu_get_real "barotp_shape"): the blocked
+// form's where bt_block_mode selects it, otherwise the shape of the pair forms (with barotp_fused = 0, one kernel per equation,
+// no tile kernel runs and the value is the shape the fused form would take)
+int bt_shape_code(blomgpu_ctx *c) {
+  const int mode = bt_block_mode(c);
+  const BtShape sh = mode ? bt_block_shape(c, mode == 1) : bt_shape(c);
+  return 100 * sh.ti + sh.tj;
+}
 // the substeps of all five phases, four per iteration; mode as bt_block_mode returns it; ph_last / ph_w: PairArgs
 int bt_block_launch(blomgpu_ctx *c, int mode, int m, int n, int ml, int nl, const int *ph_last, const double (*ph_w)[4], int src,
                     int *src_out, int *ml_out, int *nl_out) {
@@ -1156,12 +1184,8 @@ int bt_block_launch(blomgpu_ctx *c, int mode, int m, int n, int ml, int nl, cons
     else hipLaunchKernelGGL((k_bt_steps4<26, 15>), dim3(nbx, nby), dim3(BT4_NT), 0, c->stream, c->d, a);
   };
   if (mode == 1) {
-    if (!c->bt_flags || c->bt_restart) {
-      if (!c->bt_flags) HIPCHK(c, hipMalloc((void **)&c->bt_flags, sizeof(unsigned) * (nbx * nby + 16)));
-      HIPCHK(c, hipMemsetAsync(c->bt_flags, 0, sizeof(unsigned) * (nbx * nby + 16), c->stream));
-      c->bt_epoch = 0;
-      c->bt_restart = false;
-    }
+    if (!c->bt_flags || c->bt_restart)
+      if (int rc = bt_flags_restart(c, nbx * nby)) return rc;
     a.flags = c->bt_flags + 16;
     a.epoch_base = c->bt_epoch;
     c->bt_epoch += (unsigned)niter;
