@@ -34,7 +34,7 @@ void ctx_sync_view(blomgpu_ctx *c) {
     DevView &a = c->hv[v];
     a = c->h;
     a.wk = c->wk_mom;
-    a.nwk = 6;
+    a.nwk = MF_NSLOT;
     if (v == VIEW_MOM_A) { a.f[F_pu] = c->pu_alt; a.f[F_pv] = c->pv_alt; }
     if (v == VIEW_MOM_B) a.f[F_p] = c->p_alt;
     (void)hipMemcpyAsync(c->dv[v], &a, sizeof(DevView), hipMemcpyHostToDevice, c->stream);
@@ -84,7 +84,7 @@ static void set_eos(Params &P) {
                a23 = 8.9521792365142522e-04, a24 = -2.8438341552142710e-05,
                a25 = -1.1887778959461776e-05, a26 = -4.0163964812921489e-06,
                b21 = 1.1995545126831476e-09, b22 = 5.5234008384648383e-12,
-               b23 = 8.4310335919950873e-13, alpha0 = 1.e-3;
+               b23 = 8.4310335919950873e-13, alpha0 = ALPHA0;
   P.ap21 = a21 + b21 * P.pref;
   P.ap22 = a22 + b22 * P.pref;
   P.ap23 = a23 + b23 * P.pref;
@@ -214,7 +214,7 @@ static const Opt g_opts[] = {
   CR(tau_growing_hml), CR(tau_decaying_hml), CR(lfmin), CR(mstar), CR(nstar), CR(wpup_min), CR(mlbl_max_ratio),
   CR(ale_regrid_nudge_ts), CR(ale_stab_fac_limit), CR(ale_dpvar_fac), CR(ale_smooth_diff_max),
   {"ale_dpmin_interior", O_REAL, IN_C(ale_dpmin_interior), 0,                        // [m], as in &ALE_REGRID_REMAP (:1352-1353)
-   [](double &v) -> const char * { v = v * 9806.; return nullptr; }},
+   [](double &v) -> const char * { v = v * ONEM; return nullptr; }},
   // ---- integers ----
   {"nstep", O_INT, IN_P(nstep), 0},                       // host-side only (stage_cppm.hip): the device view is not touched
   PI(lstep), PI(nday_in_year), PI(itriag), PI(itrtke), PI(itrgls), PI(tkeadv), PI(tkeidf), PI(gls), PI(vcoord_tag), PI(ltedtp_opt),
@@ -333,8 +333,6 @@ static int libm_probe(blomgpu_ctx *c, int n, const double *a, const double *b, d
   return rc ? ctx_fail(c, std::string(who) + ": copy or launch failed") : 0;
 }
 
-int bt_block_mode(blomgpu_ctx *c);       // stage_barotp_pair.hip
-int bt_shape_code(blomgpu_ctx *c);
 extern "C" {
 
 const char *blomgpu_last_error(const blomgpu_ctx *ctx) {
@@ -397,15 +395,15 @@ int blomgpu_create(const blomgpu_dims *d, blomgpu_ctx **out) {
     HIPCHK(c, hipMalloc((void **)&h.m[f], bytes));
     HIPCHK(c, hipMemsetAsync(h.m[f], 0, bytes, c->stream));
   }
-  h.nwk = 32 + 5 * NT;
+  h.nwk = wk_slots(d->ntr);
   HIPCHK(c, hipMalloc((void **)&h.wk, sizeof(double) * (size_t)h.nwk * K * h.nplane));
   HIPCHK(c, hipMemsetAsync(h.wk, 0, sizeof(double) * (size_t)h.nwk * K * h.nplane, c->stream));
   HIPCHK(c, hipMalloc((void **)&h.wk2d, sizeof(double) * (size_t)NWK2D * h.nplane));
   HIPCHK(c, hipMemsetAsync(h.wk2d, 0, sizeof(double) * (size_t)NWK2D * h.nplane, c->stream));
   HIPCHK(c, hipMalloc((void **)&c->d, sizeof(DevView)));
   // momtum's own work space and interface pressures + the second stream (blomgpu_internal.h: blomgpu_ctx::overlap)
-  HIPCHK(c, hipMalloc((void **)&c->wk_mom, sizeof(double) * (size_t)6 * K * h.nplane));
-  HIPCHK(c, hipMemsetAsync(c->wk_mom, 0, sizeof(double) * (size_t)6 * K * h.nplane, c->stream));
+  HIPCHK(c, hipMalloc((void **)&c->wk_mom, sizeof(double) * (size_t)MF_NSLOT * K * h.nplane));
+  HIPCHK(c, hipMemsetAsync(c->wk_mom, 0, sizeof(double) * (size_t)MF_NSLOT * K * h.nplane, c->stream));
   for (double **pp : {&c->p_alt, &c->pu_alt, &c->pv_alt}) {
     HIPCHK(c, hipMalloc((void **)pp, sizeof(double) * (size_t)(K + 1) * h.nplane));
     HIPCHK(c, hipMemsetAsync(*pp, 0, sizeof(double) * (size_t)(K + 1) * h.nplane, c->stream));

@@ -11,6 +11,8 @@
 #include <unordered_map>
 #include <vector>
 #include "exp_libm.h"
+#include "constants.h"
+#include "workspace_slots.h"
 
 #define NBDY 4
 
@@ -208,11 +210,11 @@ struct DevView {
   // work space standing in for the reference's stage-local temporaries:
   //   wk   : nwk fields of kk levels each   (field w, level k at wk + (w*kk + k)*nplane)
   //   wk2d : NWK2D single planes
+  // (workspace_slots.h names every slot of both)
   double *wk;
   double *wk2d;
   int nwk;
 };
-#define NWK2D 48
 #define WK(V, w) (global_ptr((V).wk) + (size_t)(w) * (V).kk * (V).nplane)
 #define WK2(V, w) (global_ptr((V).wk2d) + (size_t)(w) * (V).nplane)
 
@@ -319,7 +321,7 @@ struct blomgpu_ctx {
   int ale_regrid_method = 2, ale_k_range_plevel = 1;      // 'nudge' is the reference's default
   double ale_regrid_nudge_ts = 86400., ale_stab_fac_limit = .75, ale_dpvar_fac = .75, ale_smooth_diff_max = 50000.;   // :80-85
   int ale_dktzu = 4, ale_dktzl = 2;
-  double ale_dpmin_interior = .1 * 9806.;                 // [m] in the namelist, times onem (:1352-1353)
+  double ale_dpmin_interior = .1 * ONEM;                  // [m] in the namelist, times onem (:1352-1353)
   int ndiff_rec_per_face = 0;    // neutral diffusion: records per face (0: 6 kk, the bound; stage_ale.hip)
   int ndiff_surface_align = 1;   // phy/mod_diffusion.F90:84 (the namelist default of cime_config is .true.)
   // mod_mxlayr's namelist variables (cime_config/namelist_definition_blom.xml: rm0 = 1.2, rm5 = 0, mlrttp = 'constant'), mod_niw's
@@ -561,13 +563,6 @@ int st_kfpla_halo(blomgpu_ctx *, int n);
 int st_cmnfld1(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_cmnfld.hip   // phy/mod_cmnfld_routines.F90:1090-1156
 int st_cmnfld2(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // stage_cmnfld.hip   // phy/mod_cmnfld_routines.F90:1176-1196
 int diapfl_column3_launch(blomgpu_ctx *, int n, int nn, int *errflag);
-// work-space slots in which k_remap_tile<.., FOLD = true> leaves the new dp, T, S and advected tracers of level kn for pbcor1
-// (the slots of the flux planes between k_remap_tile and k_remap_update, remap_common.h: nothing else uses them then)
-#define R_BASE(ntr) (8 + 3 * (ntr))
-#define R_DP(ntr) (R_BASE(ntr) + 0)
-#define R_T(ntr) (R_BASE(ntr) + 1)
-#define R_S(ntr) (R_BASE(ntr) + 2)
-#define R_TR(ntr, nt) (R_BASE(ntr) + 3 + (nt))
 int st_ale_vdifft(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);          // stage_ale_vdiff.hip
 int st_ale_vdiffm(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int st_ale_forcing(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);         // stage_ale_vdiff.hip
@@ -609,6 +604,7 @@ void dia_free(blomgpu_ctx *);
 int st_mom_pupv(blomgpu_ctx *, int off, int lo, int hi);                          // stage_momtum.hip
 int st_convec_velocity(blomgpu_ctx *, int nn);                                    // stage_convec.hip
 int launch_dpudpv(blomgpu_ctx *, int off, int flags);                                        // stage_simple.hip
+int launch_p_dpu_dpv(blomgpu_ctx *, int off, int flags);                                     // stage_simple.hip: the pressure scan, then launch_dpudpv
 int remap_tile_launch(blomgpu_ctx *, int n, int mm, int nn, int tsel, bool fold);  // stage_remap_tile.hip; tsel 0 all tiles, 1 those that read no halo point, 2 the others
 int pbcor_tile_launch(blomgpu_ctx *, int which, int m, int offc, int offf, int from_remap);   // stage_pbcor_tile.hip
 int launch_pscan(blomgpu_ctx *, int off, int lo, int hi_off);   // p(k+1)=p(k)+dp(k+off) over lo..ii+hi_off
@@ -633,6 +629,29 @@ struct RcclLanded {          // received E/W strips left in the transport's buff
 };
 int rccl_xctilr_multi_ex(blomgpu_ctx *, double *const *fields, int nf, int nlev, int mhl, int nhl, RcclLanded *landed);
 int rccl_xctilr_multi(blomgpu_ctx *, double *const *fields, int nf, int nlev, int mhl, int nhl);  // one message per neighbour for up to 4 plane stacks
+int rccl_arctic_gather(blomgpu_ctx *, double *const *fields, int nf, int nlev, int nrows, const double **strips, size_t *field_stride);
+int rccl_xcsum_dev(blomgpu_ctx *, const double *a, int itype, int slot);                     // comm_rccl.hip
+// halo.hip, for the RCCL transport: the arctic patch's pack kernel, the checksum of a byte string
+void arctic_pack_launch(blomgpu_ctx *, hipStream_t st, double *const *fields, int nf, double *strip, int nlev, int nrows);
+unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init);
+// stage_barotp.hip: barotp on the context it is given (the global barotropic context of RCCL tiles: with_bounds = false) and the part
+// of it that reads 3-D fields
+int st_barotp_on(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n, bool with_bounds);
+int st_barotp_bounds(blomgpu_ctx *, int m, int nn);
+// stage_barotp_pair.hip: the LDS-tiled forms of barotp's substeps, launched by stage_barotp.hip (the definitions say what each does)
+int bt_pair_halo(blomgpu_ctx *, int set);
+int bt_pair_halo_landed(blomgpu_ctx *, int set, RcclLanded *landed);
+int bt_pair_launch(blomgpu_ctx *, int m, int n, int ml, int nl, const double *wo, const double *wm, const double *wn, int do_odd, int do_even,
+                   int src, int tsel, RcclLanded *rim);
+bool bt_phase_usable(blomgpu_ctx *);
+int bt_phase_launch(blomgpu_ctx *, int m, int n, int ml, int nl, double woa, double wob, double wna, double wnb, int lll0, int last, int src,
+                    int *src_out, int *ml_out, int *nl_out);
+int bt_phase_check(blomgpu_ctx *);
+int bt_overlap_usable(blomgpu_ctx *);
+int bt_block_mode(blomgpu_ctx *);            // 1: the persistent blocked form serves this context, 2: one launch per iteration, 0: neither
+int bt_shape_code(blomgpu_ctx *);            // 100 * ti + tj of the tile shape of the next barotp call
+int bt_block_launch(blomgpu_ctx *, int mode, int m, int n, int ml, int nl, const int *ph_last, const double (*ph_w)[4], int src, int *src_out,
+                    int *ml_out, int *nl_out);
 
 // XCD-aware block order.  Workgroups are dealt round-robin over the 8 XCDs (linear id % 8), each with its own
 // 4 MB L2, so with the natural order the rows j-1, j, j+1 of a stencil land in three different L2s and are
@@ -647,6 +666,26 @@ __device__ inline void xcd_block(unsigned &bx, unsigned &by) {
   bx = nl % gx;
   by = nl / gx;
 }
+
+// The thread prologue of a kernel with one thread per point of the padded plane (plane_grid below): t_ the point, Fortran (i, j) and the
+// plane index c; the thread leaves when it lies behind the plane.  Two flavours, and a kernel says which it is:
+//   THREAD_IJ_XCD      block order renumbered through xcd_block; by_ (the renumbered blockIdx.y) stays available as the layer
+//   THREAD_IJ_NATURAL  the natural blockIdx.x order (single-plane and column kernels: nothing to gain from renumbering)
+#define THREAD_IJ_XCD(V)                                                   \
+  unsigned bx_, by_;                                                       \
+  xcd_block(bx_, by_);                                                     \
+  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
+  (void)by_;                                                               \
+  if (t_ >= (V).nplane) return;                                            \
+  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
+  const size_t c = t_;                                                     \
+  (void)i; (void)j; (void)c
+#define THREAD_IJ_NATURAL(V)                                               \
+  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;                    \
+  if (t_ >= (V).nplane) return;                                            \
+  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
+  const size_t c = t_;                                                     \
+  (void)i; (void)j; (void)c
 
 // Column kernels (one thread per column, levels walked serially) have one dependent load in flight per thread, and with
 // ~1700 wavefronts on the chip that is half the bandwidth a copy reaches (2.8 against 5.9 TB/s,

@@ -337,7 +337,6 @@ int rccl_xctilr_multi_ex(blomgpu_ctx *c, double *const *fields, int nf, int nlev
 // mirror image of a tile's columns lies in the mirror tile and, for the u- and q-grid, one column beyond it
 // (the reference's second "aia" partner, phy/mod_xc.F90:2640-2653), so instead of pairing tiles every top-row rank
 // sends its strip ((nhl+2)*ii*nlev reals, a few 100 KB) to every other one: npx-1 messages per rank in one group.
-void arctic_pack_launch(blomgpu_ctx *c, hipStream_t st, double *const *fields, int nf, double *strip, int nlev, int nrows);   // halo.hip
 // Several plane stacks of the same depth travel in one message: rank q's block is [field][level][row][i].
 int rccl_arctic_gather(blomgpu_ctx *c, double *const *fields, int nf, int nlev, int nrows, const double **strips, size_t *field_stride) {
   const DevView &h = c->h;
@@ -437,8 +436,6 @@ __global__ void k_btg_window(const DevView *__restrict__ Vp, BtPlanes PT, BtPlan
 }
 
 blomgpu_ctx *bt_global_ctx(const blomgpu_ctx *c) { return c->bt_global ? c->bt_global->G : nullptr; }
-int st_barotp_on(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n, bool with_bounds);     // stage_barotp.hip
-int st_barotp_bounds(blomgpu_ctx *c, int m, int nn);
 
 int rccl_barotp_replicated(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   BtGlobal *B = c->bt_global;
@@ -485,7 +482,6 @@ int rccl_barotp_replicated(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m
 // xcsum over RCCL ranks: the plane travels to every rank the way the barotropic solver's fields do (one grouped send/recv
 // into the global context G of the replicated solve), and every rank forms the single tile's sum on G -- the reference's
 // summation order is that of the global domain whatever the tiling (phy/mod_xc.F90:1663-1708, :2071-2192)
-int st_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot, double **sums_dev);
 int rccl_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot) {
   BtGlobal *B = c->bt_global;
   if (!B) return ctx_fail(c, "xcsum on RCCL tiles needs the global context of the replicated barotropic solve (blomgpu_rccl_attach_barotp_global)");
@@ -523,8 +519,6 @@ int rccl_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot) {
 int rccl_xctilr(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl) {
   return rccl_xctilr_multi(c, &a, 1, nlev, mhl, nhl);
 }
-
-unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init);     // halo.hip
 
 extern "C" {
 // 128-byte ncclUniqueId created on rank 0 and distributed by the launcher (torch.distributed in

@@ -3,11 +3,6 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define DIAPFL_GRAV 9.806
-#define DIAPFL_ALPHA0 1.e-3
-#define DIAPFL_EPSILP 1.e-12
-#define DIAPFL_ONEM 9806.
-
 namespace eosd {
 // dsigdt / dsigds, phy/mod_eos.F90:243-261, :306-323
 __device__ inline double dsigdt(const Params &P, double th, double s) {

@@ -527,9 +527,6 @@ static int xctilr_plain(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl) {
   return 0;
 }
 
-int rccl_arctic_gather(blomgpu_ctx *c, double *const *fields, int nf, int nlev, int nrows, const double **strips, size_t *field_stride);
-int rccl_xctilr_multi(blomgpu_ctx *c, double *const *fields, int nf, int nlev, int mhl, int nhl);
-
 // arctic patch over tiles that exchange strips (RCCL ranks; tiles of one process with the option arctic_strips, which
 // exists so that the pack/fill kernels can be tested for several tile columns on one GPU)
 static int xctilr_arctic_strips(blomgpu_ctx *c, double *a, int nlev, int mhl, int nhl, int itype) {
@@ -1207,8 +1204,6 @@ __global__ __launch_bounds__(64) void k_xcsum_rows_tiles_ragged(XcsRag tab, int 
   }
   if (threadIdx.x == 0) rowsum[j - 1] = sum8;
 }
-
-int rccl_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot);      // comm_rccl.hip
 
 static int xcsum_group(blomgpu_ctx *c, const double *a, int itype, int slot) {
   const DevView &h = c->h;

@@ -5,7 +5,7 @@
 #include "hor3map_core.h"
 #include "hor3map_pqm.h"
 #include "hor3map_ppm_fused.h"
-#include "../../include/blomgpu_hor3map.h"
+#include "hor3map_internal.h"
 #include <cstdio>
 #include <cstring>
 #include <string>

@@ -3,12 +3,6 @@
 #pragma once
 #include "blomgpu_internal.h"
 
-#define GRAV 9.806
-#define ALPHA0 1.e-3
-#define EPSILPL 1.e-14
-#define EPSILP 1.e-12
-#define ONEM 9806.
-#define ONEMM 9.806
 #define SLIP (-1.)      // phy/mod_momtum.F90:94
 #define THKBOT 10.      // phy/mod_momtum.F90:97
 #define WPGF .25        // phy/mod_pgforc.F90:47

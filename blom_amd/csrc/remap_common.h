@@ -4,32 +4,8 @@
 #include "blomgpu_internal.h"
 
 #define DPEPS 1.e-12   // phy/mod_remap.F90:40
-#define ONEMM 9.806
 #define MAXTR 4   // tracer accumulators live in registers: every loop over them has a
                   // compile-time trip count (a runtime-indexed array would go to scratch)
-
-// work-space slots (fields of kk levels)
-#define G_DX 0
-#define G_DY 1
-#define G_TX 2
-#define G_TY 3
-#define G_TD 4
-#define G_SX 5
-#define G_SY 6
-#define G_SD 7
-#define G_TRX(nt) (8 + 3 * (nt))
-#define G_TRY(nt) (9 + 3 * (nt))
-#define G_TRD(nt) (10 + 3 * (nt))
-#define F_BASE(ntr) (8 + 3 * (ntr))
-#define W_FDU(ntr) (F_BASE(ntr) + 0)
-#define W_FDV(ntr) (F_BASE(ntr) + 1)
-#define W_FTU(ntr) (F_BASE(ntr) + 2)
-#define W_FTV(ntr) (F_BASE(ntr) + 3)
-#define W_FSU(ntr) (F_BASE(ntr) + 4)
-#define W_FSV(ntr) (F_BASE(ntr) + 5)
-#define W_FTRU(ntr, nt) (F_BASE(ntr) + 6 + 2 * (nt))
-#define W_FTRV(ntr, nt) (F_BASE(ntr) + 7 + 2 * (nt))
-static_assert(F_BASE(3) == R_BASE(3) && F_BASE(0) == R_BASE(0), "R_DP.. (blomgpu_internal.h) reuse the flux planes' slots");
 
 __device__ inline double max8(double a, double b, double c, double d, double e, double f, double g, double h) {
   return fmax2(fmax2(fmax2(fmax2(fmax2(fmax2(fmax2(a, b), c), d), e), f), g), h);

@@ -21,19 +21,10 @@
 // Roofline: HBM.
 #include "remap_common.h"
 
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
 // ---- mod_advect.F90:71-94 --------------------------------------------------------------------
 __global__ void k_adv_flux_area(const DevView *__restrict__ Vp, int m, int mm, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const int k = by_;
   const size_t np = V.nplane, okm = c + (size_t)(k + mm) * np, okn = c + (size_t)(k + nn) * np;
@@ -84,7 +75,7 @@ __device__ inline Nbr wet_nbr(const DevView &V, size_t c) {
 // ---- mod_advect.F90:100-121 ---------------------------------------------------------------------
 __global__ void k_adv_pbmin(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < -1 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_ip][c]) return;
   gcd_t pb = V.f[F_p] + (size_t)V.kk * V.nplane;
   const Nbr b = wet_nbr(V, c);
@@ -96,7 +87,7 @@ __global__ void k_adv_pbmin(const DevView *__restrict__ Vp) {
   r = fmin2(r, pb[b.nw]);
   r = fmin2(r, pb[b.n]);
   r = fmin2(r, pb[b.ne]);
-  WK2(V, 0)[c] = r;
+  WK2(V, S2_REMAP_PM)[c] = r;
 }
 
 // ---- mod_remap.F90:1468-1520 (+ the in-place dp side effect of :297-303 on the outer ring) --------
@@ -107,7 +98,7 @@ __global__ void k_adv_pbmin(const DevView *__restrict__ Vp) {
 // difference of fluxes is subtracted from q dp, q T, q S)
 __global__ void k_remap_update(const DevView *__restrict__ Vp, int nn, int mmlean) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < -2 || j > V.jj + 3 || i < -2 || i > V.ii + 3 || !V.m[I_ip][c]) return;
   const int k = by_, ntr = V.ntr;
   const size_t np = V.nplane, ok = (size_t)k * np, okn = (size_t)(k + nn) * np;
@@ -130,9 +121,9 @@ __global__ void k_remap_update(const DevView *__restrict__ Vp, int nn, int mmlea
     dft = (ue ? ftu[e] : 0.) - (uc ? ftu[c] : 0.) + (vn ? ftv[nb] : 0.) - (vc ? ftv[c] : 0.);
     dfs = (ue ? fsu[e] : 0.) - (uc ? fsu[c] : 0.) + (vn ? fsv[nb] : 0.) - (vc ? fsv[c] : 0.);
   } else {
-    gcd_t fdu = WK(V, W_FDU(ntr)) + ok, fdv = WK(V, W_FDV(ntr)) + ok;
-    gcd_t ftu = WK(V, W_FTU(ntr)) + ok, ftv = WK(V, W_FTV(ntr)) + ok;
-    gcd_t fsu = WK(V, W_FSU(ntr)) + ok, fsv = WK(V, W_FSV(ntr)) + ok;
+    gcd_t fdu = WK(V, RF_DU(ntr)) + ok, fdv = WK(V, RF_DV(ntr)) + ok;
+    gcd_t ftu = WK(V, RF_TU(ntr)) + ok, ftv = WK(V, RF_TV(ntr)) + ok;
+    gcd_t fsu = WK(V, RF_SU(ntr)) + ok, fsv = WK(V, RF_SV(ntr)) + ok;
     dfd = fdu[e] - fdu[c] + fdv[nb] - fdv[c];
     dft = ftu[e] - ftu[c] + ftv[nb] - ftv[c];
     dfs = fsu[e] - fsu[c] + fsv[nb] - fsv[c];
@@ -144,7 +135,7 @@ __global__ void k_remap_update(const DevView *__restrict__ Vp, int nn, int mmlea
   for (int nt = 0; nt < ntr; nt++) {
     if (trc_skip_adv(V.P, nt + 1)) continue;                   // phy/mod_remap.F90:1497-1499
     gd_t tr = V.f[F_trc] + okn + (size_t)nt * 2 * V.kk * np;
-    gcd_t fu = WK(V, W_FTRU(ntr, nt)) + ok, fv = WK(V, W_FTRV(ntr, nt)) + ok;
+    gcd_t fu = WK(V, RF_TRU(ntr, nt)) + ok, fv = WK(V, RF_TRV(ntr, nt)) + ok;
     tr[c] = (q * tr[c] - (fu[e] - fu[c] + fv[nb] - fv[c]) * s2i) / dpn;
   }
   dp[c] = fmax2(0., dpn - DPEPS);

@@ -27,17 +27,7 @@
 // *_xale, tests/test_xcheck_ale.py) -- a cross-check, not a pin.
 #include "blomgpu_internal.h"
 #include "eos.h"
-#include "../../include/blomgpu_hor3map.h"
-
-int h3m_use_stream(blomgpu_h3m_grid *G, hipStream_t stream);          // hor3map.hip
-int h3m_sequence_begin(blomgpu_h3m_grid *G);
-int h3m_sequence_begin_deferred(blomgpu_h3m_grid *G);
-int h3m_sequence_end_deferred(blomgpu_h3m_grid *G);
-int h3m_sequence_poll(blomgpu_h3m_grid *G, unsigned long long *column);
-int h3m_sequence_end(blomgpu_h3m_grid *G);
-int h3m_set_stream(blomgpu_h3m_grid *G, hipStream_t stream);
-int h3m_set_active(blomgpu_h3m_grid *G, const int *active);
-int h3m_extract_polycoeff_many(blomgpu_h3m_grid *G, int nf, blomgpu_h3m_src *const *srcs, double *const *outs);
+#include "hor3map_internal.h"
 
 #define H3M_MAXF 8
 #include "stage_ndiff.h"
@@ -190,18 +180,12 @@ static int ale_ndiff_buffers(blomgpu_ctx *c, AleState *a) {
   return 0;
 }
 
-#define PLANE_T(V)                                                         \
-  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;                    \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
 // source interfaces of the p-columns (:203-211) and their regridded positions for vcoord_type = 'plevel' (:263-284);
 // any other point of the plane: unit layers, left where they are
 __global__ void k_ale_p_src_dst(const DevView *__restrict__ Vp, int nn, const double *__restrict__ plevel, double *__restrict__ psrc,
                                 double *__restrict__ pdst, int ring, int *__restrict__ active) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const int kk = V.kk;
   const bool col = j >= 1 - ring && j <= V.jj + ring && i >= 1 - ring && i <= V.ii + ring && V.m[I_ip][c];
@@ -226,8 +210,6 @@ __global__ void k_ale_p_src_dst(const DevView *__restrict__ Vp, int nn, const do
 // 1-based accessors of a column's planes
 #define PL(a, k) (a)[c + (size_t)((k)-1) * np]
 #define ALE_BFSQ_MIN 1.e-7
-#define ALE_GRAV 9.806
-#define ALE_EPSILP 1.e-12
 #define ALE_MVAL (-1.e33)
 
 // first half, :311-404: interface densities of the reconstructed T, S (the diagnostic array sigint), then the layer densities
@@ -236,7 +218,7 @@ __global__ void k_ale_p_src_dst(const DevView *__restrict__ Vp, int nn, const do
 __global__ void k_ale_direct_pre(const DevView *__restrict__ Vp, int nn, const double *__restrict__ psrc, const double *__restrict__ pcT,
                                  const double *__restrict__ pcS, int npc, double *__restrict__ sgs, double *__restrict__ sgt, int ring) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const int kk = V.kk;
   const bool col = j >= 1 - ring && j <= V.jj + ring && i >= 1 - ring && i <= V.ii + ring && V.m[I_ip][c];
@@ -266,12 +248,12 @@ __global__ void k_ale_direct_pre(const DevView *__restrict__ Vp, int nn, const d
   gcd_t sigma = V.f[F_sigma] + (size_t)nn * np, sigmar = V.f[F_sigmar];
   for (int k = 1; k <= kk; k++) { PL(sgs, k) = PL(sigma, k); PL(sgt, k) = PL(sigmar, k); }              // :330-335
   PL(sgt, kk + 1) = PL(sgt, kk);
-  const double beta = ALE_BFSQ_MIN / (ALE_GRAV * ALE_GRAV);
+  const double beta = ALE_BFSQ_MIN / (GRAV * GRAV);
 #define P(k) PL(psrc, k)
 #define S(k) PL(sgs, k)
   int kl = kk, ku = kl - 1;                                                           // :339-398
   while (ku > 0) {
-    bool thin = P(kl + 1) - P(ku) < ALE_EPSILP;
+    bool thin = P(kl + 1) - P(ku) < EPSILP;
     if (thin || S(kl) - S(ku) < .5 * beta * (P(kl + 1) - P(ku))) {
       double sdpsum = S(ku) * (P(ku + 1) - P(ku)) + S(kl) * (P(kl + 1) - P(kl));
       double smean = 0.;
@@ -282,7 +264,7 @@ __global__ void k_ale_direct_pre(const DevView *__restrict__ Vp, int nn, const d
           if (thin) {
             ku = ku - 1;
             sdpsum = sdpsum + S(ku) * (P(ku + 1) - P(ku));
-            thin = P(kl + 1) - P(ku) < ALE_EPSILP;
+            thin = P(kl + 1) - P(ku) < EPSILP;
             if (!thin) smean = sdpsum / (P(kl + 1) - P(ku));
             added = true;
           } else if (smean - S(ku - 1) < .5 * beta * (P(kl + 1) - P(ku - 1))) {
@@ -296,7 +278,7 @@ __global__ void k_ale_direct_pre(const DevView *__restrict__ Vp, int nn, const d
           if (thin) {
             kl = kl + 1;
             sdpsum = sdpsum + S(kl) * (P(kl + 1) - P(kl));
-            thin = P(kl + 1) - P(ku) < ALE_EPSILP;
+            thin = P(kl + 1) - P(ku) < EPSILP;
             if (!thin) smean = sdpsum / (P(kl + 1) - P(ku));
             added = true;
           } else if (S(kl + 1) - smean < .5 * beta * (P(kl + 2) - P(ku))) {
@@ -322,7 +304,7 @@ __global__ void k_ale_direct_post(const DevView *__restrict__ Vp, const double *
                                   const double *__restrict__ sgt, const double *__restrict__ plevel, double dpmin_interior,
                                   int k_range_plevel, double *__restrict__ pdst, int ring) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const int kk = V.kk;
   const bool col = j >= 1 - ring && j <= V.jj + ring && i >= 1 - ring && i <= V.ii + ring && V.m[I_ip][c];
@@ -451,7 +433,7 @@ __global__ __launch_bounds__(256) void k_ale_nudge(const DevView *__restrict__ V
                             double *__restrict__ sd2, double *__restrict__ sgt, double *__restrict__ dsg, double *__restrict__ spm,
                             double *__restrict__ dpm, double *__restrict__ pdst, double *__restrict__ sfac) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const int kk = V.kk;
   const bool col = j >= 1 - Q.ring && j <= V.jj + Q.ring && i >= 1 - Q.ring && i <= V.ii + Q.ring && V.m[I_ip][c];
@@ -651,7 +633,7 @@ __global__ __launch_bounds__(256) void k_ale_nudge(const DevView *__restrict__ V
         } else {
           const double dsigdx_up = dsigdt_(V.P, tu, su) * dbT + dsigds_(V.P, tu, su) * dbS;
           const double dsigdx_lo = dsigdt_(V.P, tl, sl) * dtT + dsigds_(V.P, tl, sl) * dtS;
-          const double dp_up = fmax2(p_0 - p_m, ALE_EPSILP), dp_lo = fmax2(p_1 - p_0, ALE_EPSILP);
+          const double dp_up = fmax2(p_0 - p_m, EPSILP), dp_lo = fmax2(p_1 - p_0, EPSILP);
           double sig_intrp = ((sd1 + .5 * dsigdx_lo) * dp_up + (sd2_m - .5 * dsigdx_up) * dp_lo) / (dp_up + dp_lo);
           sig_intrp = fmax2(fmin2(sd2_m, sd1), fmin2(fmax2(sd2_m, sd1), sig_intrp));
           const double dsig = st - sig_intrp;
@@ -719,7 +701,7 @@ __global__ __launch_bounds__(256) void k_ale_nudge(const DevView *__restrict__ V
         k = ks;
       } else {
         const double dp_up = D(ku) - D(ku - 1), dp_lo = D(kl + 1) - D(kl);
-        D(ku) = fmax2(D(ku - 1), D(ku) - (dpmin_sum - dp_sum) * dp_up / fmax2(ALE_EPSILP, dp_up + dp_lo));
+        D(ku) = fmax2(D(ku - 1), D(ku) - (dpmin_sum - dp_sum) * dp_up / fmax2(EPSILP, dp_up + dp_lo));
         for (int q = ku; q <= kl - 1; q++) D(q + 1) = fmin2(D(ke + 1), D(q) + DM(q));
         k = kl;
       }
@@ -746,7 +728,7 @@ __global__ __launch_bounds__(256) void k_ale_nudge(const DevView *__restrict__ V
 __global__ void k_ale_smooth(const DevView *__restrict__ Vp, double smooth_diff_max, const double *__restrict__ pdst,
                              const double *__restrict__ sfac, double *__restrict__ pout, int ring) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const int kk = V.kk, ni = V.ni;
   const int k = blockIdx.y + 1;                                  // interface 1..kk+1
@@ -794,7 +776,7 @@ __global__ void k_ale_smooth(const DevView *__restrict__ Vp, double smooth_diff_
 __global__ void k_ale_copy_back(const DevView *__restrict__ Vp, int nn, const double *__restrict__ pdst, const double *__restrict__ rm,
                                 int f0, int nf, const double *__restrict__ flx, int ntr_loc) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, per = (size_t)V.kk * np;
   const int k = blockIdx.y;
@@ -819,7 +801,7 @@ __global__ void k_ale_copy_back(const DevView *__restrict__ Vp, int nn, const do
 // the new layer thicknesses alone (copy_jslice_to_3d's dp, :1168), ahead of the copy-back of the tracers
 __global__ void k_ale_dp_new(const DevView *__restrict__ Vp, int nn, const double *__restrict__ pdst) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int k = blockIdx.y;
@@ -829,7 +811,7 @@ __global__ void k_ale_dp_new(const DevView *__restrict__ Vp, int nn, const doubl
 // :1696-1711 pu, pv from the OLD dpu, dpv of the interior velocity points
 __global__ void k_ale_pupv(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t np = V.nplane;
   if (V.m[I_iu][c]) {
@@ -845,7 +827,7 @@ __global__ void k_ale_pupv(const DevView *__restrict__ Vp, int nn) {
 // :1715-1733 the old bottom pressure into util1 (j = -2..jj+3, i = -1..ii), then p from the new dp (i = -2..ii+3)
 __global__ void k_ale_pscan(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -2 || j > V.jj + 3 || i < -2 || i > V.ii + 3 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   if (i >= -1 && i <= V.ii) V.f[F_util1][c] = V.f[F_p][c + (size_t)V.kk * np];
@@ -859,7 +841,7 @@ __global__ void k_ale_pscan(const DevView *__restrict__ Vp, int nn) {
 __global__ void k_ale_uv_src_dst(const DevView *__restrict__ Vp, int nn, double *__restrict__ psrc, double *__restrict__ pdst,
                                  double *__restrict__ uin, int *__restrict__ active) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const int isv = blockIdx.y;
   const size_t np = V.nplane, nc = 2 * np, cc = c + (size_t)isv * np;
   const int kk = V.kk;
@@ -879,7 +861,7 @@ __global__ void k_ale_uv_src_dst(const DevView *__restrict__ Vp, int nn, double 
 
 __global__ void k_ale_uv_back(const DevView *__restrict__ Vp, int nn, const double *__restrict__ rm) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const int isv = blockIdx.z;
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !(isv ? V.m[I_iv][c] : V.m[I_iu][c])) return;
   const int k = blockIdx.y;
@@ -1226,7 +1208,7 @@ int st_ale_regrid_remap(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
 // columns take no part
 __global__ __launch_bounds__(256) void k_ale_zl_p_src(const DevView *__restrict__ Vp, int mm, double *__restrict__ psrcp, int *__restrict__ activep) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const size_t np = V.nplane;
   const bool col = j >= 1 && j <= V.jj && i >= 1 && i <= V.ii && V.m[I_ip][c];
   global_ptr(activep)[c] = col;
@@ -1248,7 +1230,7 @@ __global__ __launch_bounds__(256) void k_ale_zl_p_src(const DevView *__restrict_
 __global__ __launch_bounds__(256) void k_ale_zl_uv_src(const DevView *__restrict__ Vp, int mm, double *__restrict__ psrcp, double *__restrict__ uinp,
                                                        int *__restrict__ activep) {
   const DevView &V = *Vp;
-  PLANE_T(V);
+  THREAD_IJ_NATURAL(V);
   const int isv = blockIdx.y;
   const size_t np = V.nplane, nc = 2 * np, cc = c + (size_t)isv * np;
   const int kk = V.kk;

@@ -9,16 +9,8 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define GRAV 9.806
-#define SPCIFH 3990.
-#define ALPHA0 1.e-3
-#define DPMIN_VDIFF (0.1 * 9806.)
+#define DPMIN_VDIFF (0.1 * ONEM)
 
-#define COL(V)                                                             \
-  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;                    \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
 #define L(a, k) (a)[c + (size_t)((k)-1) * np]
 
 // T, S and up to NTB tracers of a column in ONE forward and ONE backward sweep.  The reference solves field after field (:112-203);
@@ -35,7 +27,7 @@ __device__ __forceinline__ void vdifft_pass(const DevView &V, size_t c, int nn, 
   const double cpi = 1. / SPCIFH, dtg = V.P.delt1 * GRAV, cc = GRAV * GRAV * V.P.delt1 / (ALPHA0 * ALPHA0);
   gcd_t __restrict__ dp = V.f[F_dp] + (size_t)nn * np;
   gd_t __restrict__ temp = V.f[F_temp] + (size_t)nn * np, saln = V.f[F_saln] + (size_t)nn * np;
-  gd_t __restrict__ gamT = WK(V, 0), gamS = WK(V, 1);
+  gd_t __restrict__ gamT = WK(V, VD_GAM0), gamS = WK(V, VD_GAM1);
   gcd_t __restrict__ nut = V.f[F_kdiff_t], nus = V.f[F_kdiff_s];
   const double hfsw = V.f[F_sswflx][c], hfns = V.f[F_surflx][c] - hfsw, hfrs = V.f[F_surrlx][c];       // :86-93
   const double sfbr = V.f[F_brnflx][c], sfnb = V.f[F_salflx][c] - sfbr, sfrs = V.f[F_salrlx][c];
@@ -148,7 +140,7 @@ __device__ __forceinline__ void vdifft_pass(const DevView &V, size_t c, int nn, 
 
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_ale_vdifft(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COL(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk, ntr = V.ntr;
@@ -196,7 +188,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
 // blockIdx.y = 0: u-columns, 1: v-columns, :258-356
 __global__ __launch_bounds__(64) void k_ale_vdiffm(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COL(V);
+  THREAD_IJ_NATURAL(V);
   const bool isv = blockIdx.y == 1;
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !(isv ? V.m[I_iv][c] : V.m[I_iu][c])) return;
   const size_t np = V.nplane, mns = isv ? c - V.ni : c - 1;
@@ -204,7 +196,7 @@ __global__ __launch_bounds__(64) void k_ale_vdiffm(const DevView *__restrict__ V
   const double cc = GRAV * GRAV * V.P.delt1 / (ALPHA0 * ALPHA0);
   gcd_t dp = (isv ? V.f[F_dpv] : V.f[F_dpu]) + (size_t)nn * np, kv = V.f[F_kvisc_m];
   gd_t x = (isv ? V.f[F_v] : V.f[F_u]) + (size_t)nn * np;
-  gd_t gam = WK(V, isv ? 1 : 0);
+  gd_t gam = WK(V, isv ? VD_GAM1 : VD_GAM0);
   // fp(k) = nuv(k) * fpbase(k) is formed once per level and carried to the next one (the reference forms it as fp(k+1) at level k
   // and again as fp(k) at level k+1: the same product); the next four levels' inputs are loaded ahead
   auto fpv = [&](double kva, double kvb, double dpa, double dpb) {
@@ -283,11 +275,9 @@ int st_ale_vdiffm(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n
 //      of mod_swabs -- netCDF-bound, hence uploaded), mld (mod_cmnfld), the surface fluxes; scalars swamxd, brine_mlbase_frac.
 //      Parity: cross-checked against the real module built against a stand-in for mod_swabs (oracle/xcheck) -- not a pin.
 #include "exp_libm.h"
-#define ONEM 9806.
-#define ONEMU .009806
 __global__ __launch_bounds__(64) void k_ale_forcing(const DevView *__restrict__ Vp, int nn, double swamxd, double brine_mlbase_frac) {
   const DevView &V = *Vp;
-  COL(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;

@@ -12,18 +12,10 @@
 // reference's order of operations.
 #include "blomgpu_internal.h"
 
-#define ONEM 9806.
-
-#define THREAD_IJ(V)                                                       \
-  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;                    \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
 // ---- :177-224 velocity bounds and coastal wave breaking coefficients (column max/min of u,v) ----
 __global__ void k_bt_bounds(const DevView *__restrict__ Vp, int m, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t np = V.nplane, om = c + (size_t)(m - 1) * np;
   if (V.m[I_iu][c]) {
@@ -63,14 +55,14 @@ __global__ void k_bt_bounds(const DevView *__restrict__ Vp, int m, int nn) {
 // ones; per q-point the surviving value is that of the LAST writer in that order. ------------
 __global__ void k_bt_pvtrop_old(const DevView *__restrict__ Vp, int n) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -2 || j > V.jj + 3 || i < 0 || i > V.ii + 1) return;
   V.f[F_pvtrop_o][c] = V.f[F_pvtrop][c + (size_t)(n - 1) * V.nplane];
 }
 
 __global__ void k_bt_pvtrop(const DevView *__restrict__ Vp, int n) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   const int ii = V.ii, jj = V.jj, ni = V.ni;
   if (j < 0 || j > jj + 1 || i < 0 || i > ii + 1) return;
   gcd_t pb_p = V.f[F_pb_p];
@@ -100,7 +92,7 @@ __global__ void k_bt_pvtrop(const DevView *__restrict__ Vp, int n) {
 // ---- nb == 1 reload of the subcycling state, :339-348 --------------------------------------------
 __global__ void k_bt_load(const DevView *__restrict__ Vp) {   // always into buffer set 0 (*_t)
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   for (int l = 0; l < 2; l++) {
     const size_t o = c + (size_t)l * V.nplane;
@@ -112,7 +104,7 @@ __global__ void k_bt_load(const DevView *__restrict__ Vp) {   // always into buf
 
 __global__ void k_bt_zero_sums(const DevView *__restrict__ Vp) {       // :361-379
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j >= -1 && j <= V.jj + 2 && i >= 0 && i <= V.ii + 1 && V.m[I_iu][c]) { V.f[F_ubflxs_t][c] = 0.; V.f[F_ubcors_t][c] = 0.; }
   if (j >= 0 && j <= V.jj + 2 && i >= 0 && i <= V.ii && V.m[I_iv][c]) { V.f[F_vbflxs_t][c] = 0.; V.f[F_vbcors_t][c] = 0.; }
 }
@@ -127,7 +119,7 @@ struct BtArgs {
 // ---- continuity, :401-411 / :626-636 ---------------------------------------------------------------
 __global__ void k_bt_cont(const DevView *__restrict__ Vp, BtArgs a) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < a.j0 || j > a.j1 || i < a.i0 || i > a.i1 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, oml = (size_t)(a.ml - 1) * np, onl = (size_t)(a.nl - 1) * np;
   const double wbaro = V.P.wbaro, dlt = V.P.dlt;
@@ -140,7 +132,7 @@ __global__ void k_bt_cont(const DevView *__restrict__ Vp, BtArgs a) {
 // ---- u momentum, :420-457 / :745-781 (enscon) and :464-502 / :788-826 (enecon, enedis) ------------
 __global__ void k_bt_umom(const DevView *__restrict__ Vp, BtArgs a) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < a.j0 || j > a.j1 || i < a.i0 || i > a.i1 || !V.m[I_iu][c]) return;
   const size_t np = V.nplane, oml = (size_t)(a.ml - 1) * np, onl = (size_t)(a.nl - 1) * np;
   const size_t om = (size_t)(a.m - 1) * np, on = (size_t)(a.n - 1) * np;
@@ -175,7 +167,7 @@ __global__ void k_bt_umom(const DevView *__restrict__ Vp, BtArgs a) {
 // ---- v momentum, :520-557 / :646-682 (enscon) and :564-602 / :690-728 ------------------------------
 __global__ void k_bt_vmom(const DevView *__restrict__ Vp, BtArgs a) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < a.j0 || j > a.j1 || i < a.i0 || i > a.i1 || !V.m[I_iv][c]) return;
   const size_t np = V.nplane, oml = (size_t)(a.ml - 1) * np, onl = (size_t)(a.nl - 1) * np;
   const size_t om = (size_t)(a.m - 1) * np, on = (size_t)(a.n - 1) * np;
@@ -210,7 +202,7 @@ __global__ void k_bt_vmom(const DevView *__restrict__ Vp, BtArgs a) {
 // ---- phase epilogues, :847-977 ------------------------------------------------------------------------
 __global__ void k_bt_epilogue(const DevView *__restrict__ Vp, int nb, int m, int n, int ml, int nl, int set) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t np = V.nplane, om = (size_t)(m - 1) * np, on = (size_t)(n - 1) * np;
   const size_t oml = (size_t)(ml - 1) * np, onl = (size_t)(nl - 1) * np, o3 = 2 * np;
@@ -305,24 +297,10 @@ __global__ void k_bt_arctic_swap(const DevView *__restrict__ Vp, int n) {
   }
 }
 
-int bt_pair_halo(blomgpu_ctx *c, int set);
-bool bt_phase_usable(blomgpu_ctx *c);
-int bt_phase_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, double woa, double wob, double wna, double wnb, int lll0,
-                    int last, int src, int *src_out, int *ml_out, int *nl_out);
-int bt_phase_check(blomgpu_ctx *c);
-int bt_overlap_usable(blomgpu_ctx *c);
-int bt_block_mode(blomgpu_ctx *c);
-int bt_block_launch(blomgpu_ctx *c, int mode, int m, int n, int ml, int nl, const int *ph_last, const double (*ph_w)[4], int src,
-                    int *src_out, int *ml_out, int *nl_out);
-int bt_pair_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, const double *wo, const double *wm, const double *wn,
-                   int do_odd, int do_even, int src, int tsel, RcclLanded *rim);
-int bt_pair_halo_landed(blomgpu_ctx *c, int set, RcclLanded *landed);
-
 int st_barotp_bounds(blomgpu_ctx *c, int m, int nn) {
   hipLaunchKernelGGL(k_bt_bounds, plane_grid(c->h, 1, 64), dim3(64), 0, c->stream, c->d, m, nn);
   return 0;
 }
-int st_barotp_on(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n, bool with_bounds);
 int st_barotp(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   TimeScope ts(c, "barotp");
   // RCCL tiles with a global barotropic context attached: gather, solve the whole 2-D domain here, take the window

@@ -906,7 +906,6 @@ int bt_pair_halo(blomgpu_ctx *c, int set) {
   return 0;
 }
 
-bool bt_phase_usable(blomgpu_ctx *c);
 // Tile shape of the one-pair-per-launch form.  Where the persistent form runs, its shape; otherwise chosen from the
 // number of tiles (option barotp_tile = 3216 / 3208 / 1608 overrides).
 static BtShape bt_phase_shape(blomgpu_ctx *c);

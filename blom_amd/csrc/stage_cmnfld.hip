@@ -9,30 +9,16 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define GRAV 9.806
-#define RHO0 1.e3
-#define EPSILP 1.e-12
-#define ONEM 9806.
-#define ONEMM 9.806
 // phy/mod_cmnfld.F90:36-46
 #define SLS0 (10. * ONEM)
 #define SLSMFQ 2.
 #define SLSELS 2.
 #define BFSQMN 1.e-7
 
-// (CM_GAM behind the nine slots of difest_isobml's kernels, stage_difest_iso.hip: inside blomgpu_step k_cmn_bfsqf runs beside them)
-enum { CM_DELP, CM_BFSQ, CM_SLS2, CM_GAM_ALE, CM_GAM = 9, CM_NSLOT };   // (the hybrid coordinate's kernel keeps its slot)
-
-#define COLUMN_IJ(V)                                                     \
-  const int t_ = blockIdx.x * blockDim.x + threadIdx.x;                  \
-  if (t_ >= (V).nplane) return;                                          \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);  \
-  const size_t c = t_
-
 // ---- :61-227 ---------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_cmn_bfsqf(const DevView *__restrict__ Vp, int n, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -1 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -165,7 +151,7 @@ __global__ __launch_bounds__(64) void k_cmn_bfsqf(const DevView *__restrict__ Vp
 // ---- geopotential at layer interfaces, :437-455 ---------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_cmn_phi(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -1 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -198,7 +184,7 @@ __global__ __launch_bounds__(64) void k_cmn_phi(const DevView *__restrict__ Vp, 
 template <int NB>
 __global__ __launch_bounds__(64) void k_cmn_nslope(const DevView *__restrict__ Vp, int n, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   const bool isv = blockIdx.y == 1;
   if (isv ? (j < 0 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_iv][c])
           : (j < -1 || j > V.jj + 2 || i < 0 || i > V.ii + 2 || !V.m[I_iu][c])) return;
@@ -282,7 +268,7 @@ __global__ __launch_bounds__(64) void k_cmn_nslope(const DevView *__restrict__ V
 // (the mixed-layer-depth estimates of :1110-1150 belong to the other vertical coordinates and to diagnostics)
 __global__ __launch_bounds__(64) void k_cmn_z(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -319,7 +305,7 @@ __global__ __launch_bounds__(64) void k_cmn_z(const DevView *__restrict__ Vp, in
 // the reference; the next four levels' p, T, S are loaded ahead.
 __global__ __launch_bounds__(64) void k_cmn_bfsqf_ale(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -1 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -417,7 +403,7 @@ __global__ __launch_bounds__(64) void k_cmn_bfsqf_ale(const DevView *__restrict_
 // cmnfld_bfsqi_ale, :352-421: p from dp (j,i = -2..+3), then the interface buoyancy frequency (j,i = 0..+1)
 __global__ __launch_bounds__(64) void k_cmn_bfsqi_ale(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 0 || j > V.jj + 1 || i < 0 || i > V.ii + 1 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -464,7 +450,7 @@ __global__ __launch_bounds__(64) void k_cmn_bfsqi_ale(const DevView *__restrict_
 // the columns (stage_ndiff.hip); here they are multiplied with the buoyancy frequency as far down as both columns reach
 __global__ __launch_bounds__(64) void k_cmn_nnslope_ale(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   const bool isv = blockIdx.y == 1;
   if (isv ? (j < 0 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_iv][c])
           : (j < -1 || j > V.jj + 2 || i < 0 || i > V.ii + 2 || !V.m[I_iu][c])) return;
@@ -491,7 +477,7 @@ __global__ __launch_bounds__(64) void k_cmn_nnslope_ale(const DevView *__restric
 // cmnfld_nslope_ale, :654-811 (after the geopotential, which is k_cmn_phi's loop): u- (blockIdx.y = 0) and v-points (1)
 __global__ __launch_bounds__(64) void k_cmn_nslope_ale(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   const bool isv = blockIdx.y == 1;
   if (isv ? (j < 0 || j > V.jj + 2 || i < -1 || i > V.ii + 2 || !V.m[I_iv][c])
           : (j < -1 || j > V.jj + 2 || i < 0 || i > V.ii + 2 || !V.m[I_iu][c])) return;
@@ -550,7 +536,7 @@ __global__ __launch_bounds__(64) void k_cmn_nslope_ale(const DevView *__restrict
 // p(k+1) = p(k) + dp(kn), j,i = -2..+3 (cmnfld_bfsqi_ale :364-375)
 __global__ __launch_bounds__(64) void k_cmn_pscan3(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < -2 || j > V.jj + 3 || i < -2 || i > V.ii + 3 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   double a = V.f[F_p][c];
@@ -573,11 +559,10 @@ int st_cmnfld_bfsqi_ale(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, i
 // the vertical coordinates other than isopyc_bulkml with mldmth = 'lev82' (:1121-1131).  DIAG: the form cmnfld1 runs under
 // isopyc_bulkml for the diagnostics mldl82 mldl82mn mldl82mx mldl82sq (:1109-1113; :1124 does not apply): it writes mldl82 only
 #define DBCL82 .0003
-#define ONECM 98.06
 template <bool DIAG>
 __global__ __launch_bounds__(64) void k_cmn_mldl82(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
-  COLUMN_IJ(V);
+  THREAD_IJ_NATURAL(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;

@@ -12,26 +12,14 @@
 #include "eos.h"
 #include "diapfl_common.h"
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
 #define MAXTR 64   // tracer sums of a column: dynamically indexed (private memory), any tracer count up to this
-enum { CV_UN = 0 };   // work field: remapped velocity column
 
 __global__ __launch_bounds__(64) void k_convec_column(const DevView *__restrict__ Vp, int n, int nn, int *errflag) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kk = V.kk, ntr = V.ntr;
   const size_t np = V.nplane;
-  const double epsilp = 1.e-12;
   // 1-based level k of the time level n: element c + (k - 1 + nn) * np
   gd_t ttem = V.f[F_temp] + c + (size_t)nn * np - np, ssal = V.f[F_saln] + c + (size_t)nn * np - np;
   gd_t delp = V.f[F_dp] + c + (size_t)nn * np - np, dens = V.f[F_sigma] + c + (size_t)nn * np - np;
@@ -60,7 +48,7 @@ __global__ __launch_bounds__(64) void k_convec_column(const DevView *__restrict_
 #pragma unroll
       for (int u = 0; u < COLUMN_U; u++) {
         if (!walking || k0 + u > kk) break;
-        if (a[u] < epsilp) {
+        if (a[u] < EPSILP) {
           dps = dps + a[u];
           DP(k0 + u) = 0.;
           k = k0 + u + 1;
@@ -177,7 +165,7 @@ __global__ __launch_bounds__(64) void k_convec_column(const DevView *__restrict_
       while (true) {
         const int kn = k + 1 <= kk ? k + 1 : kk;             // (the next level's values are on their way during the test)
         const double tn = TT(kn), sn = SS(kn), dn = DP(kn);
-        if (!(eos::rho(dps, ttmp, stmp) > eos::rho(dps, tk, sk) || dk < epsilp)) break;
+        if (!(eos::rho(dps, ttmp, stmp) > eos::rho(dps, tk, sk) || dk < EPSILP)) break;
         tdps = tdps + tk * dk;
         sdps = sdps + sk * dk;
         dps = dps + dk;
@@ -234,7 +222,7 @@ __global__ __launch_bounds__(64) void k_convec_column(const DevView *__restrict_
 template <int NSINGLE>
 __global__ __launch_bounds__(64) void k_convec_velocity(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const bool isv = by_ == 1;
   if (!V.m[isv ? I_iv : I_iu][c]) return;
@@ -335,7 +323,7 @@ __global__ __launch_bounds__(64) void k_convec_velocity(const DevView *__restric
 #define CVF_W 6
 __global__ __launch_bounds__(64) void k_convec_velocity_flat(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   __shared__ double s_pn[CVF_W][64], s_vel[CVF_W][64], s_po[CVF_W][64];
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const bool isv = by_ == 1;

@@ -31,24 +31,7 @@
 
 #define DPEPS 1.e-12
 
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
 enum { ST_0000 = 0, ST_1111, ST_1110, ST_0111, ST_1100, ST_0110, ST_0011, ST_0100, ST_0010 };   // :60-68
-
-// work-space slots
-enum { W_HM = 0, W_HF, W_HPC0, W_HPC1, W_HPC2, W_TE, /* + ntl */ };
-#define W_HTF(ntl) (W_TE + (ntl))
-#define W_TPC0(ntl) (W_TE + 2 * (ntl))
-#define W_TPC1(ntl) (W_TE + 3 * (ntl))
-#define W_TPC2(ntl) (W_TE + 4 * (ntl))
-#define W_NSLOT(ntl) (W_TE + 5 * (ntl))
 
 // ---- init_cppm: set_stencil_coeffs (:101-320), set_slope_coeffs (:322-341), set_d2_mask (:343-359) ----
 struct CppmTab {
@@ -74,7 +57,7 @@ __device__ inline CppmTab cppm_tab(const DevView &V, int dir) {
 
 __global__ void k_cppm_init(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   const int dir = by_;
   const size_t np = V.nplane;
   CppmTab T = cppm_tab(V, dir);
@@ -207,7 +190,7 @@ __global__ void k_cppm_init(const DevView *__restrict__ Vp) {
 // stencil tag halo through a real plane, :2612-2614 / :2635-2637
 __global__ void k_cppm_tag_convert(const DevView *__restrict__ Vp, int dir, int back) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   (void)i; (void)j;
   gi_t st = dir ? V.m[I_cppm_stj] : V.m[I_cppm_sti];
   if (!back) V.f[F_util1][c] = (double)st[c];
@@ -231,7 +214,7 @@ __device__ inline int cppm_mirror_tag(int st) {
 }
 __global__ void k_cppm_arctic_init_swap(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (V.j0 + V.jj != V.jtdm) return;                        // nproc == jpr
   const int which = by_;
   if (which == 0) {
@@ -283,7 +266,7 @@ int st_init_cppm(blomgpu_ctx *c) {
 template <int DIR>
 __global__ void k_cppm_arctic_edge_swap(const DevView *__restrict__ Vp, int w) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (V.j0 + V.jj != V.jtdm) return;
   if (DIR == 0) {
     if (j != V.jj || i < 1 - w || i > V.ii + w) return;
@@ -311,7 +294,7 @@ __global__ void k_cppm_arctic_edge_swap(const DevView *__restrict__ Vp, int w) {
 template <int DIR, int LIM>
 __global__ void k_cppm_hm(const DevView *__restrict__ Vp, int nn, int second_pass) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < -3 + LIM || s > sdm + 4 - LIM) return;
   const int k = by_;
@@ -321,7 +304,7 @@ __global__ void k_cppm_hm(const DevView *__restrict__ Vp, int nn, int second_pas
     gcd_t ca2 = (DIR ? V.f[F_cau] : V.f[F_cav]) + ok;
     h = h / (1. - (ca2[c + od] - ca2[c]) * V.f[F_scp2i][c]);
   }
-  WK(V, W_HM)[c + ok] = h;
+  WK(V, CP_HM)[c + ok] = h;
 }
 
 // Thickness edge values of cell c with limiting: h_edges_nosc :361-434 (LIM 0), h_edges_mono :436-488
@@ -387,13 +370,13 @@ __device__ inline void cppm_h_edges(const CppmTab &T, size_t c, int sd, const do
 template <int DIR, int LIM>
 __global__ void k_cppm_hedges(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < 1 || s > sdm) return;
   const size_t ok = (size_t)by_ * V.nplane;
   const CppmTab T = cppm_tab(V, DIR);
   double hel, her;
-  cppm_h_edges<LIM>(T, c, sd, WK(V, W_HM) + ok, hel, her);
+  cppm_h_edges<LIM>(T, c, sd, WK(V, CP_HM) + ok, hel, her);
   V.f[F_hel_3d][c + ok] = hel;
   V.f[F_her_3d][c + ok] = her;
 }
@@ -519,18 +502,18 @@ __device__ inline double *cppm_tracer(const DevView &V, int nt, int k, int nn) {
 template <int DIR, int LIM, int FC>
 __global__ void k_cppm_tedge(const DevView *__restrict__ Vp, int nn, int ntl) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < -1 + LIM || s > sdm + 3 - LIM) return;
   const int k = by_;
   const size_t np = V.nplane, ok = (size_t)k * np;
   const CppmTab T = cppm_tab(V, DIR);
   double t1, t2, t3, t4;
-  if (FC) cppm_tevc(T, np, c, sd, WK(V, W_HM) + ok, V.f[F_hel_3d] + ok, V.f[F_her_3d] + ok, t1, t2, t3, t4);
+  if (FC) cppm_tevc(T, np, c, sd, WK(V, CP_HM) + ok, V.f[F_hel_3d] + ok, V.f[F_her_3d] + ok, t1, t2, t3, t4);
   else { t1 = T.hevc[0][c]; t2 = T.hevc[1][c]; t3 = T.hevc[2][c]; t4 = T.hevc[3][c]; }
   for (int nt = 0; nt < ntl; nt++) {
     const double *tm = cppm_tracer(V, nt, k, nn);
-    WK(V, W_TE + nt)[c + ok] = t1 * tm[c - 2 * sd] + t2 * tm[c - sd] + t3 * tm[c] + t4 * tm[c + sd];
+    WK(V, CP_TE + nt)[c + ok] = t1 * tm[c - 2 * sd] + t2 * tm[c - sd] + t3 * tm[c] + t4 * tm[c + sd];
   }
 }
 
@@ -539,13 +522,13 @@ __global__ void k_cppm_tedge(const DevView *__restrict__ Vp, int nn, int ntl) {
 template <int DIR, int LIM, int FC>
 __global__ void k_cppm_parab(const DevView *__restrict__ Vp, int nn, int ntl) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < 0 || s > sdm + 1) return;
   const int k = by_;
   const size_t np = V.nplane, ok = (size_t)k * np;
   const CppmTab T = cppm_tab(V, DIR);
-  gcd_t hmv = WK(V, W_HM) + ok;
+  gcd_t hmv = WK(V, CP_HM) + ok;
   const double hm0 = hmv[c];
   double hel0, her0;
   // thickness factors of the tracer parabolas (FC) at s-1, s, s+1; for 'partial' they are constants
@@ -581,7 +564,7 @@ __global__ void k_cppm_parab(const DevView *__restrict__ Vp, int nn, int ntl) {
   }
   const double ssc = T.ssc[c], scc = T.scc[c];
   for (int nt = 0; nt < ntl; nt++) {
-    const double *tm = cppm_tracer(V, nt, k, nn), *te = WK(V, W_TE + nt) + ok;
+    const double *tm = cppm_tracer(V, nt, k, nn), *te = WK(V, CP_TE + nt) + ok;
     const double tmm = tm[c - sd], tm0 = tm[c], tmp = tm[c + sd];
     double tel = te[c], ter = te[c + sd];
     bool limit = true;
@@ -644,25 +627,25 @@ __global__ void k_cppm_parab(const DevView *__restrict__ Vp, int nn, int ntl) {
         }
       }
     }
-    WK(V, W_TPC0(ntl) + nt)[c + ok] = tel;
+    WK(V, CP_TPC0(ntl) + nt)[c + ok] = tel;
     if (FC) {
-      WK(V, W_TPC1(ntl) + nt)[c + ok] = hf1m * tm0 + hf1l * tel + hf1r * ter;
-      WK(V, W_TPC2(ntl) + nt)[c + ok] = hf2m[1] * tm0 + hf2l[1] * tel + hf2r[1] * ter;
+      WK(V, CP_TPC1(ntl) + nt)[c + ok] = hf1m * tm0 + hf1l * tel + hf1r * ter;
+      WK(V, CP_TPC2(ntl) + nt)[c + ok] = hf2m[1] * tm0 + hf2l[1] * tel + hf2r[1] * ter;
     } else {
-      WK(V, W_TPC1(ntl) + nt)[c + ok] = 6. * tm0 - 4. * tel - 2. * ter;
-      WK(V, W_TPC2(ntl) + nt)[c + ok] = 3. * (tel - 2. * tm0 + ter);
+      WK(V, CP_TPC1(ntl) + nt)[c + ok] = 6. * tm0 - 4. * tel - 2. * ter;
+      WK(V, CP_TPC2(ntl) + nt)[c + ok] = 3. * (tel - 2. * tm0 + ter);
     }
   }
-  WK(V, W_HPC0)[c + ok] = hel0;
-  WK(V, W_HPC1)[c + ok] = 6. * hm0 - 4. * hel0 - 2. * her0;
-  WK(V, W_HPC2)[c + ok] = 3. * (hel0 - 2. * hm0 + her0);
+  WK(V, CP_HPC0)[c + ok] = hel0;
+  WK(V, CP_HPC1)[c + ok] = 6. * hm0 - 4. * hel0 - 2. * her0;
+  WK(V, CP_HPC2)[c + ok] = 3. * (hel0 - 2. * hm0 + her0);
 }
 
 // flux_integration :1373-1468 + flux accumulation :1612-1618
 template <int DIR>
 __global__ void k_cppm_flux(const DevView *__restrict__ Vp, int n, int mm, int ntl) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < 1 || s > sdm + 1) return;
   const int k = by_;
@@ -671,7 +654,7 @@ __global__ void k_cppm_flux(const DevView *__restrict__ Vp, int n, int mm, int n
   const double ca = (DIR ? V.f[F_cav] : V.f[F_cau])[c + ok];
   const double db = (DIR ? V.f[F_pbv] : V.f[F_pbu])[c + (size_t)(n - 1) * np];
   gcd_t ai = V.f[F_scp2i], p = V.f[F_p];
-  gcd_t hpc0 = WK(V, W_HPC0) + ok, hpc1 = WK(V, W_HPC1) + ok, hpc2 = WK(V, W_HPC2) + ok;
+  gcd_t hpc0 = WK(V, CP_HPC0) + ok, hpc1 = WK(V, CP_HPC1) + ok, hpc2 = WK(V, CP_HPC2) + ok;
   double hf, p0, p1, p2;
   size_t up;
   if (ca < 0.) {
@@ -711,14 +694,14 @@ __global__ void k_cppm_flux(const DevView *__restrict__ Vp, int n, int mm, int n
       p2 = q2 * h0 + q3 * h1 + q4 * h2;
     }
   }
-  WK(V, W_HF)[c + ok] = hf;
+  WK(V, CP_HF)[c + ok] = hf;
   gd_t mflx = DIR ? V.f[F_vflx] : V.f[F_uflx], tflx = DIR ? V.f[F_vtflx] : V.f[F_utflx];
   gd_t sflx = DIR ? V.f[F_vsflx] : V.f[F_usflx];
   mflx[c + okm] = mflx[c + okm] + hf;
   for (int nt = 0; nt < ntl; nt++) {
-    const double htf = (p0 * WK(V, W_TPC0(ntl) + nt)[up + ok] + p1 * WK(V, W_TPC1(ntl) + nt)[up + ok] +
-                        p2 * WK(V, W_TPC2(ntl) + nt)[up + ok]) * ca;
-    WK(V, W_HTF(ntl) + nt)[c + ok] = htf;
+    const double htf = (p0 * WK(V, CP_TPC0(ntl) + nt)[up + ok] + p1 * WK(V, CP_TPC1(ntl) + nt)[up + ok] +
+                        p2 * WK(V, CP_TPC2(ntl) + nt)[up + ok]) * ca;
+    WK(V, CP_HTF(ntl) + nt)[c + ok] = htf;
     if (nt == 0) tflx[c + okm] = tflx[c + okm] + htf;
     if (nt == 1) sflx[c + okm] = sflx[c + okm] + htf;
   }
@@ -728,19 +711,19 @@ __global__ void k_cppm_flux(const DevView *__restrict__ Vp, int n, int mm, int n
 template <int DIR>
 __global__ void k_cppm_update(const DevView *__restrict__ Vp, int nn, int ntl) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   SWEEP_COORDS(V);
   if (o < 1 || o > odm || s < 1 || s > sdm) return;
   const int k = by_;
   const size_t np = V.nplane, ok = (size_t)k * np, okn = (size_t)(k + nn) * np;
   const double ai = V.f[F_scp2i][c];
   const double ho = fmax2(0., V.f[F_dp][c + okn]) + DPEPS;
-  gcd_t hf = WK(V, W_HF) + ok;
+  gcd_t hf = WK(V, CP_HF) + ok;
   const double hn = ho - (hf[c + sd] - hf[c]) * ai;
   const double hni = 1. / hn;
   for (int nt = 0; nt < ntl; nt++) {
     double *tm = cppm_tracer(V, nt, k, nn);
-    gcd_t htf = WK(V, W_HTF(ntl) + nt) + ok;
+    gcd_t htf = WK(V, CP_HTF(ntl) + nt) + ok;
     tm[c] = (ho * tm[c] - (htf[c + sd] - htf[c]) * ai) * hni;
   }
   V.f[F_dp][c + okn] = fmax2(0., hn - DPEPS);
@@ -791,7 +774,7 @@ int st_cppm(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   (void)m; (void)k1m;
   const DevView &h = c->h;
   if (!c->cppm_ready) return ctx_fail(c, "cppm: init_cppm has not been called (blomgpu_init_cppm)");
-  if (W_NSLOT(2 + h.ntr) > h.nwk) return ctx_fail(c, "cppm: device work space too small for this many tracers");
+  if (CP_NSLOT(2 + h.ntr) > h.nwk) return ctx_fail(c, "cppm: device work space too small for this many tracers");
   const bool fc = c->cppm_compat == 1, mono = c->cppm_limiting == 1;
   if (fc) return mono ? cppm_variant<1, 1>(c, n, mm, nn, k1n) : cppm_variant<0, 1>(c, n, mm, nn, k1n);
   return mono ? cppm_variant<1, 0>(c, n, mm, nn, k1n) : cppm_variant<0, 0>(c, n, mm, nn, k1n);

@@ -45,12 +45,9 @@ enum { A_NONE = 0, A_UB = 1, A_VB = 2, A_PLANE = 3, A_ONEM = 4 };   // fld = src
 // the level of the source that the reference passes (0-based plane of the field; a layer row adds its layer)
 enum { LV_0, LV_M, LV_N, LV_KK, LV_MM, LV_NN, LV_TKE, LV_GLS };
 enum { SRC_DPML = -1 };                             // dpml as :1148-1171 forms it
-constexpr double ONEM = 9806.;                      // phy/mod_constants.F90
-constexpr double SPVAL = 1.e33;                     // -spval: inival of maxbld (:5948) and mldl82mx (:5901); +spval: of mldl82mn (:5900)
-constexpr double ONECM = 98.06, ONEMM = 9.806;      // phy/mod_constants.F90:51-52
+// (SPVAL: -spval is the inival of maxbld (:5948) and mldl82mx (:5901), +spval of mldl82mn (:5900))
 constexpr double DPBOT = ONEM;                      // phy/mod_dia.F90:196
 constexpr double EPSIL = 1.e-11, NF90_FILL_DOUBLE = 9.9692099683868690e+36;   // finlyr, :6126, :6140
-constexpr double EPSILP = 1.e-12;                   // phy/mod_constants.F90:43
 constexpr double SIGEPS = 1.e-9;                    // phy/mod_dia.F90:1120
 constexpr double DZEPS = 1e1 * EPSILP, DPEPS = 1e5 * EPSILP, FLXEPS = 1e5 * EPSILP;   // diazlv, :4760-4762
 

@@ -12,20 +12,6 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define GRAV 9.806
-#define ALPHA0 1.e-3
-#define EPSILP 1.e-12
-#define ONEM 9806.
-
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
 // 1-based layer index k, as in the Fortran
 #define AR(slot, k) WK(V, slot)[c + (size_t)((k)-1) * np]
 
@@ -33,7 +19,7 @@
 
 __global__ void k_diapfl_kming(const DevView *__restrict__ Vp) {                                // :725-733
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 0 || j > V.jj + 1 || i < 0 || i > V.ii + 1 || !V.m[I_ip][c]) return;
   V.m[I_kming][c] = (int)rint(V.f[F_util1][c]);
 }
@@ -43,7 +29,6 @@ __global__ void k_diapfl_kming(const DevView *__restrict__ Vp) {                
 // kmin, kmin+1) are the velocity and thickness arrays themselves under the position -> layer map
 // (kmin -> 1, kmin+1 -> 2), the interface fluxes fpu/fpl are evaluated where the tridiagonal sweep
 // consumes them, and the forward-eliminated velocity is kept in place; only gtd needs a work plane.
-enum { U_GTD = 0, U_NSLOT };
 
 // fluxes through the upper interface of position k (fpu(k)) and, same interface seen from above,
 // fpl(k-1): the average of the two neighbouring p-columns, clipped at the velocity-point bottom (:779-817)
@@ -92,7 +77,7 @@ __device__ inline void diapfl_mom_flux(const double *p, const double *fpug, cons
 
 __global__ void k_diapfl_momentum(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const bool isv = by_ == 1;
   if (!(isv ? V.m[I_iv][c] : V.m[I_iu][c])) return;
@@ -190,7 +175,7 @@ __global__ void k_diapfl_momentum(const DevView *__restrict__ Vp, int nn) {
 // dpu/dpv at the new level from the updated p, :971-1000 (u: i 1..ii+1, j 1..jj ; v: i 1..ii, j 1..jj+1)
 __global__ void k_diapfl_dpudpv(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   const int k = by_;
   const size_t np = V.nplane, o0 = (size_t)k * np, o1 = (size_t)(k + 1) * np, ob = (size_t)V.kk * np;
   gcd_t p = V.f[F_p];

@@ -23,24 +23,19 @@
 // Work planes: dsgu dsgl fcu fcl fmax h r t f ft gtd (11) + pres (wkp1).
 #include "diapfl_common.h"
 
-#define GRAV DIAPFL_GRAV
-#define ALPHA0 DIAPFL_ALPHA0
-#define EPSILP DIAPFL_EPSILP
-#define ONEM DIAPFL_ONEM
 #define MAXTR 4
 // level index clamped into [lo, hi]: a look-ahead past the end of a sweep reads the last level again
 #define CLAMPK(k, lo, hi) ((k) < (lo) ? (lo) : ((k) > (hi) ? (hi) : (k)))
 
-enum { E_SU, E_SL, E_FCU, E_FCL, E_FMAX, E_H, E_R, E_T, E_F, E_FT, E_GTD, E_NSLOT };
-// the work space of this kernel, wavefront-major: level k of the 64 columns of wavefront b holds its E_NSLOT values
+// the work space of this kernel, wavefront-major: level k of the 64 columns of wavefront b holds its D3_NSLOT values
 // and the interface pressure in WNS consecutive rows of 64 doubles, at wk + (((b*(kk+1) + k-1)*WNS + slot)*64 + lane).
 // A sweep reads and writes 3-8 slots of a level: with the slots of a level side by side they are one 6 KB piece of
 // memory instead of pieces of 512 B that lie 45 MB apart.
-#define WNS (E_NSLOT + 1)
+#define WNS (D3_NSLOT + 1)
 #define W(slot, k) wb[((size_t)((k)-1) * WNS + (slot)) * 64]
 #define ST(a, k) (a)[c + (size_t)((k)-1) * np]
 #define SIGR(k) sigr[c + (size_t)((k)-1) * np]
-#define PRES(k) wb[((size_t)((k)-1) * WNS + E_NSLOT) * 64]
+#define PRES(k) wb[((size_t)((k)-1) * WNS + D3_NSLOT) * 64]
 #define TRC(nt, k) trc[c + (size_t)((k)-1 + (nt)*2 * kk) * np]
 
 // one wavefront per 64 columns and ~1700 wavefronts in all: occupancy cannot exceed 2 waves per SIMD anyway,
@@ -199,7 +194,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
               const double q = ((fmax_p + fcu_p) * sui_p + presb - a6[u]) * sl;
               fcl = fmax2(-q, fcl);
               fmax_p = q + fcl;
-              W(E_SU, k) = su; W(E_SL, k) = sl; W(E_FCU, k) = fcu; W(E_FCL, k) = fcl; W(E_FMAX, k) = fmax_p;
+              W(D3_SU, k) = su; W(D3_SL, k) = sl; W(D3_FCU, k) = fcu; W(D3_FCL, k) = fcl; W(D3_FMAX, k) = fmax_p;
               fcu_p = fcu;
               sui_p = 1. / su;
               tp = tk; sp = sk; dens_p = dens_k; sr_p = sr_k;
@@ -212,7 +207,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
           for (int u = 0; u < DU; u++) {
             const int kq = CLAMPK(k0 - u, kfpl, kmax - 1);
-            a0[u] = PRES(kq + 1); a1[u] = W(E_SL, kq); a2[u] = W(E_FCL, kq); a3[u] = W(E_FCU, kq); a4[u] = W(E_SU, kq);
+            a0[u] = PRES(kq + 1); a1[u] = W(D3_SL, kq); a2[u] = W(D3_FCL, kq); a3[u] = W(D3_FCU, kq); a4[u] = W(D3_SU, kq);
           }
 #pragma unroll
           for (int u = 0; u < DU; u++) {
@@ -220,9 +215,9 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
             if (k >= kfpl) {
               const double q = ((fmax_p + fcu_p) * sui_p + presb - a0[u]) * a1[u];
               const double fcl = fmax2(-q, a2[u]);
-              W(E_FCL, k) = fcl;
+              W(D3_FCL, k) = fcl;
               fmax_p = q + fcl;
-              W(E_FMAX, k) = fmax_p;
+              W(D3_FMAX, k) = fmax_p;
               fcu_p = a3[u];
               sui_p = 1. / a4[u];
             }
@@ -243,10 +238,10 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
           const double sg = .5 * (su + sl);                                                                               \
           const double sui = 1. / su, sli = 1. / sl;                                                                      \
           const double fk = fmin2(fmin2(v_fm, .5 * sqrt(cc * v_nu * sg * (sui + sli)) * shm), cc * v_nu * sg / fmax2(EPSILP, v_dp)); \
-          W(E_F, kl) = fk;                                                                                                \
-          W(E_H, kl) = v_fcu * sui - v_fcl * sli + g_fcl_m * g_sli_m - (fcu_n) * (1. / (su_n));                          \
-          W(E_R, kl) = 4. * cc * v_nu * sg * (sui + sli);                                                                 \
-          W(E_T, kl) = .25 * shm;                                                                                         \
+          W(D3_F, kl) = fk;                                                                                                \
+          W(D3_H, kl) = v_fcu * sui - v_fcl * sli + g_fcl_m * g_sli_m - (fcu_n) * (1. / (su_n));                          \
+          W(D3_R, kl) = 4. * cc * v_nu * sg * (sui + sli);                                                                 \
+          W(D3_T, kl) = .25 * shm;                                                                                         \
           dflim = fmax2(dflim, v_fm);                                                                                     \
           g_fcl_m = v_fcl; g_sli_m = sli;                                                                                 \
         }
@@ -255,7 +250,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
           for (int u = 0; u < DH; u++) {
             const int kq = CLAMPK(k0 + u, kfpl, kmax - 1);
-            a0[u] = PRES(kq); a1[u] = W(E_SU, kq); a2[u] = W(E_FCU, kq); a3[u] = W(E_FMAX, kq); a4[u] = W(E_FCL, kq); a5[u] = W(E_SL, kq);
+            a0[u] = PRES(kq); a1[u] = W(D3_SU, kq); a2[u] = W(D3_FCU, kq); a3[u] = W(D3_FMAX, kq); a4[u] = W(D3_FCL, kq); a5[u] = W(D3_SL, kq);
             a6[u] = ST(nu, kq); a7[u] = ST(dp, kq);
           }
 #pragma unroll
@@ -264,9 +259,9 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
             if (k <= kmax - 1) {
               const double q = ((fmax_m - fcl_m) * sli_m + a0[u] - preskf) * a1[u];
               double fcu = a2[u];
-              if (fcu > q) { fcu = q; W(E_FCU, k) = q; done = false; }
+              if (fcu > q) { fcu = q; W(D3_FCU, k) = q; done = false; }
               double fm = a3[u];
-              if (fm > q - fcu) { fm = q - fcu; W(E_FMAX, k) = fm; kfmaxu = k; }
+              if (fm > q - fcu) { fm = q - fcu; W(D3_FMAX, k) = fm; kfmaxu = k; }
               fmax_m = fm;
               fcl_m = a4[u];
               sli_m = 1. / a5[u];
@@ -298,15 +293,15 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               const int kq = CLAMPK(k0 + u, kfpl, kmax - 1), kn = CLAMPK(kq + 1, kfpl, kmax - 1);
-              a0[u] = W(E_FMAX, kq); a1[u] = W(E_F, kn); a2[u] = W(E_SU, kn); a3[u] = ST(dp, kq); a4[u] = W(E_H, kq);
-              a5[u] = W(E_R, kq); a6[u] = W(E_T, kq); a7[u] = W(E_SL, kq);
+              a0[u] = W(D3_FMAX, kq); a1[u] = W(D3_F, kn); a2[u] = W(D3_SU, kn); a3[u] = ST(dp, kq); a4[u] = W(D3_H, kq);
+              a5[u] = W(D3_R, kq); a6[u] = W(D3_T, kq); a7[u] = W(D3_SL, kq);
             }
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               k = k0 + u;
               if (k <= kmax - 1) {
                 const double fmx = a0[u];
-                if (remfmx) { W(E_GTD, k) = 0.; W(E_FT, k) = fmx; }
+                if (remfmx) { W(D3_GTD, k) = 0.; W(D3_FT, k) = fmx; }
                 else {
                   const double fp = k + 1 <= kmax - 1 ? a1[u] : 0.;
                   const double suip = k + 1 <= kmax - 1 ? 1. / a2[u] : sui_b;
@@ -315,12 +310,12 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
                   flux_solution(q, a5[u], a6[u], f0, dfdg);
                   if (f0 >= fmx) { f0 = fmx; dfdg = 0.; if (k > kfmaxu) remfmx = true; }
                   const double g = ctd * bitd;
-                  W(E_GTD, k) = g;
+                  W(D3_GTD, k) = g;
                   atd = -dfdg * slim;
                   ctd = -dfdg * suip;
                   bitd = 1. / (1. - atd * g);
                   fnew_m = (f0 - atd * (fnew_m - f0m) + ctd * fp) * bitd;
-                  W(E_FT, k) = fnew_m;
+                  W(D3_FT, k) = fnew_m;
                   f0m = f0;
                   slim = 1. / a7[u];
                 }
@@ -333,7 +328,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               const int kq = CLAMPK(k0 - u, kfpl, kmax - 1);
-              a0[u] = W(E_FMAX, kq); a1[u] = W(E_FT, kq); a2[u] = W(E_F, kq); a3[u] = W(E_GTD, kq);
+              a0[u] = W(D3_FMAX, kq); a1[u] = W(D3_FT, kq); a2[u] = W(D3_F, kq); a3[u] = W(D3_GTD, kq);
             }
 #pragma unroll
             for (int u = 0; u < DU; u++) {
@@ -341,7 +336,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
               if (k >= kfpl) {
                 const double fk = fmin2(a0[u], a1[u] - gtd_p * fnew_p);
                 maxdf = fmax2(maxdf, fabs(fk - a2[u]));
-                W(E_F, k) = fk;
+                W(D3_F, k) = fk;
                 fnew_p = fk;
                 gtd_p = a3[u];
               }
@@ -354,15 +349,15 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               const int kq = CLAMPK(k0 - u, kfpl, kmax - 1), km1 = CLAMPK(kq - 1, kfpl, kmax - 1);
-              a0[u] = W(E_FMAX, kq); a1[u] = W(E_F, km1); a2[u] = W(E_SL, km1); a3[u] = ST(dp, kq); a4[u] = W(E_H, kq);
-              a5[u] = W(E_R, kq); a6[u] = W(E_T, kq); a7[u] = W(E_SU, kq);
+              a0[u] = W(D3_FMAX, kq); a1[u] = W(D3_F, km1); a2[u] = W(D3_SL, km1); a3[u] = ST(dp, kq); a4[u] = W(D3_H, kq);
+              a5[u] = W(D3_R, kq); a6[u] = W(D3_T, kq); a7[u] = W(D3_SU, kq);
             }
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               k = k0 - u;
               if (k >= kfpl) {
                 const double fmx = a0[u];
-                if (remfmx) { W(E_GTD, k) = 0.; W(E_FT, k) = fmx; }
+                if (remfmx) { W(D3_GTD, k) = 0.; W(D3_FT, k) = fmx; }
                 else {
                   const double fm = k - 1 >= kfpl ? a1[u] : 0.;
                   const double slim = k - 1 >= kfpl ? 1. / a2[u] : 1.;
@@ -371,12 +366,12 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
                   flux_solution(q, a5[u], a6[u], f0, dfdg);
                   if (f0 >= fmx) { f0 = fmx; dfdg = 0.; if (k <= kfmaxu) remfmx = true; }
                   const double g = atd * bitd;
-                  W(E_GTD, k) = g;
+                  W(D3_GTD, k) = g;
                   atd = -dfdg * slim;
                   ctd = -dfdg * suip;
                   bitd = 1. / (1. - ctd * g);
                   fnew_p = (f0 + atd * fm - ctd * (fnew_p - f0p)) * bitd;
-                  W(E_FT, k) = fnew_p;
+                  W(D3_FT, k) = fnew_p;
                   f0p = f0;
                   suip = 1. / a7[u];
                 }
@@ -389,7 +384,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
             for (int u = 0; u < DU; u++) {
               const int kq = CLAMPK(k0 + u, kfpl, kmax - 1);
-              a0[u] = W(E_FMAX, kq); a1[u] = W(E_FT, kq); a2[u] = W(E_F, kq); a3[u] = W(E_GTD, kq);
+              a0[u] = W(D3_FMAX, kq); a1[u] = W(D3_FT, kq); a2[u] = W(D3_F, kq); a3[u] = W(D3_GTD, kq);
             }
 #pragma unroll
             for (int u = 0; u < DU; u++) {
@@ -397,7 +392,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
               if (k <= kmax - 1) {
                 const double fk = fmin2(a0[u], a1[u] - gtd_m * fnew_m);
                 maxdf = fmax2(maxdf, fabs(fk - a2[u]));
-                W(E_F, k) = fk;
+                W(D3_F, k) = fk;
                 fnew_m = fk;
                 gtd_m = a3[u];
               }
@@ -415,7 +410,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 #pragma unroll
         for (int u = 0; u < DU; u++) {
           const int kq = CLAMPK(k0 + u, kfpl, kmax - 1);
-          a0[u] = W(E_F, kq); a1[u] = W(E_FCU, kq); a2[u] = W(E_SU, kq); a3[u] = W(E_FCL, kq); a4[u] = W(E_SL, kq);
+          a0[u] = W(D3_F, kq); a1[u] = W(D3_FCU, kq); a2[u] = W(D3_SU, kq); a3[u] = W(D3_FCL, kq); a4[u] = W(D3_SL, kq);
         }
 #pragma unroll
         for (int u = 0; u < DU; u++) {
@@ -465,13 +460,13 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
         else if (pos == kmin + 1) { dk = d2; fu = fpl0; fl = fpl1; }
         else { dk = b0[u]; fu = fu_next; fl = b1[u]; }
         g = ctd * bitd;
-        W(E_GTD, pos) = g;
+        W(D3_GTD, pos) = g;
         const double q = 1. / (dk + fu + fl);
         const double atd = -fu * q;
         ctd = -fl * q;
         const double dtd = dk * q;
         bitd = 1. / (1. - atd * g);
-        if (more_tracers) { W(E_R, pos) = dtd; W(E_T, pos) = atd; W(E_F, pos) = bitd; }   // the solve's slots are free by now
+        if (more_tracers) { W(D3_R, pos) = dtd; W(D3_T, pos) = atd; W(D3_F, pos) = bitd; }   // the solve's slots are free by now
         s_prev = (dtd * b3[u] - atd * s_prev) * bitd;
         t_prev = (dtd * b4[u] - atd * t_prev) * bitd;
         ST(saln, lay) = s_prev;
@@ -500,7 +495,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
        for (int u = 0; u < DU; u++) {
          const int pq = CLAMPK(p0 - u, kmin, kmax - 1);
          const int lq = pq == kmin ? 1 : (pq == kmin + 1 ? 2 : pq);
-         b0[u] = W(E_GTD, pq); b3[u] = ST(saln, lq); b4[u] = ST(temp, lq);
+         b0[u] = W(D3_GTD, pq); b3[u] = ST(saln, lq); b4[u] = ST(temp, lq);
 #pragma unroll
          for (int nt = 0; nt < MAXTR; nt++) bt[nt][u] = nt < ntr ? TRC(nt, lq) : 0.;
        }
@@ -527,7 +522,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
         for (int b = 0; b < MAXTR; b++) xp[b] = nt0 + b < ntr ? TRC(nt0 + b, km1) : 0.;
         for (int pos = kmin; pos <= kmax; pos++) {
           const int lay = pos == kmin ? 1 : (pos == kmin + 1 ? 2 : pos);
-          const double dtd = W(E_R, pos), atd = W(E_T, pos), bi = W(E_F, pos);
+          const double dtd = W(D3_R, pos), atd = W(D3_T, pos), bi = W(D3_F, pos);
           double xv[MAXTR];
 #pragma unroll
           for (int b = 0; b < MAXTR; b++) xv[b] = nt0 + b < ntr ? TRC(nt0 + b, lay) : 0.;
@@ -538,7 +533,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
         double gn = g;
         for (int pos = kmax - 1; pos >= kmin; pos--) {
           const int lay = pos == kmin ? 1 : (pos == kmin + 1 ? 2 : pos);
-          const double gp = W(E_GTD, pos);
+          const double gp = W(D3_GTD, pos);
           double xv[MAXTR];
 #pragma unroll
           for (int b = 0; b < MAXTR; b++) xv[b] = nt0 + b < ntr ? TRC(nt0 + b, lay) : 0.;
@@ -648,7 +643,7 @@ __global__ void __launch_bounds__(64, 1) k_diapfl_column3(const DevView *__restr
 
 int diapfl_column3_launch(blomgpu_ctx *c, int n, int nn, int *errflag) {
   const DevView &h = c->h;
-  if (E_NSLOT > h.nwk) return ctx_fail(c, "diapfl: work space too small");
+  if (D3_NSLOT > h.nwk) return ctx_fail(c, "diapfl: work space too small");
   const dim3 g = plane_grid(h, 1, 64);
   if ((size_t)g.x * (h.kk + 1) * WNS * 64 > (size_t)h.nwk * h.kk * h.nplane) return ctx_fail(c, "diapfl: work space too small");
   TimeScope tk(c, "k_diapfl_column3");

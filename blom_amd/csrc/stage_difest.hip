@@ -12,23 +12,9 @@
 #include "blomgpu_internal.h"
 #include "../../include/blomgpu.h"
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
-#define GRAV 9.806
-#define ALPHA0 1.e-3
-#define PI_BLOM 3.1415926536      // phy/mod_constants.F90:39
-
 __global__ void k_difest_ustar3(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const double us = V.f[F_ustar][c];
   V.f[F_ustar3][c] = us * us * us;
@@ -37,7 +23,7 @@ __global__ void k_difest_ustar3(const DevView *__restrict__ Vp) {
 // phy/mod_niw.F90:136-205: u-points i = 1..ii+1 -> util1, v-points j = 1..jj+1 -> util2
 __global__ void k_niw_uv(const DevView *__restrict__ Vp, int m, int mm) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   const size_t np = V.nplane, om = (size_t)(m - 1) * np;
   const int mmm = (m - 1) * 2;
   const double delt1 = V.P.delt1, dlt = V.P.dlt, ipfac = 2., cori10 = 2.5256e-5;
@@ -83,7 +69,7 @@ __global__ void k_niw_uv(const DevView *__restrict__ Vp, int m, int mm) {
 // :207-217
 __global__ void k_niw_idkedt(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   gci_t iu = V.m[I_iu], iv = V.m[I_iv];
   gcd_t u1 = V.f[F_util1], u2 = V.f[F_util2];

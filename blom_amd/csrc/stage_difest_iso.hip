@@ -31,24 +31,9 @@
 #include "atan2_libm.h"
 #include <cmath>
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
-#define GRAV 9.806
-#define ALPHA0 1.e-3
-#define PI_BLOM 3.1415926536      // phy/mod_constants.F90:40
 #define BU 8                      // levels whose loads the column loops keep in flight
-#define EPSILP 1.e-12
-#define ONEM 9806.
-#define DPBMIN 98.06              // onecm, :174
-#define DPTMIN 9806.              // `integer, parameter :: dptmin = onem`, :173
+#define DPBMIN ONECM              // :174
+#define DPTMIN ONEM               // `integer, parameter :: dptmin = onem`, :173
 #define DRHOMN 6.e-3
 #define NU0 1.e-5
 #define NUS0 5.e-3
@@ -85,9 +70,6 @@
 #define GLS_GHMIN (-.28)
 #define GLS_GHCRI .03
 #define LS_UNLMT_MIN 1.e-8
-
-// work-space slots (fields of kk levels)
-enum { W_DU2 = 0, W_DV2, W_BVFSQ, W_BVF, W_EGR, W_ANISOK, W_SM1, W_SM2, W_NUB, W_NSLOT };
 
 struct TkeC {            // initke's derived constants, phy/mod_tke.F90:133-160
   double sqrt2, cmu_fac1, cmu_fac2, cmu_fac3, tke_exp1, gls_exp1, gls_fac6, s0, s1, s2, s4, s5, s6, b0, b1, b2, b3, b4, b5, cmu0p3;
@@ -137,7 +119,7 @@ static TkeC tke_consts() {
 // ---- :366-390 ------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_dfi_kmax_kfil(const DevView *__restrict__ Vp, int n, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 0 || j > V.jj + 1 || i < 0 || i > V.ii + 1) return;
   gi_t kmax = V.m[I_dfe_kmax], kfil = V.m[I_dfe_kfil];
   if (!V.m[I_ip][c]) { kmax[c] = 0; return; }
@@ -168,7 +150,7 @@ __global__ __launch_bounds__(64) void k_dfi_kmax_kfil(const DevView *__restrict_
 // :392-411: kfil of the interior through util1 and its halo update back into kfil on 0..ii+1
 __global__ void k_dfi_kfil_util(const DevView *__restrict__ Vp, int back) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (!V.m[I_ip][c]) return;
   gi_t kfil = V.m[I_dfe_kfil];
   if (!back) {
@@ -180,12 +162,12 @@ __global__ void k_dfi_kfil_util(const DevView *__restrict__ Vp, int back) {
 // ---- :413-511: blockIdx.y = 0 the u-columns (j = 1..jj, i = 1..ii+1), 1 the v-columns (j = 1..jj+1, i = 1..ii) -------------
 __global__ __launch_bounds__(64) void k_dfi_uv2(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   const bool isv = by_ == 1;
   if (isv ? (j < 1 || j > V.jj + 1 || i < 1 || i > V.ii) : (j < 1 || j > V.jj || i < 1 || i > V.ii + 1)) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
-  gd_t d2 = WK(V, isv ? W_DV2 : W_DU2) + c;
+  gd_t d2 = WK(V, isv ? DF_DV2 : DF_DU2) + c;
   gi_t msk = V.m[isv ? I_mskv : I_msku] + c;
   if (!V.m[isv ? I_iv : I_iu][c]) {
     for (int k = 0; k < kk; k++) { d2[(size_t)k * np] = 0.; msk[(size_t)k * np] = 0; }
@@ -249,7 +231,7 @@ __global__ __launch_bounds__(64) void k_dfi_uv2(const DevView *__restrict__ Vp, 
 // a third of what its bytes allow.)
 __global__ void k_dfi_common(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kf = V.m[I_dfe_kfil][c], km = V.m[I_dfe_kmax][c];
   if (km - kf < 1) return;
@@ -275,7 +257,7 @@ __global__ void k_dfi_common(const DevView *__restrict__ Vp, int nn) {
     dr = tup;
   V.f[F_drhol][o] = dr;
   const int mu0 = V.m[I_msku][o], mu1 = V.m[I_msku][o + 1], mv0 = V.m[I_mskv][o], mv1 = V.m[I_mskv][o + ni];
-  gcd_t du2 = WK(V, W_DU2), dv2 = WK(V, W_DV2);
+  gcd_t du2 = WK(V, DF_DU2), dv2 = WK(V, DF_DV2);
   const double d2 = ((double)mu0 * du2[o] + (double)mu1 * du2[o + 1]) / (double)(mu0 + mu1 > 1 ? mu0 + mu1 : 1) +
                     ((double)mv0 * dv2[o] + (double)mv1 * dv2[o + ni]) / (double)(mv0 + mv1 > 1 ? mv0 + mv1 : 1);
   V.f[F_du2l][o] = d2;
@@ -291,18 +273,16 @@ __global__ void k_dfi_common(const DevView *__restrict__ Vp, int nn) {
 // from the old difdia, bvfbot, and exp(p(k)/q) of every interface once -- a level needs its own and the next one's), k_dfi_vert_c
 // behind (values copied down through the levels outside the range, the vertical averages dfddsu / dfddsl, the fill above kfil, the
 // near-inertial term, the surface interface).
-#define S2_BVFBOT 10
-#define S2_EXPB 11
 __global__ __launch_bounds__(64) void k_dfi_vert_a(const DevView *__restrict__ Vp, DfePar D, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kf = V.m[I_dfe_kfil][c], km = V.m[I_dfe_kmax][c];
   const size_t np = V.nplane;
   const int kk = V.kk;
   gcd_t p = V.f[F_p] + c, dp = V.f[F_dp] + c + (size_t)nn * np;
   gcd_t drhol = V.f[F_drhol] + c, du2l = V.f[F_du2l] + c, difdia = V.f[F_difdia] + c;
-  gd_t bvfsq = WK(V, W_BVFSQ) + c, bvf = WK(V, W_BVF) + c, ex = V.f[F_wkp1] + c;
+  gd_t bvfsq = WK(V, DF_BVFSQ) + c, bvf = WK(V, DF_BVF) + c, ex = V.f[F_wkp1] + c;
   gd_t Buoy = V.f[F_Buoy] + c, Shear2 = V.f[F_Shear2] + c, Prod = V.f[F_Prod] + c;
   const double pbot = p[(size_t)kk * np], q = V.f[F_tdmls][c];
   double bvfbot = 0., dps = 0.;
@@ -360,7 +340,7 @@ __global__ __launch_bounds__(64) void k_dfi_vert_a(const DevView *__restrict__ V
 // one thread per point and level: the level's diffusivity, :2729-2949
 __global__ void k_dfi_vert_b(const DevView *__restrict__ Vp, DfePar D, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int k = by_ + 1;
   const int kf = V.m[I_dfe_kfil][c], km = V.m[I_dfe_kmax][c];
@@ -371,9 +351,9 @@ __global__ void k_dfi_vert_b(const DevView *__restrict__ Vp, DfePar D, int nn) {
   const TkeC &T = D.T;
   gcd_t p = V.f[F_p];
   const double pk = p[o], pk1 = p[o + np], pbot = p[c + (size_t)kk * np];
-  const double dpk = V.f[F_dp][o + (size_t)nn * np], b2 = WK(V, W_BVFSQ)[o];
+  const double dpk = V.f[F_dp][o + (size_t)nn * np], b2 = WK(V, DF_BVFSQ)[o];
   double nub;
-  if (P.bdmtyp == 1) nub = P.bdmc1 / WK(V, W_BVF)[o];
+  if (P.bdmtyp == 1) nub = P.bdmc1 / WK(V, DF_BVF)[o];
   else if (P.bdmtyp == 2) nub = P.bdmc2;
   else nub = 0.;
   if (P.iwdflg == 1) nub = nub * (1. + (P.iwdfac - 1.) * V.f[F_ficem][c]);
@@ -414,7 +394,7 @@ __global__ void k_dfi_vert_b(const DevView *__restrict__ Vp, DfePar D, int nn) {
       else gl = (gl + delt1 * gprod) / (1. + delt1 * (gq - (gbuoy / gl)));
       gl = fmax2(gl, GLS_PSI_MIN);
       // q = .56**(.5 gls_n) cmu0**gls_p * tke**(gls_m + .5 gls_n) * bvf**(-gls_n): the last two exponents are 1; gls_n < 0: the larger one
-      gl = fmax2(gl, T.gls_qfac * tk * WK(V, W_BVF)[o]);
+      gl = fmax2(gl, T.gls_qfac * tk * WK(V, DF_BVF)[o]);
       tke_epsilon = T.cmu_fac2 * gl;
     }
     const double tke_q = tke_epsilon / tk;
@@ -483,12 +463,12 @@ __global__ void k_dfi_vert_b(const DevView *__restrict__ Vp, DfePar D, int nn) {
   } else
     nuls = 0.;
   V.f[F_difdia][o] = nub + nus + nut + nuls;
-  WK(V, W_NUB)[o] = nub;
+  WK(V, DF_NUB)[o] = nub;
 }
 
 __global__ __launch_bounds__(64) void k_dfi_vert_c(const DevView *__restrict__ Vp, DfePar D, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kf = V.m[I_dfe_kfil][c], km = V.m[I_dfe_kmax][c];
   const bool any = km - kf >= 1;
@@ -496,7 +476,7 @@ __global__ __launch_bounds__(64) void k_dfi_vert_c(const DevView *__restrict__ V
   const int kk = V.kk;
   gcd_t p = V.f[F_p] + c, dp = V.f[F_dp] + c + (size_t)nn * np;
   gd_t difdia = V.f[F_difdia] + c, Lsc = V.f[F_L_scale] + c;
-  gcd_t bvfsq = WK(V, W_BVFSQ) + c, nubw = WK(V, W_NUB) + c;
+  gcd_t bvfsq = WK(V, DF_BVFSQ) + c, nubw = WK(V, DF_NUB) + c;
   double *tke = nullptr, *gls = nullptr;
   if (D.use_tke) {
     tke = V.f[F_trc] + c + ((size_t)nn + (size_t)(D.itke - 1) * 2 * kk) * np;
@@ -637,7 +617,7 @@ __device__ __noinline__ double dfi_falign(double y, double x, double hangle) {
 // falign of every point and level, one thread each (rhsctp): the baroclinic velocities at the p-point (:2311-2316), the barotropic ones
 // (:2286-2295), sin / atan2.  In the column kernel the call cost 97 us a launch (117 -> 215 us: ~300 dependent instructions per level and
 // column); here the same arithmetic runs on 93 000 wavefronts -- the levels of a column's range only: evaluated at every level the kernel took
-// 115 us --, and the column kernel reads one more plane (work slot W_EGR).
+// 115 us --, and the column kernel reads one more plane (work slot DF_EGR).
 __global__ void k_dfi_falign(const DevView *__restrict__ Vp, int n, int nn) {
   const DevView &V = *Vp;
   unsigned bx_, by_;
@@ -661,13 +641,13 @@ __global__ void k_dfi_falign(const DevView *__restrict__ Vp, int n, int nn) {
   gcd_t u = V.f[F_u], v = V.f[F_v], dpu = V.f[F_dpu], dpv = V.f[F_dpv];
   const double ubc = (u[o] * dpu[o] + u[o + 1] * dpu[o + 1]) / fmax2(EPSILP, dpu[o] + dpu[o + 1]);
   const double vbc = (v[o] * dpv[o] + v[o + ni] * dpv[o + ni]) / fmax2(EPSILP, dpv[o] + dpv[o + ni]);
-  WK(V, W_EGR)[c + (size_t)(k - 1) * np] = dfi_falign(vbc + vbt, ubc + ubt, V.f[F_hangle][c]);
+  WK(V, DF_EGR)[c + (size_t)(k - 1) * np] = dfi_falign(vbc + vbt, ubc + ubt, V.f[F_hangle][c]);
 }
 
 // ---- difest_lateral_iso, :2040-2575 -------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(64) void k_dfi_lateral(const DevView *__restrict__ Vp, DfePar D, int n, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, on = (size_t)(n - 1) * np;
   const int kk = V.kk, ni = V.ni;
@@ -677,7 +657,7 @@ __global__ __launch_bounds__(64) void k_dfi_lateral(const DevView *__restrict__ 
   const bool any = km - kf >= 1;
   gcd_t p = V.f[F_p] + c, temp = V.f[F_temp] + c + (size_t)nn * np, saln = V.f[F_saln] + c + (size_t)nn * np;
   gd_t difint = V.f[F_difint] + c, difiso = V.f[F_difiso] + c;
-  gd_t anisok = WK(V, W_ANISOK) + c;
+  gd_t anisok = WK(V, DF_ANISOK) + c;
   gcd_t rig = V.f[F_rig] + c;
   gcd_t u = V.f[F_u] + c + (size_t)nn * np, v = V.f[F_v] + c + (size_t)nn * np;
   gcd_t dpu = V.f[F_dpu] + c + (size_t)nn * np, dpv = V.f[F_dpv] + c + (size_t)nn * np;
@@ -739,7 +719,7 @@ __global__ __launch_bounds__(64) void k_dfi_lateral(const DevView *__restrict__ 
   const bool vel = D.edanis;                                          // the baroclinic velocities at the p-point are needed for the anisotropy (:2308)
   // rhsctp (round 6): the topographic beta; falign of the level comes from k_dfi_falign's plane
   const double betatp = D.rhsctp ? V.f[F_betatp][c] : 0.;
-  gcd_t fal = WK(V, W_EGR) + c;
+  gcd_t fal = WK(V, DF_EGR) + c;
   double egrs = 0., dps_e = 0.;
   const int ka = kf > 2 ? kf : 2, kb = km < kk ? km : kk;            // the levels inside the range (when there are any)
   const double pkf_g = any ? PL(kf) + DPGRAV : 0.;
@@ -999,13 +979,13 @@ __global__ __launch_bounds__(64) void k_dfi_lateral(const DevView *__restrict__ 
 // ---- :2582-2607: lateral smoothing of difint, difiso (edfsmo); the unsmoothed fields lie in two work-space slots -------------------
 __global__ void k_dfi_smooth(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   const int mrg = 2;
   if (j < 1 - mrg || j > V.jj + mrg || i < 1 - mrg || i > V.ii + mrg || !V.m[I_ip][c]) return;
   const int k = by_, ni = V.ni;
   const size_t np = V.nplane, o = (size_t)k * np, okn = (size_t)(k + nn) * np;
   gci_t ip = V.m[I_ip];
-  gcd_t dp = V.f[F_dp] + okn, u1 = WK(V, W_SM1) + o, u2 = WK(V, W_SM2) + o;
+  gcd_t dp = V.f[F_dp] + okn, u1 = WK(V, DF_SM1) + o, u2 = WK(V, DF_SM2) + o;
   const double ws = .125 * (double)ip[c - ni] * fmin2(ONEM, dp[c - ni]) / ONEM;
   const double ww = .125 * (double)ip[c - 1] * fmin2(ONEM, dp[c - 1]) / ONEM;
   const double we = .125 * (double)ip[c + 1] * fmin2(ONEM, dp[c + 1]) / ONEM;
@@ -1032,7 +1012,7 @@ int st_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn) {
   if (h.P.vcoord_tag != 1) return ctx_fail(c, "difest_isobml is the isopycnic coordinate's (phy/mod_blom_step.F90:140)");
   if (h.P.itrtke >= 1 && (h.P.itrtke > h.ntr || h.P.itrgls < 1 || h.P.itrgls > h.ntr)) return ctx_fail(c, "difest: itrtke / itrgls outside 1..ntr");
   if (h.P.bdmldp && c->bdml_logc == 0.) return ctx_fail(c, " difest_vertical_iso: bdmldp needs the plane bdmlq and the option bdml_logc (the host's log)");
-  if (W_NSLOT > h.nwk) return ctx_fail(c, "difest: work space too small");
+  if (DF_NSLOT > h.nwk) return ctx_fail(c, "difest: work space too small");
   if (int rc = st_difest_isobml_pre(c, m, n, mm, nn)) return rc;                  // :750-790
   DfePar D;
   D.egc = c->egc; D.eggam = c->eggam; D.eglsmn = c->eglsmn; D.egmndf = c->egmndf; D.egmxdf = c->egmxdf; D.egidfq = c->egidfq;
@@ -1054,8 +1034,8 @@ int st_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn) {
     hipLaunchKernelGGL(k_dfi_uv2, g2, b64, 0, c->stream, c->d, nn);
     hipLaunchKernelGGL(k_dfi_common, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, nn);
     // difest_vertical_iso (vert_a/b/c: reads the common part's drhol, du2l, rig; writes difdia, the closure's tracers and fields, work
-    // slots W_BVFSQ, W_BVF, W_NUB, wkp1, two 2-D slots) and difest_lateral_iso (falign, lateral: reads rig, msku/v, the state, cmnfld2's
-    // nnslpx/y; writes difint, difiso, difwgt, W_EGR, W_ANISOK, W_SM1/2) share no array one of them writes: inside blomgpu_step (phys_dag)
+    // slots DF_BVFSQ, DF_BVF, DF_NUB, wkp1, two 2-D slots) and difest_lateral_iso (falign, lateral: reads rig, msku/v, the state, cmnfld2's
+    // nnslpx/y; writes difint, difiso, difwgt, DF_EGR, DF_ANISOK, DF_SM1/2) share no array one of them writes: inside blomgpu_step (phys_dag)
     // the lateral part runs on the second stream -- behind cmnfld2's kernels if they are there -- beside the vertical chain
     const bool aside = ctx_overlap_on(c) && (c->phys_dag & 1) && !c->tiling.multi();
     hipStream_t sl = c->stream;
@@ -1080,8 +1060,8 @@ int st_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn) {
     if (int rc = st_xctilr(c, h.f[F_difint], 1, h.kk, mrgint + 1, mrgint + 1, 1)) return rc;
     if (int rc = st_xctilr(c, h.f[F_difiso], 1, h.kk, mrgiso + 1, mrgiso + 1, 1)) return rc;
     const size_t bytes = sizeof(double) * (size_t)h.kk * h.nplane;
-    HIPCHK(c, hipMemcpyAsync(WK(h, W_SM1), h.f[F_difint], bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(WK(h, W_SM2), h.f[F_difiso], bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(WK(h, DF_SM1), h.f[F_difint], bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(WK(h, DF_SM2), h.f[F_difiso], bytes, hipMemcpyDeviceToDevice, c->stream));
     hipLaunchKernelGGL(k_dfi_smooth, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, nn);
     HIPCHK(c, hipGetLastError());
   } else {

@@ -30,10 +30,6 @@
 #define DT_LN (DT_LW * (DT_TH + 2))
 #define DT_NT (DT_TW * DT_TH)
 #define DT_TB 4                      // tracers per batch
-// work-space slots shared with pbcor's tile kernel (stage_pbcor_tile.hip)
-#define N_S 1
-#define N_T 2
-#define N_TR(nt) (3 + (nt))
 
 #define MP(m) ((m) & 1)
 #define MU(m) (((m) >> 1) & 1)

@@ -14,30 +14,14 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define GRAV 9.806
-#define RHO0 1.e3
-#define EPSILP 1.e-12
-
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
-// work-space slots per component: mfl needs kk+1 levels and borrows the first level of the next slot
-enum { G_MFL = 0, G_SPARE, G_DLM, G_DLP, G_NSLOT };
-
 __global__ void k_eddtra_gm(const DevView *__restrict__ Vp, int n, int mm, int nn, int *__restrict__ errflag) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const bool isv = by_ == 1;
   if (!(isv ? V.m[I_iv][c] : V.m[I_iu][c])) return;
   const size_t np = V.nplane, xb = c, xa = isv ? c - V.ni : c - 1;
-  const int kk = V.kk, sb = isv ? G_NSLOT : 0;
+  const int kk = V.kk, sb = isv ? ED_NSLOT : 0;
   const double ffac = .0625, fface = .99 * ffac, eps = 1.e-14, delt1 = V.P.delt1;
   gd_t mf = (isv ? V.f[F_vmfltd] : V.f[F_umfltd]) + (size_t)mm * np;
   gcd_t nslp = isv ? V.f[F_nslpy] : V.f[F_nslpx], dpz = (isv ? V.f[F_dpv] : V.f[F_dpu]) + (size_t)nn * np;
@@ -265,7 +249,7 @@ __global__ void k_eddtra_gm(const DevView *__restrict__ Vp, int n, int mm, int n
 // interface diffusion, :152-226
 __global__ void k_eddtra_intdif(const DevView *__restrict__ Vp, int mm, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const int k = by_ + 1, kk = V.kk, ni = V.ni;
   const size_t np = V.nplane;
@@ -302,7 +286,7 @@ __global__ void k_eddtra_intdif(const DevView *__restrict__ Vp, int mm, int nn) 
 // heat and salt components, :1837-1857
 __global__ void k_eddtra_ts(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t np = V.nplane, o = c + (size_t)(by_ + mm) * np;
   gcd_t temp = V.f[F_temp], saln = V.f[F_saln];
@@ -322,7 +306,7 @@ int st_eddtra(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   const DevView &h = c->h;
   if (h.P.vcoord_tag != 1) return st_eddtra_ale(c, m, n, mm, nn, k1m, k1n);           // :1859-1901 (stage_eddtra_ale.hip)
   if (c->mlrmth == 2) return ctx_fail(c, " init_eddtra: mlrmth = bod23 is unsupported with vcoord = 'isopyc_bulkml'!");   // :1787-1795
-  if (h.nwk < 2 * G_NSLOT) return ctx_fail(c, "eddtra: device work space too small");
+  if (h.nwk < 2 * ED_NSLOT) return ctx_fail(c, "eddtra: device work space too small");
   if (int rc = ctx_err_words(c)) return rc;
   int *errflag = c->err_dev + 1;
   {

@@ -22,21 +22,7 @@
 #include "eos.h"
 #include "pow_libm.h"
 
-#define GRAV 9.806
-#define RHO0 1.e3
-#define ALPHA0 1.e-3
-#define ONEM 9806.
-#define EPSILP 1.e-12
 #define DBCL82 .0003          /* phy/mod_cmnfld.F90:48 */
-
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
 
 struct EdaPar {
   int mlrmth;
@@ -51,7 +37,7 @@ __device__ inline void rmeanfilt(double &filtered, double signal, double wg, dou
 // :1050-1123 (mlrmth = 'fox08' or 'bod23')
 __global__ void k_eda_mixed_layer(const DevView *__restrict__ Vp, int nn, EdaPar Q) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int kk = V.kk;
@@ -96,7 +82,6 @@ __global__ void k_eda_mixed_layer(const DevView *__restrict__ Vp, int nn, EdaPar
   V.f[F_util1][c] = eos::sig0(tmldp * dpmli, smldp * dpmli);
 }
 
-enum { E_PUV = 0, E_GM, E_SM, E_MFL, E_DLM, E_DLP, E_NARR };
 #define EU 4        /* levels whose loads a pass keeps in flight */
 
 // :1197-1738.  The reference's ten loops over a column are three passes here, each statement as it stands:
@@ -109,7 +94,7 @@ enum { E_PUV = 0, E_GM, E_SM, E_MFL, E_DLM, E_DLP, E_NARR };
 // What a pass reads at the next EU levels is loaded before the current ones are worked on.
 __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int nn, EdaPar Q, int *__restrict__ errflag) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const bool isv = by_ == 1;
   if (!(isv ? V.m[I_iv][c] : V.m[I_iu][c])) return;
@@ -123,8 +108,8 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
   gcd_t hmlb = V.f[F_hml_tfbnd], scp2 = V.f[F_scp2];
 #define AT(a, x, k) (a)[(x) + (size_t)((k)-1) * np]
 #define CLK(k, lo, hi) ((k) < (lo) ? (lo) : ((k) > (hi) ? (hi) : (k)))
-  gd_t __restrict__ const wb = global_ptr(V.wk) + ((size_t)(by_ * gridDim.x + bx_) * (kk + 2) * E_NARR) * 64 + threadIdx.x;
-#define W(a, k) wb[((size_t)((k)-1) * E_NARR + (a)) * 64]
+  gd_t __restrict__ const wb = global_ptr(V.wk) + ((size_t)(by_ * gridDim.x + bx_) * (kk + 2) * EA_NARR) * 64 + threadIdx.x;
+#define W(a, k) wb[((size_t)((k)-1) * EA_NARR + (a)) * 64]
   const double mfleps = eps * EPSILP * (isv ? V.f[F_scv2] : V.f[F_scu2])[c];           // :1216
   const double et2mf = -GRAV * RHO0 * delt1 * (isv ? V.f[F_scvx] : V.f[F_scuy])[c];    // :1219
   const double pt = fmax2(AT(p, xa, 1), AT(p, xb, 1));                                 // ptu / ptv, :1182-1194
@@ -134,7 +119,7 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
   int kmax = 1, ka = kk + 2;                   // ka: first interface k >= 2 with puv(k) > puv(1) + hml*onem
   {
     double a = pt;
-    W(E_PUV, 1) = a;
+    W(EA_PUV, 1) = a;
     for (int k0 = 1; k0 <= kk; k0 += EU) {
       double a0[EU], a1[EU], a2[EU];
 #pragma unroll
@@ -145,13 +130,13 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
         if (k > kk) break;
         AT(mfgm, xb, k) = 0.; AT(mfsm, xb, k) = 0.;                                    // :1209-1213
         a = a + a0[u];
-        W(E_PUV, k + 1) = a;
+        W(EA_PUV, k + 1) = a;
         if (a1[u] > EPSILP || a2[u] > EPSILP) kmax = k;
         if (a > pml_a && ka > k + 1) ka = k + 1;
       }
     }
   }
-  const double pml = fmin2(pml_a, W(E_PUV, kmax + 1));                                 // :1236
+  const double pml = fmin2(pml_a, W(EA_PUV, kmax + 1));                                 // :1236
   const double dpmli = 1. / (pml - puv1);                                              // :1240
   const int kml = ka <= kmax ? ka : kmax + 1;                                          // :1244-1251
   // the submesoscale transport of the column (upsilon), :1125-1176 (bod23, fox08) or zero (:1030-1044)
@@ -190,7 +175,7 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
         const int kq = CLK(k0 + u, 2, kk);                   // difint(k-1), difint(k), nslp(k): read for kml <= k <= kmax only
         d0[u] = AT(difint, xa, kq - 1); d1[u] = AT(difint, xb, kq - 1); d2[u] = AT(difint, xa, kq); d3[u] = AT(difint, xb, kq);
         sl[u] = AT(nslp, xb, kq);
-        pu[u] = W(E_PUV, CLK(k0 + u, 1, kk + 1));
+        pu[u] = W(EA_PUV, CLK(k0 + u, 1, kk + 1));
         const int kp = CLK(k0 + u, 1, kk);                   // p(k+1) of the two columns: read for k <= kmax only
         a0[u] = AT(p, xa, kp + 1); a1[u] = AT(p, xb, kp + 1);
       }
@@ -209,11 +194,11 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
           gm = k <= kmax ? gm_below(k, d0[u], d1[u], d2[u], d3[u], sl[u]) : 0.;        // :1255-1260
           sm = 0.;                                                                     // :1278-1280
         }
-        W(E_GM, k) = gm; W(E_SM, k) = sm;
-        W(E_MFL, k) = gm + sm;                                                         // :1288-1290
+        W(EA_GM, k) = gm; W(EA_SM, k) = sm;
+        W(EA_MFL, k) = gm + sm;                                                         // :1288-1290
         if (k <= kmax) {                                                               // :1296-1301
-          W(E_DLM, k) = fmax2(0., fmin2(a0[u], pb) - fmax2(pa_k, pt));
-          W(E_DLP, k) = fmax2(0., fmin2(a1[u], pb) - fmax2(pb_k, pt));
+          W(EA_DLM, k) = fmax2(0., fmin2(a0[u], pb) - fmax2(pa_k, pt));
+          W(EA_DLP, k) = fmax2(0., fmin2(a1[u], pb) - fmax2(pb_k, pt));
           pa_k = a0[u]; pb_k = a1[u];
         }
       }
@@ -231,14 +216,14 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
     // a register, the far interface and the two thicknesses of EU steps are loaded ahead (no step writes what a later step's
     // look-ahead reads)
     const bool up = kdir > 0;
-    double carry = up ? W(E_MFL, 1) : W(E_MFL, kmax + 1);
+    double carry = up ? W(EA_MFL, 1) : W(EA_MFL, kmax + 1);
     for (int s0 = 0; s0 <= kmax - 1; s0 += EU) {
       double a0[EU], a1[EU], a2[EU];
 #pragma unroll
       for (int u = 0; u < EU; u++) {
         const int st = s0 + u <= kmax - 1 ? s0 + u : kmax - 1;
         const int kq = up ? 1 + st : kmax - st;
-        a0[u] = up ? W(E_MFL, kq + 1) : W(E_MFL, kq); a1[u] = W(E_DLM, kq); a2[u] = W(E_DLP, kq);
+        a0[u] = up ? W(EA_MFL, kq + 1) : W(EA_MFL, kq); a1[u] = W(EA_DLM, kq); a2[u] = W(EA_DLP, kq);
       }
 #pragma unroll
       for (int u = 0; u < EU; u++) {
@@ -256,7 +241,7 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
               if (hi < .5 * q) lo = hi - q;
               else { lo = -.5 * q; hi = -lo; }
             }
-            W(E_MFL, k) = lo; W(E_MFL, k + 1) = hi;
+            W(EA_MFL, k) = lo; W(EA_MFL, k + 1) = hi;
             changed = true;
           } else if (hi - lo < -ffac * fmax2(EPSILP, dq) * scp2b) {
             const double q = fface * dq * scp2b;
@@ -267,7 +252,7 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
               if (hi > -.5 * q) lo = hi + q;
               else { lo = .5 * q; hi = -lo; }
             }
-            W(E_MFL, k) = lo; W(E_MFL, k + 1) = hi;
+            W(EA_MFL, k) = lo; W(EA_MFL, k + 1) = hi;
             changed = true;
           }
         }
@@ -283,8 +268,8 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
 #pragma unroll
       for (int u = 0; u < EU; u++) {
         const int kq = CLK(k0 + u, 1, kmax + 1), kl = CLK(k0 + u - 1, 1, kmax);
-        am[u] = W(E_MFL, kq); ag[u] = W(E_GM, kq); as[u] = W(E_SM, kq);
-        a1[u] = W(E_DLM, kl); a2[u] = W(E_DLP, kl);                 // of the layer above interface k
+        am[u] = W(EA_MFL, kq); ag[u] = W(EA_GM, kq); as[u] = W(EA_SM, kq);
+        a1[u] = W(EA_DLM, kl); a2[u] = W(EA_DLP, kl);                 // of the layer above interface k
       }
 #pragma unroll
       for (int u = 0; u < EU; u++) {
@@ -329,7 +314,7 @@ __global__ void k_eda_column(const DevView *__restrict__ Vp, int n, int mm, int 
 // heat and salt components, :1874-1901
 __global__ void k_eda_ts(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t np = V.nplane, o = c + (size_t)(by_ + mm) * np;
   gcd_t temp = V.f[F_temp], saln = V.f[F_saln];
@@ -357,7 +342,7 @@ int st_eddtra_ale(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n
   (void)m; (void)k1m; (void)k1n;
   const DevView &h = c->h;
   if (h.P.eitmth != 2) return ctx_fail(c, " eitmth_opt is unsupported for vcoord = 'cntiso_hybrid'!");      // :1865-1872
-  if (h.nwk < 2 * E_NARR + 3) return ctx_fail(c, "eddtra: device work space too small");
+  if (h.nwk < 2 * EA_NARR + 3) return ctx_fail(c, "eddtra: device work space too small");
   if (int rc = ctx_err_words(c)) return rc;
   int *errflag = c->err_dev + 1;
   EdaPar Q;

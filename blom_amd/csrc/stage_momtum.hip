@@ -11,24 +11,12 @@
 
 #include "momtum_common.h"
 
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
-#define S2_DRAG 3      // 2-D work plane
-#define S2_QUM 4       // four consecutive 2-D work planes: the barotropic part of utotm, vtotm, utotn, vtotn
-
 
 // pu(k+1) = pu(k) + dpu(k+off), same for pv; range lo..+hi (:322-338 with lo=-1,hi=2; :1252-1267 interior)
 // ring: only the points of the range that lie outside the tile's interior
 __global__ void k_mom_pupv(const DevView *__restrict__ Vp, int off, int lo, int hi, int ring) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < lo || j > V.jj + hi || i < lo || i > V.ii + hi) return;
   if (ring && j >= 1 && j <= V.jj && i >= 1 && i <= V.ii) return;
   const size_t np = V.nplane;
@@ -39,7 +27,7 @@ __global__ void k_mom_pupv(const DevView *__restrict__ Vp, int off, int lo, int 
 // p(k+1) = p(k) + dp(k+off) for j,i = lo..+hi
 __global__ void k_mom_pscan(const DevView *__restrict__ Vp, int off, int lo, int hi, int ring) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < lo || j > V.jj + hi || i < lo || i > V.ii + hi || !V.m[I_ip][c]) return;
   if (ring && j >= 1 && j <= V.jj && i >= 1 && i <= V.ii) return;
   const size_t np = V.nplane;
@@ -49,7 +37,7 @@ __global__ void k_mom_pscan(const DevView *__restrict__ Vp, int off, int lo, int
 // ---- :260-292 bottom drag ------------------------------------------------------------------------
 __global__ void k_mom_drag(const DevView *__restrict__ Vp, int n, int nn) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 0 || j > V.jj || i < 0 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, on = (size_t)(n - 1) * np, e = c + 1, nb = c + V.ni;
   const double thkbop = THKBOT * ONEM, tsfac = V.P.dlt / V.P.delt1;
@@ -82,7 +70,7 @@ __global__ void k_mom_drag(const DevView *__restrict__ Vp, int n, int nn) {
 // (u, v at time levels m, n) instead of once per layer and sweep inside the marches (a division each)
 __global__ void k_mom_qplanes(const DevView *__restrict__ Vp, int m, int n) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   (void)i; (void)j;
   const size_t np = V.nplane, om = (size_t)(m - 1) * np, on = (size_t)(n - 1) * np;
   const double tsfac = V.P.dlt / V.P.delt1;

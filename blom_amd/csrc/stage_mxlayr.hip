@@ -25,25 +25,7 @@
 #include "diapfl_common.h"
 #include "exp_libm.h"
 
-#define GRAV 9.806
-#define ALPHA0 1.e-3
-#define SPCIFH 3.99e3
-#define EPSILP 1.e-12
-#define ONEM 9806.
 #define TENCM 980.6
-#define ONECM 98.06
-#define ONEMM 9.806
-#define ONEMU 9.806e-3
-
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
 
 // namelist-type variables of mod_mxlayr, mod_eddtra, mod_niw, mod_swabs that the column kernel reads
 struct MxlPar {
@@ -54,7 +36,7 @@ struct MxlPar {
 
 namespace eos0 {
 using namespace eos;
-constexpr double alpha0 = 1.e-3;
+constexpr double alpha0 = ALPHA0;
 constexpr double ap110 = a11 - a21 / alpha0, ap120 = a12 - a22 / alpha0, ap130 = a13 - a23 / alpha0, ap140 = a14 - a24 / alpha0,
                  ap150 = a15 - a25 / alpha0, ap160 = a16 - a26 / alpha0;
 // dsigdt0 / dsigds0, phy/mod_eos.F90:263-282, :325-344 (surface reference pressure: coefficients :118-129)
@@ -89,7 +71,7 @@ __device__ inline double p_p_alpha(double p1, double p2, double th, double s) {
 // ---- :222-235 buoyancy of the mixed layer at the surface reference pressure -------------------------------------------
 __global__ void k_mxl_bg2_sig(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, o1 = c + (size_t)nn * np, o2 = o1 + np;
   const double d1 = V.f[F_dp][o1], d2 = V.f[F_dp][o2];
@@ -102,7 +84,7 @@ __global__ void k_mxl_bg2_sig(const DevView *__restrict__ Vp, int nn) {
 // ---- :237-256 its squared gradient at u-points (i = 1..ii+1) and v-points (j = 1..jj+1) --------------------------------
 __global__ void k_mxl_bg2_grad(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   gcd_t u1 = V.f[F_util1];
   if (j >= 1 && j <= V.jj && i >= 1 && i <= V.ii + 1 && V.m[I_iu][c]) {
     const double q = (u1[c] - u1[c - 1]) * V.f[F_scuxi][c];
@@ -117,7 +99,7 @@ __global__ void k_mxl_bg2_grad(const DevView *__restrict__ Vp) {
 // ---- :257-278 averaged onto the p-points ---------------------------------------------------------------------------------
 __global__ void k_mxl_bg2_sum(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   gci_t ip = V.m[I_ip];
   gcd_t u2 = V.f[F_util2], u3 = V.f[F_util3];
@@ -155,7 +137,7 @@ __device__ inline void tracers4(int ntr, L load, U use, int first = 0) {
 #define MAXTR_MXL 64     // tracer sums of a column: dynamically indexed (private memory), any tracer count up to this
 __global__ __launch_bounds__(64) void k_mxl_column(const DevView *__restrict__ Vp, MxlPar M, int n, int nn KPROF_ARGS) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kk = V.kk, ntr = V.ntr, ni = V.ni;
   const size_t np = V.nplane;
@@ -989,7 +971,7 @@ __global__ __launch_bounds__(64) void k_mxl_column(const DevView *__restrict__ V
 //      wavefronts instead of being walked one after the other by the column's one thread.
 __global__ __launch_bounds__(64) void k_mxl_clamp(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const int kk = V.kk;
   const size_t np = V.nplane;

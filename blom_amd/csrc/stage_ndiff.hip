@@ -29,10 +29,6 @@
 #include "eos.h"
 #include "stage_ndiff.h"
 
-#define ND_GRAV 9.806
-#define ND_ALPHA0 1.e-3
-#define ND_EPSILP 1.e-12
-#define ND_ONEMM 9.806
 #define ND_MVAL 1.e30
 #define ND_DSTSNP_FAC .01   // :41-44
 #define ND_RHO_EPS 1.e-5
@@ -135,7 +131,7 @@ __device__ void nd_face(const DevView &V, const NdArgs &A, size_t cm, size_t cp,
   ((.5 * (DTM(ism, ksm) + DTP(isp_, ksp))) * (TSP(isp_, ksp, 0) - TSM(ism, ksm, 0)) +                                        \
    (.5 * (DSM(ism, ksm) + DSP(isp_, ksp))) * (TSP(isp_, ksp, 1) - TSM(ism, ksm, 1)))
   const int ksmx_m = A.ksmx[cm], ksmx_p = A.ksmx[cp], kdmx_m = A.kdmx[cm], kdmx_p = A.kdmx[cp];
-  const double cnslp = ND_ALPHA0 * (isv ? V.f[F_scvyi][cp] : V.f[F_scuxi][cp]) / ND_GRAV;      // :1080, :1135
+  const double cnslp = ALPHA0 * (isv ? V.f[F_scvyi][cp] : V.f[F_scuxi][cp]) / GRAV;      // :1080, :1135
   unsigned long long stm[NWS], stp[NWS];                                   // stab_src_m, stab_src_p (kk <= 64 NWS)
   for (int q = 0; q < NWS; q++) stm[q] = stp[q] = 0ull;
 #define SWI(ks_) (NWS == 1 ? 0 : ((ks_)-1) >> 6)
@@ -275,14 +271,14 @@ __device__ void nd_face(const DevView &V, const NdArgs &A, size_t cm, size_t cp,
     drho_curr = DRHO_CUR();
     if (wm) {
       if (drho_prev - drho_curr > ND_RHO_EPS) {
-        if (is_m == 2 && psm - psm1 > ND_ONEMM) STM_SET(ks_m);
+        if (is_m == 2 && psm - psm1 > ONEMM) STM_SET(ks_m);
         mode = then_p ? 2 : 0;
       } else if (is_m == 1 && PBM(2, ks_m - 1)) {                // (a copy of mval leaves the entry unset)
         PNM_SET(1, ks_m, prevm2);
       }
     } else {
       if (drho_curr - drho_prev > ND_RHO_EPS) {
-        if (is_p == 2 && psp - psp1 > ND_ONEMM) STP_SET(ks_p);
+        if (is_p == 2 && psp - psp1 > ONEMM) STP_SET(ks_p);
         mode = 0;
       } else if (is_p == 1 && PBP(2, ks_p - 1)) {
         PNP_SET(1, ks_p, prevp2);
@@ -641,7 +637,7 @@ __device__ void nd_face(const DevView &V, const NdArgs &A, size_t cm, size_t cp,
             ks = ks + 1;
           }
           if (out) break;
-          const double q = (PNS(ks) - p_nslp_dst) / fmax2(PNS(ks) - PNS(ks - 1), ND_EPSILP);
+          const double q = (PNS(ks) - p_nslp_dst) / fmax2(PNS(ks) - PNS(ks - 1), EPSILP);
           NSXY(kd) = q * NSL(ks - 1) + (1. - q) * NSL(ks);
           kd = kd + 1;
           if (kd > kk) break;
@@ -829,7 +825,7 @@ __global__ __launch_bounds__(64) void k_ndiff_uvflx(const DevView *__restrict__ 
       const double tflx = tf[u], sflx = sf[u];
       if (!(tflx == tflx)) continue;
       const double p_ni_up = pup[u], p_ni_lo = plo[u];
-      const double dp_ni_i = 1. / fmax2(ND_EPSILP, p_ni_lo - p_ni_up);
+      const double dp_ni_i = 1. / fmax2(EPSILP, p_ni_lo - p_ni_up);
       while (kuv <= kk) {
         if (pk1 < p_ni_lo) {
           const double mlfrac = fmax2(0., pk1 - fmax2(p_ni_up, pk)) * dp_ni_i;

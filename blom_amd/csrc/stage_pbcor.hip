@@ -12,26 +12,13 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define EPSILP 1.e-12
 #define DPEPS1 1.e-5   // phy/mod_pbcor.F90:58
 #define DPEPS2 1.e-7   // phy/mod_pbcor.F90:59
-
-#define THREAD_IJ(V)                                                       \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_
-
-#define S2_PBUT 1
-#define S2_PBVT 2
 
 // from_remap: remap left the new dp in the work space (stage_remap_tile.hip, FOLD)
 __global__ void k_pbc_pscan(const DevView *__restrict__ Vp, int which, int offc, int from_remap) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 0 || j > V.jj + 1 || i < 0 || i > V.ii + 1 || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   gd_t dp = from_remap ? WK(V, R_DP(V.ntr)) : V.f[F_dp] + (size_t)offc * np, p = V.f[F_p];
@@ -59,7 +46,7 @@ __global__ void k_pbc_pscan(const DevView *__restrict__ Vp, int which, int offc,
 
 __global__ void k_pbc_total(const DevView *__restrict__ Vp, int which, int m, int n, int offf) {
   const DevView &V = *Vp;
-  THREAD_IJ(V);
+  THREAD_IJ_XCD(V);
   const size_t np = V.nplane;
   const double dlt = V.P.dlt;
   gcd_t pbot = V.f[F_p] + (size_t)V.kk * np;

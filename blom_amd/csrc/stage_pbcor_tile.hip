@@ -18,7 +18,6 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-#define EPSILP 1.e-12
 #define DPEPS1 1.e-5   // phy/mod_pbcor.F90:58
 #define DPEPS2 1.e-7   // phy/mod_pbcor.F90:59
 
@@ -27,15 +26,6 @@
 #define PT_LW (PT_TW + 2)
 #define PT_LN (PT_LW * (PT_TH + 2))
 #define PT_NT (PT_TW * PT_TH)
-
-// work-space slots of the new state
-#define N_DP 0
-#define N_S 1
-#define N_T 2
-#define N_TR(nt) (3 + (nt))
-// 2-D work planes written by k_pbc_total (stage_pbcor.hip)
-#define S2_PBUT 1
-#define S2_PBVT 2
 
 #define MP(m) ((m) & 1)
 #define MU(m) (((m) >> 1) & 1)

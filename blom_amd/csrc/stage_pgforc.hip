@@ -16,12 +16,6 @@
 #include "blomgpu_internal.h"
 #include "eos.h"
 
-int launch_p_dpu_dpv(blomgpu_ctx *c, int off, int with_pupv);
-
-#define EPSILP 1.e-12
-#define GRAV 9.806
-
-
 __global__ void k_pgf_copy_old2d(const DevView *__restrict__ Vp, int n) {
   const DevView &V = *Vp;
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -536,10 +530,7 @@ __global__ __launch_bounds__(128) void k_pgf_uv_next(const DevView *__restrict__
 }
 
 // ---- pgforc_dynamic_enthalpy, phy/mod_pgforc.F90:269-412 ---------------------------------------------
-// work-space slots of the layer potentials
-enum { DH_POT = 0, DH_POTPB, DH_A, DH_T, DH_ALPR, DH_NSLOT };
 #define P0_DYNH 0.           // phy/mod_pgforc.F90:49
-#define ONEMM_ 9.806
 
 // per p-column, j,i = 0..jj/ii: bottom-up potentials (:282-312) and the derivatives (:318-341)
 __global__ void k_pgf_dynh_col(const DevView *__restrict__ Vp, int nn) {
@@ -577,7 +568,7 @@ __global__ void k_pgf_dynh_col(const DevView *__restrict__ Vp, int nn) {
   for (int k = 1; k <= kk; k++) {
     const double tk = LV(temp, k), sk = LV(saln, k);
     double da = 0., dt = 0.;
-    if (!(LV(dp, k) < ONEMM_)) {
+    if (!(LV(dp, k) < ONEMM)) {
       double ts_t, ts_s;
       eos::dynh_derivatives(P0_DYNH, LV(p, k), LV(p, k + 1), tk, sk, ts_t, ts_s);
       da = ts_s / eos::dalpds(pref, tk, sk);
@@ -611,7 +602,7 @@ __global__ void k_pgf_dynh_uv(const DevView *__restrict__ Vp, int n, int nn) {
   for (int k = kk; k >= 1; k--) {
     const size_t o = (size_t)(k - 1) * np;
     double g = -(pot[c + o] - pot[mns + o]);
-    if (dp[mns + o] >= ONEMM_ && dp[c + o] >= ONEMM_)
+    if (dp[mns + o] >= ONEMM && dp[c + o] >= ONEMM)
       g = g + .5 * ((dt[mns + o] + dt[c + o]) * (temp[c + o] - temp[mns + o]) + (da[mns + o] + da[c + o]) * (ar[c + o] - ar[mns + o]));
     pgf[c + o] = g;
     const double dpk = dpz[c + o];

@@ -114,17 +114,17 @@ __device__ inline void add_contrib_t(const double *g, int ntr, int x, double pbf
   const double dpt = g[RT_G_DPT(ntr) * RT_GN + x];
   const double pup = g[RT_G_PUP(ntr) * RT_GN + x];
   const double dl = fmin2(dpt, fmax2(0., pbface - pup));
-  const double dx = g[G_DX * RT_GN + x], dy = g[G_DY * RT_GN + x];
+  const double dx = g[RG_DX * RT_GN + x], dy = g[RG_DY * RT_GN + x];
   const double fd = a * dl + ax * dx + ay * dy;
   A.fd = A.fd + fd;
   const double qx = ax * dl + axx * dx + axy * dy;
   const double qy = ay * dl + axy * dx + ayy * dy;
-  A.ft = A.ft + fd * g[G_TD * RT_GN + x] + qx * g[G_TX * RT_GN + x] + qy * g[G_TY * RT_GN + x];
-  A.fs = A.fs + fd * g[G_SD * RT_GN + x] + qx * g[G_SX * RT_GN + x] + qy * g[G_SY * RT_GN + x];
+  A.ft = A.ft + fd * g[RG_TD * RT_GN + x] + qx * g[RG_TX * RT_GN + x] + qy * g[RG_TY * RT_GN + x];
+  A.fs = A.fs + fd * g[RG_SD * RT_GN + x] + qx * g[RG_SX * RT_GN + x] + qy * g[RG_SY * RT_GN + x];
 #pragma unroll
   for (int nt = 0; nt < MAXTR; nt++)
     if (nt < ntr)
-      A.ftr[nt] = A.ftr[nt] + fd * g[G_TRD(nt) * RT_GN + x] + qx * g[G_TRX(nt) * RT_GN + x] + qy * g[G_TRY(nt) * RT_GN + x];
+      A.ftr[nt] = A.ftr[nt] + fd * g[RG_TRD(nt) * RT_GN + x] + qx * g[RG_TRX(nt) * RT_GN + x] + qy * g[RG_TRY(nt) * RT_GN + x];
   if (MORE) { rec[slot].fd = fd; rec[slot].qx = qx; rec[slot].qy = qy; rec[slot].x = x; }
 }
 
@@ -225,7 +225,7 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
     cav_q = V.f[F_cav][c + ok];
     s2_q = scp2[c];
     s2i_q = scp2i[c];
-    pm = WK2(V, 0)[c];
+    pm = WK2(V, S2_REMAP_PM)[c];
     gpoint = inplane && j >= -1 && j <= V.jj + 2 && i >= -1 && i <= V.ii + 2;
   }
   // (c) this thread's face: threads 0..255 the u-face, threads 256..511 the v-face of tile point t mod 256.
@@ -310,16 +310,16 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
       dx = 0.; dy = 0.; xd = 0.; yd = 0.;
     }
     if (MORE) { k_dxi = dxi; k_dyi = dyi; k_xd = xd; k_yd = yd; }
-    gv[G_DX] = dx;
-    gv[G_DY] = dy;
+    gv[RG_DX] = dx;
+    gv[RG_DY] = dy;
     gv[8 + 3 * MAXTR] = dpt;                     // stored at RT_G_DPT / RT_G_PUP
     gv[9 + 3 * MAXTR] = plo[sidx] - dpt;
-    limited_gradient_t(sc + 2 * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[G_TX], gv[G_TY], gv[G_TD]);
-    limited_gradient_t(sc + 3 * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[G_SX], gv[G_SY], gv[G_SD]);
+    limited_gradient_t(sc + 2 * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[RG_TX], gv[RG_TY], gv[RG_TD]);
+    limited_gradient_t(sc + 3 * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[RG_SX], gv[RG_SY], gv[RG_SD]);
 #pragma unroll
     for (int nt = 0; nt < MAXTR; nt++)
       if (nt < nadv)
-        limited_gradient_t(sc + (4 + nt) * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[G_TRX(nt)], gv[G_TRY(nt)], gv[G_TRD(nt)]);
+        limited_gradient_t(sc + (4 + nt) * RT_SN, nb, sidx, dxi, dyi, xd, yd, gv[RG_TRX(nt)], gv[RG_TRY(nt)], gv[RG_TRD(nt)]);
   }
   if (gthread && gx >= 1 && gy >= 1) {
     // corner velocities at the corner common to (x-1,y-1), (x,y-1), (x-1,y), (x,y), mod_remap.F90:623-659
@@ -461,17 +461,17 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
       }
     }
   }
-  // the flux planes of k_remap_update: W_FDU, W_FDV, W_FTU, W_FTV, .. alternate
+  // the flux planes of k_remap_update: RF_DU, RF_DV, RF_TU, RF_TV, .. alternate
   const int off = uface ? 0 : 1;
   if (!FOLD) {
     if (base && !lean) {
-      WK(V, W_FDU(ntr) + off)[fc + ok] = A.fd;
-      WK(V, W_FTU(ntr) + off)[fc + ok] = A.ft;
-      WK(V, W_FSU(ntr) + off)[fc + ok] = A.fs;
+      WK(V, RF_DU(ntr) + off)[fc + ok] = A.fd;
+      WK(V, RF_TU(ntr) + off)[fc + ok] = A.ft;
+      WK(V, RF_SU(ntr) + off)[fc + ok] = A.fs;
     }
 #pragma unroll
     for (int nt = 0; nt < MAXTR; nt++)
-      if (nt < nadv) WK(V, W_FTRU(ntr, L.idx[nt]) + off)[fc + ok] = A.ftr[nt];
+      if (nt < nadv) WK(V, RF_TRU(ntr, L.idx[nt]) + off)[fc + ok] = A.ftr[nt];
   }
   }
   // ---- FOLD: the update of the owned cells, mod_remap.F90:1468-1520 ------------------------------------------------------
@@ -555,7 +555,7 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
             for (int pz = 0; pz < 3; pz++)
               f = f + rec[pz].fd * bg[(3 * a + 2) * RT_GN + rec[pz].x] + rec[pz].qx * bg[(3 * a) * RT_GN + rec[pz].x] +
                   rec[pz].qy * bg[(3 * a + 1) * RT_GN + rec[pz].x];
-            WK(V, W_FTRU(ntr, L.idx[b0 + a]) + off2)[fc + ok] = f;
+            WK(V, RF_TRU(ntr, L.idx[b0 + a]) + off2)[fc + ok] = f;
           }
       }
       if (next && gthread) {
@@ -605,9 +605,9 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
         if (a < nb_) {
           double gxx = 0., gyy = 0., gdd = 0.;
           if (gpoint) limited_gradient_t(sc + a * RT_SN, nb, sidx, k_dxi, k_dyi, k_xd, k_yd, gxx, gyy, gdd);
-          gr[G_TRX(a) * RT_GN + q] = gxx;
-          gr[G_TRY(a) * RT_GN + q] = gyy;
-          gr[G_TRD(a) * RT_GN + q] = gdd;
+          gr[RG_TRX(a) * RT_GN + q] = gxx;
+          gr[RG_TRY(a) * RT_GN + q] = gyy;
+          gr[RG_TRD(a) * RT_GN + q] = gdd;
         }
     }
     __syncthreads();
@@ -623,8 +623,8 @@ __global__ void __launch_bounds__(RT_NT, 4) k_remap_tile(const DevView *__restri
           double f = 0.;
 #pragma unroll
           for (int pz = 0; pz < 3; pz++)
-            f = f + rec[pz].fd * gr[G_TRD(a) * RT_GN + rec[pz].x] + rec[pz].qx * gr[G_TRX(a) * RT_GN + rec[pz].x] +
-                rec[pz].qy * gr[G_TRY(a) * RT_GN + rec[pz].x];
+            f = f + rec[pz].fd * gr[RG_TRD(a) * RT_GN + rec[pz].x] + rec[pz].qx * gr[RG_TRX(a) * RT_GN + rec[pz].x] +
+                rec[pz].qy * gr[RG_TRY(a) * RT_GN + rec[pz].x];
           fl[a * RT_NT + t] = f;
         }
     }
@@ -692,7 +692,7 @@ int remap_tile_launch(blomgpu_ctx *c, int n, int mm, int nn, int tsel, bool fold
   const int ntx = (h.ni + stx - 1) / stx, nty = (h.nj + sty - 1) / sty;
   static_assert(RT_NSC(MAXTR) * RT_SN <= RT_NG(MAXTR) * RT_GN, "the scalars must fit under the gradient slots");
   if (h.ntr > 255) return ctx_fail(c, "remap: tracer indices are packed in 8 bits");
-  if (h.ntr > 0 && W_FTRV(h.ntr, h.ntr - 1) >= h.nwk) return ctx_fail(c, "remap: work space too small for this many tracers");
+  if (h.ntr > 0 && RF_TRV(h.ntr, h.ntr - 1) >= h.nwk) return ctx_fail(c, "remap: work space too small for this many tracers");
   // the advected tracers (TKE and its length scale are not advected unless use_TKEADV, mod_remap.F90:314-316)
   AdvList L;
   int nadv = 0;

@@ -6,20 +6,10 @@
 // per-column loop where a k-recurrence exists.  Roofline: HBM.
 #include "blomgpu_internal.h"
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
 // ---- init_fluxes, phy/mod_state.F90:352-372 ------------------------------------------------
 __global__ void k_init_fluxes(const DevView *__restrict__ Vp, int mm) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 0 || j > V.jj + 2 || i < 0 || i > V.ii + 2) return;
   const size_t o = c + (size_t)(by_ + mm) * V.nplane;
   if (V.m[I_iu][c]) { V.f[F_uflx][o] = 0.; V.f[F_utflx][o] = 0.; V.f[F_usflx][o] = 0.; }
@@ -64,7 +54,7 @@ int st_init_fluxes(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
 // ---- initms / tmsmt1, phy/mod_tmsmt.F90:161-277 ---------------------------------------------
 __global__ void k_tmsmt1(const DevView *__restrict__ Vp, int off, int is_initms) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const int k = by_;                         // 0-based layer
   const size_t ok = c + (size_t)k * V.nplane, okn = c + (size_t)(k + off) * V.nplane;
@@ -97,7 +87,7 @@ int st_initms(blomgpu_ctx *c, int mm) {
 //      mod_mxlayr.F90:1270-1280).  One thread per column, coalesced plane-by-plane. -----------
 __global__ void k_pscan(const DevView *__restrict__ Vp, int off, int lo, int hi_off) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < lo || j > V.jj + hi_off || i < lo || i > V.ii + hi_off || !V.m[I_ip][c]) return;
   column_scan(V.f[F_p][c], V.f[F_dp] + (size_t)off * V.nplane + c, V.f[F_p] + c, V.nplane, V.kk);
 }
@@ -151,7 +141,7 @@ __global__ __launch_bounds__(256) void k_pscan_lanes(const DevView *__restrict__
 // 4 = dpuold, dpvold at every point of the range (ale_regrid_remap, phy/mod_ale_regrid_remap.F90:1735-1762)
 __global__ __launch_bounds__(64) void k_dpudpv(const DevView *__restrict__ Vp, int off, int flags) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < -1 || j > V.jj + 2 || i < -1 || i > V.ii + 2) return;
   const int with_pupv = flags & 1;
   const bool old_too = ((flags & 2) && j >= 1 && j <= V.jj && i >= 1 && i <= V.ii) || (flags & 4);
@@ -232,19 +222,16 @@ int launch_pscan(blomgpu_ctx *c, int off, int lo, int hi_off) {
 // 2-D work planes, then the filter with one thread per point and layer.  As one column kernel the filter walked the
 // layers serially, one memory latency per layer: 0.28 ms on the channel grid and 0.23 ms on the three times smaller
 // tripolar grid alike.
-#define S2_PBFACO 0
-#define S2_PBFACN 1
-#define S2_PBFACM 9
-// dp_in_wk (inside blomgpu_step): pbcor2 left its new, not yet rescaled layer thicknesses of level m in the work space (slot 0,
+// dp_in_wk (inside blomgpu_step): pbcor2 left its new, not yet rescaled layer thicknesses of level m in the work space (slot N_DP,
 // stage_pbcor_tile.hip) and did not launch its column pass: the factor pb / p(kk+1) of that pass (phy/mod_pbcor.F90:696-726) is
 // formed here with the two others, and k_tmsmt2 applies it where it reads dp of level m
 __global__ __launch_bounds__(64) void k_tmsmt2_fac(const DevView *__restrict__ Vp, int m, int nn, int dp_in_wk) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   gcd_t dpo = V.f[F_dpold] + c + (size_t)nn * np, dpn = V.f[F_dp] + c + (size_t)nn * np;
-  gcd_t ndp = dp_in_wk ? WK(V, 0) + c : dpn;
+  gcd_t ndp = dp_in_wk ? WK(V, N_DP) + c : dpn;
   double pbfaco = 0., pbfacn = 0., psum = V.f[F_p][c];
   const int kk = V.kk;
   for (int k0 = 0; k0 < kk; k0 += COLUMN_U) {
@@ -271,33 +258,32 @@ __global__ __launch_bounds__(64) void k_tmsmt2_fac(const DevView *__restrict__ V
 // not launched (k_dpudpv does the same for dpuold, dpvold)
 __global__ void k_tmsmt2(const DevView *__restrict__ Vp, int mm, int nn, int from_wk, int ahead, int dp_in_wk) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const int k = by_;
-  const double epsilp = 1.e-12;
   const double pbfaco = WK2(V, S2_PBFACO)[c], pbfacn = WK2(V, S2_PBFACN)[c];
   const double wts1 = V.P.wts1, wts2 = V.P.wts2;
   const size_t okm = c + (size_t)(k + mm) * np, okn = c + (size_t)(k + nn) * np, ok = c + (size_t)k * np;
   double pold = fmax2(0., V.f[F_dpold][okn] * pbfaco);
-  double pmid = fmax2(0., dp_in_wk ? WK(V, 0)[ok] * WK2(V, S2_PBFACM)[c] : V.f[F_dp][okm]);
+  double pmid = fmax2(0., dp_in_wk ? WK(V, N_DP)[ok] * WK2(V, S2_PBFACM)[c] : V.f[F_dp][okm]);
   double pnew = fmax2(0., V.f[F_dp][okn] * pbfacn);
   const double dpm = wts1 * pmid + wts2 * (pold + pnew);
   V.f[F_dp][okm] = dpm;
-  pold = pold + epsilp;
-  pmid = pmid + epsilp;
-  pnew = pnew + epsilp;
-  const double tmid = from_wk ? WK(V, 2)[ok] : V.f[F_temp][okm], smid = from_wk ? WK(V, 1)[ok] : V.f[F_saln][okm];
-  const double tnew = (wts1 * pmid * tmid + wts2 * (pold * V.f[F_told][ok] + pnew * V.f[F_temp][okn])) / (dpm + epsilp);
-  const double snew = (wts1 * pmid * smid + wts2 * (pold * V.f[F_sold][ok] + pnew * V.f[F_saln][okn])) / (dpm + epsilp);
+  pold = pold + EPSILP;
+  pmid = pmid + EPSILP;
+  pnew = pnew + EPSILP;
+  const double tmid = from_wk ? WK(V, N_T)[ok] : V.f[F_temp][okm], smid = from_wk ? WK(V, N_S)[ok] : V.f[F_saln][okm];
+  const double tnew = (wts1 * pmid * tmid + wts2 * (pold * V.f[F_told][ok] + pnew * V.f[F_temp][okn])) / (dpm + EPSILP);
+  const double snew = (wts1 * pmid * smid + wts2 * (pold * V.f[F_sold][ok] + pnew * V.f[F_saln][okn])) / (dpm + EPSILP);
   V.f[F_temp][okm] = tnew;
   V.f[F_saln][okm] = snew;
   if (ahead) { V.f[F_dpold][okm] = dpm; V.f[F_told][ok] = tnew; V.f[F_sold][ok] = snew; }
   for (int nt = 0; nt < V.ntr; nt++) {
     gd_t tr = V.f[F_trc] + (size_t)nt * 2 * V.kk * np;
     gd_t tro = V.f[F_trcold] + (size_t)nt * V.kk * np;
-    const double xmid = from_wk ? WK(V, 3 + nt)[ok] : tr[okm];
-    const double xnew = (wts1 * pmid * xmid + wts2 * (pold * tro[ok] + pnew * tr[okn])) / (dpm + epsilp);
+    const double xmid = from_wk ? WK(V, N_TR(nt))[ok] : tr[okm];
+    const double xnew = (wts1 * pmid * xmid + wts2 * (pold * tro[ok] + pnew * tr[okn])) / (dpm + EPSILP);
     tr[okm] = xnew;
     if (ahead) tro[ok] = xnew;
   }
@@ -342,7 +328,7 @@ int st_mxlayr_tail(blomgpu_ctx *c, int nn, int k1n) {
 // ---- kfpla halo through util1, phy/mod_cmnfld_routines.F90:1176-1196 --------------------------
 __global__ void k_kfpla_util(const DevView *__restrict__ Vp, int n, int back) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (!V.m[I_ip][c]) return;
   gi_t kf = V.m[I_kfpla] + (size_t)(n - 1) * V.nplane;
   if (!back) {
@@ -363,7 +349,7 @@ int st_kfpla_halo(blomgpu_ctx *c, int n) {
 //      idlage/mod_idlage.F90:57-96: surface layer reset, deeper layers aged, all p-points incl. the halo ----
 __global__ void k_idlage_step(const DevView *__restrict__ Vp, int nn) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (!V.m[I_ip][c]) return;
   const int k = by_;
   const size_t np = V.nplane;
@@ -396,7 +382,7 @@ int st_updtrc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
 //      correction term of call 5 (:182-194) needs mod_forcing's salt_corr, which no stage here produces. ----
 __global__ void k_budget_columns(const DevView *__restrict__ Vp, int nn, int which) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const double scp2 = V.f[F_scp2][c];

@@ -17,22 +17,6 @@
 #include "pow_libm.h"
 #include <cmath>
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
-#define SPCIFH 3990.
-#define T0DEG 273.15
-#define EPSILT 1.e-11
-#define ONEM 9806.
-#define S2_VRTSFL 8      // 2-D work plane: the reference's local array vrtsfl
-
 struct ThermfPar {
   double trxday, srxday, trxdpt, srxdpt, trxlim, srxlim, xmi, sref, area;
   int l1mi, l2mi, l3mi, l4mi, l5mi;
@@ -52,7 +36,7 @@ __device__ inline double intp1d(double d1, double d2, double d3, double d4, doub
 
 __global__ void k_thermf_channel_flux(const DevView *__restrict__ Vp, ThermfPar T, int nn, int k1n) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, o1 = c + (size_t)nn * np, o2 = o1 + np, ok1 = c + (size_t)(k1n - 1) * np;
   const int kk = V.kk, ntr = V.ntr;
@@ -117,7 +101,7 @@ __global__ void k_thermf_channel_flux(const DevView *__restrict__ Vp, ThermfPar 
 // :275-343; sums[0] = totsfl, sums[1] = totwfl
 __global__ void k_thermf_channel_corr(const DevView *__restrict__ Vp, ThermfPar T, const double *__restrict__ sums) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const double sflxc = (-T.sref * sums[1] * 1.e-3 - sums[0]) / T.area;

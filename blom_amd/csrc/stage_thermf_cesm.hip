@@ -18,26 +18,6 @@
 #include "pow_libm.h"
 #include <cmath>
 
-#define PLANE_IJ(V)                                                        \
-  unsigned bx_, by_;                                                       \
-  xcd_block(bx_, by_);                                                     \
-  const int t_ = bx_ * blockDim.x + threadIdx.x;                           \
-  (void)by_;                                                               \
-  if (t_ >= (V).nplane) return;                                            \
-  const int i = t_ % (V).ni - (NBDY - 1), j = t_ / (V).ni - (NBDY - 1);    \
-  const size_t c = t_;                                                     \
-  (void)i; (void)j; (void)c
-
-// phy/mod_constants.F90:32-56
-#define GRAV 9.806
-#define SPCIFH 3990.
-#define T0DEG 273.15
-#define ALPHA0 1.e-3
-#define EPSILT 1.e-11
-#define ONEM 9806.
-#define G2KG 1.e-3
-#define KG2G 1.e3
-#define S2_VRTSFL 8      // 2-D work plane: the reference's local array vrtsfl (as in stage_thermf.hip)
 #define NLEV_RLX 48      // levels of tflxap sflxap tflxdi sflxdi (phy/mod_forcing.F90:95-100)
 
 struct GetfrcPar { double w1, w2; int l1, l2; };      // l1, l2: 0-based levels of the _da pairs
@@ -66,7 +46,7 @@ __device__ inline double intp5(gcd_t a, size_t np, int l1, int l2, int l3, int l
 
 __global__ void k_getfrc_cesm(const DevView *__restrict__ Vp, GetfrcPar G) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   const size_t o1 = c + (size_t)G.l1 * V.nplane, o2 = c + (size_t)G.l2 * V.nplane;
 #define GETFRC(dst, src) V.f[dst][c] = G.w1 * V.f[src][o1] + G.w2 * V.f[src][o2]
@@ -82,7 +62,7 @@ __global__ void k_getfrc_cesm(const DevView *__restrict__ Vp, GetfrcPar G) {
 
 __global__ void k_sfcstr_cesm(const DevView *__restrict__ Vp) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   if (V.m[I_iu][c]) V.f[F_taux][c] = V.f[F_ztx][c];
   if (V.m[I_iv][c]) V.f[F_tauy][c] = V.f[F_mty][c];
@@ -130,7 +110,7 @@ __device__ inline double rs_walk(gcd_t dp, gcd_t x, gd_t frac, size_t np, int kk
 
 __global__ void k_thermf_cesm_flux(const DevView *__restrict__ Vp, ThermfCesmPar T, int nn, int k1m, int k1n) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane, o1 = c + (size_t)nn * np, o2 = o1 + np, okm = c + (size_t)(k1m - 1) * np, okn = c + (size_t)(k1n - 1) * np;
   const int kk = V.kk, ntr = V.ntr;
@@ -253,7 +233,7 @@ __global__ void k_thermf_cesm_flux(const DevView *__restrict__ Vp, ThermfCesmPar
 // :343-410; sums[0] = the salt plane's sum, sums[1 .. ntr'] the tracers' in their order, sums[ntr'+1], sums[ntr'+2] = totsrp, totsrn
 __global__ void k_thermf_cesm_corr(const DevView *__restrict__ Vp, ThermfCesmPar T, const double *__restrict__ sums, int nq) {
   const DevView &V = *Vp;
-  PLANE_IJ(V);
+  THREAD_IJ_XCD(V);
   if (j < 1 || j > V.jj || i < 1 || i > V.ii || !V.m[I_ip][c]) return;
   const size_t np = V.nplane;
   const double sflxc = sums[0] / T.area;
@@ -362,10 +342,9 @@ int st_getfrc_cesm(blomgpu_ctx *c) {
   if (c->l1ci < 1 || c->l1ci > 2 || c->l2ci < 1 || c->l2ci > 2) return ctx_fail(c, "getfrc_cesm: l1ci and l2ci are 1 or 2");
   GetfrcPar G;
   G.w1 = 0.;
-  if (c->smtfrc) {                                                 // cesm/mod_cesm.F90:213-219 (pi of phy/mod_constants.F90:40)
+  if (c->smtfrc) {                                                 // cesm/mod_cesm.F90:213-219 (the reference's own pi)
     if (c->nstep_in_cpl < 1) return ctx_fail(c, "getfrc_cesm: nstep_in_cpl has not been set");
-    const double pi = 3.1415926536;
-    G.w1 = .5 * (1. + std::cos((double)((c->h.P.nstep - 1) % c->nstep_in_cpl + 1) * pi / (double)c->nstep_in_cpl));
+    G.w1 = .5 * (1. + std::cos((double)((c->h.P.nstep - 1) % c->nstep_in_cpl + 1) * PI_BLOM / (double)c->nstep_in_cpl));
   }
   G.w2 = 1. - G.w1;
   G.l1 = c->l1ci - 1;

@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Which arrays a kernel of blom_amd/csrc reads and writes, from its source text: the fields V.f[F_*], the integer fields V.m[I_*], the
-work-space slots WK(V, slot) / WK2(V, slot) (slot names resolved to numbers through the file's enums and #defines, so that slots of
-different stages compare).  An array counts as WRITTEN when it is bound to a mutable pointer (gd_t / gi_t) or stored through directly;
-every other mention is a read.  Used by tests/test_side_by_side_sets.py to check the pairs blomgpu_step runs side by side on its two
+work-space slots WK(V, slot) / WK2(V, slot) (slot names resolved to numbers through the enums and #defines of the file and of the
+headers it includes with "...", so that slots of different stages compare).  An array counts as WRITTEN when it is bound to a mutable
+pointer (gd_t / gi_t) or stored through directly; every other mention is a read.  Used by tests/test_side_by_side_sets.py to check the pairs blomgpu_step runs side by side on its two
 streams, and from the command line:  tools/kernel_rw_sets.py blom_amd/csrc/stage_x.hip k_a k_b ..."""
-import re, sys
+import os, re, sys
 
 TOK = re.compile(r"\b(F_\w+|I_\w+)\b|\bWK\(\s*\w+\s*,([^()]*)\)|\bWK2\(\s*\w+\s*,([^()]*)\)")
 
@@ -12,7 +12,7 @@ TOK = re.compile(r"\b(F_\w+|I_\w+)\b|\bWK\(\s*\w+\s*,([^()]*)\)|\bWK2\(\s*\w+\s*
 def constants(src):
     """names of enum members and integer #defines -> value"""
     val = {}
-    for m in re.finditer(r"#define\s+(\w+)\s+(\d+)\s*$", src, re.M):
+    for m in re.finditer(r"#define\s+(\w+)\s+(\d+)\s*(?://.*|/\*.*\*/\s*)?$", src, re.M):
         val[m.group(1)] = int(m.group(2))
     for m in re.finditer(r"enum\s*\w*\s*\{([^}]*)\}", src):
         nxt = 0
@@ -28,6 +28,21 @@ def constants(src):
             val[name] = nxt
             nxt += 1
     return val
+
+
+def with_includes(path, seen=None):
+    """the text of the headers `path` includes with "...", recursively and inside its own directory tree, then its own text"""
+    seen = set() if seen is None else seen
+    path = os.path.realpath(path)
+    if path in seen:
+        return ""
+    seen.add(path)
+    src, root, out = open(path).read(), os.path.dirname(path), ""
+    for m in re.finditer(r'^\s*#include\s+"([^"]+)"', src, re.M):
+        inc = os.path.realpath(os.path.join(root, m.group(1)))
+        if inc.startswith(root + os.sep) and os.path.exists(inc):
+            out += with_includes(inc, seen)
+    return out + src
 
 
 def bodies(src):
@@ -84,7 +99,7 @@ def _call_args(text, start):
 
 def rw_sets(path, kernel):
     src = open(path).read()
-    val = constants(src)
+    val = constants(with_includes(path))
     body = re.sub(r"//[^\n]*", "", bodies(src)[kernel])
     reads, writes = set(_names(body, val)), set()
     for stmt in body.split(";"):
