@@ -505,6 +505,8 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   // sequence on plain launches: correct, and a few per cent slower -- a caller that times steps wants to know)
   if (s == "graph_steps") { *v = c->graph_steps; return 0; }
   if (s == "graph_failures") { *v = c->graph_failures; return 0; }
+  // how many steps blomgpu_step has run without keeping the heat and salt flux diagnostics current (flux_diag: all but the last two of a call)
+  if (s == "flux_diag_steps_skipped") { *v = (double)c->flux_diag_skipped; return 0; }
   // thermf_cesm's correction of the virtual salt flux (cesm/mod_thermf_cesm.F90:342-343), from the sum the last thermf left on the device
   if (s == "thermf_cesm_launches") { *v = (double)c->cesm_launches; return 0; }      // (counted where they are issued, single tile)
   if (s == "sflxc") {
@@ -685,6 +687,12 @@ int blomgpu_diaacc(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
 }
 int blomgpu_dia_select(blomgpu_ctx *c, const char *names) { return dia_select(c, names); }
 int blomgpu_dia_alarm(blomgpu_ctx *c, int alarm) { return dia_alarm(c, alarm); }
+// on != 0: every step of a blomgpu_step call keeps the heat and salt flux diagnostics current, not only its last two
+int blomgpu_keep_flux_diagnostics(blomgpu_ctx *c, int on) {
+  if (!c) return ctx_fail(c, "blomgpu_keep_flux_diagnostics: null context");
+  c->keep_flux_diag = on != 0;
+  return 0;
+}
 int blomgpu_dia_nacc(blomgpu_ctx *c, int *nacc) { return dia_nacc(c, nacc); }
 int blomgpu_dia_get(blomgpu_ctx *c, const char *name, double *out) { return dia_get(c, name, out); }
 int blomgpu_dia_finalize(blomgpu_ctx *c) { return dia_finalize(c); }
@@ -1031,6 +1039,10 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
   if (int rc = dia_step_check(c)) return rc;
   if (cesm_on(c) && c->use_graph)
     return ctx_fail(c, "blomgpu_step: the coupled experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
+  // (the stage entries outside this call keep the flux diagnostics current, whichever way it returns)
+  struct FluxDiagBack { blomgpu_ctx *c; ~FluxDiagBack() { c->flux_diag = true; } } flux_diag_back{c};
+  // the row test walks the selection: once per call, the selection cannot change inside it
+  const bool flux_diag_lazy = !c->keep_flux_diag && c->h.P.vcoord_tag == 1 && !dia_reads_flux_diag(c);
   for (int it = 0; it < nsteps; it++) {
     const int ns = *nstep;
     const int m = ns % 2 + 1, n = (ns + 1) % 2 + 1;
@@ -1040,6 +1052,14 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     // (not while diavfl's group is selected: its dp(km) - dpold(km) needs the dpold the PREVIOUS step's tmsmt1 left, and the fold
     // would have tmsmt2 overwrite it in front of diaacc.  The cost of the launch it brings back: DESIGN 3.13)
     c->tmsmt1_ahead = !c->use_graph && !c->csdiag && it < nsteps - 1 && c->tmsmt_ahead && !dia_reads_dpold(c);
+    // The heat and salt flux diagnostics (blomgpu_internal.h: flux_diag) are kept current only by the steps that can leave something
+    // observable in them.  The caller sees them when the call has returned, on both time levels: level m of the last step is written in
+    // that step; its level n was written one step earlier (eddtra, remap, pbcor1, diffus under level m there) and by the last step's
+    // pbcor2.  Every older value is zeroed (k_init_fluxes_ring) or assigned (remap's tile kernel, eddtra, diffus' *flld) under the same
+    // constant masks before it could be seen.  So all but the last two steps skip, unless something reads the arrays every step:
+    // csdiag's checksums, a diaacc row -- or the launches are a captured graph's, the same in every step.  The hybrid-coordinate
+    // sequence writes these arrays inside fused kernels (eddtra_ale, ndiff) and keeps today's form.
+    c->flux_diag = !(flux_diag_lazy && !c->use_graph && !c->csdiag && it < nsteps - 2);
     // (the hybrid-coordinate sequence too: the engine's status of ale_regrid_remap stays on the device until the check below)
     bool graph = c->use_graph && !c->timing && !c->tiling.multi() && c->steps_warm >= 2;
     hipGraphExec_t &ge = c->step_graph[ns & 1];
@@ -1077,6 +1097,7 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     }
     if (graph) { HIPCHK(c, hipGraphLaunch(ge, c->stream)); c->graph_steps++; }
     else if (int rc = step_sequence(c, m, n, mm, nn, k1m, k1n)) { c->tmsmt1_done_ahead = false; return rc; }
+    if (!c->flux_diag) c->flux_diag_skipped++;
     dia_count(c);                                          // nacc_phy, phy/mod_dia.F90:1123-1125
     c->steps_done++;
     c->steps_warm++;

@@ -454,6 +454,13 @@ struct blomgpu_ctx {
   // these two live across TWO steps of one blomgpu_step call (tmsmt2 of a step does the next step's tmsmt1), so they are not part of
   // StepState: blomgpu_step sets tmsmt1_ahead per step, tmsmt2 sets tmsmt1_done_ahead, the next step_sequence consumes it
   bool tmsmt1_ahead = false, tmsmt1_done_ahead = false;
+  // The heat and salt flux diagnostics utflx usflx vtflx vsflx (as far as pbcor and diffus accumulate into them), u|v t|s fltd and
+  // u|v t|s flld have no reader inside a step: blomgpu_step clears flux_diag for the steps of a call that leave nothing observable in
+  // them (all but the last two: a caller sees both time levels once the call returns), and eddtra, diffus and the tile kernel of pbcor
+  // then skip what only keeps them current (flux_diag_on below).  Not part of StepState, which step_sequence resets; true outside
+  // blomgpu_step.  keep_flux_diag: blomgpu_keep_flux_diagnostics, the caller's off-switch.
+  bool flux_diag = true, keep_flux_diag = false;
+  long long flux_diag_skipped = 0;   // steps run with flux_diag false since the context was created (blomgpu_get_real "flux_diag_steps_skipped")
   hipGraphExec_t step_graph[2] = {nullptr, nullptr};
   int steps_done = 0;
   int steps_warm = 0;            // plain steps since the last option change (graph capture waits for 2: both time levels' buffers exist)
@@ -495,6 +502,8 @@ int ctx_side_fork(blomgpu_ctx *c, int ev);     // `side` waits for what is on th
 int ctx_side_done(blomgpu_ctx *c, int ev);     // marks the end of a section on `side` ...
 int ctx_side_join(blomgpu_ctx *c, int ev);     // ... and the context's stream waits for it
 bool ctx_overlap_on(const blomgpu_ctx *c);
+// whether this launch keeps the heat and salt flux diagnostics current: always when a stage is called on its own
+static inline bool flux_diag_on(const blomgpu_ctx *c) { return !c->seq.in_sequence || c->flux_diag; }
 
 int  ctx_fail(blomgpu_ctx *c, const std::string &msg);
 int  ctx_pack_masks(blomgpu_ctx *c);     // mpack = ip | iu << 1 | iv << 2 | iq << 3, after any upload of a mask
@@ -586,6 +595,7 @@ int dia_name_full(int index, char *buf, int cap, int *kind, int *grid);
 int dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
 bool dia_reads_mldl82(const blomgpu_ctx *);  // one of the four mldl82 names is selected: st_cmnfld1 forms the field under isopyc_bulkml too
 bool dia_reads_dpold(const blomgpu_ctx *);   // diavfl's group is selected: a step's tmsmt1 stays a launch of its own (api.hip, blomgpu_step)
+bool dia_reads_flux_diag(const blomgpu_ctx *);   // a selected row's source is one of the twelve heat / salt flux diagnostics: every step keeps them current
 double *dia_acc_span(const blomgpu_ctx *, size_t *n);   // the accumulators' planes, for halo updates inside diaacc (halo.hip, ctx_locate_ptr)
 int dia_set_sigdia(blomgpu_ctx *, const double *sigdia, int n);
 int dia_get_sigdia(blomgpu_ctx *, double *out, int cap, int *n);

@@ -883,6 +883,18 @@ void dia_free(blomgpu_ctx *c) {
 bool dia_active(const blomgpu_ctx *c) { return c->dia != nullptr; }
 // diavfl reads dpold(km) as the previous step's tmsmt1 left it: blomgpu_step must not fold this step's tmsmt1 into its tmsmt2
 bool dia_reads_dpold(const blomgpu_ctx *c) { return c->dia && c->dia->vfl; }
+// A selected row accumulates one of the heat and salt flux diagnostics that eddtra, diffus and pbcor keep current for diaacc alone
+// (blomgpu_step, flux_diag): by the table's source column, whatever the row's kind (layers, depth levels, classes).  An OP_COL
+// row's src is a C_* code, not a field.
+bool dia_reads_flux_diag(const blomgpu_ctx *c) {
+  if (!c->dia) return false;
+  for (int r : c->dia->rows) {
+    if (g_rows[r].op == OP_COL) continue;
+    for (int f : {F_utflx, F_usflx, F_vtflx, F_vsflx, F_utfltd, F_usfltd, F_vtfltd, F_vsfltd, F_utflld, F_usflld, F_vtflld, F_vsflld})
+      if (g_rows[r].src == f) return true;
+  }
+  return false;
+}
 // the accumulators as a halo update sees them (xctilr of uflxlvl / vflxlvl inside diavfl): base and number of doubles in whole planes
 // one of mldl82 mldl82mn mldl82mx mldl82sq is selected: cmnfld1 forms mldl82 under isopyc_bulkml too (phy/mod_cmnfld_routines.F90:1109-1113)
 bool dia_reads_mldl82(const blomgpu_ctx *c) { return c->dia && c->dia->ml82; }

@@ -36,6 +36,9 @@
 #define MV(m) (((m) >> 2) & 1)
 
 // move_mask: tracers (bit nt) that are NOT diffused but wait in the work space (pbcor1 left them there): interior copy
+// FLUX_DIAG = false (a step of blomgpu_step that leaves nothing observable in them, api.hip: flux_diag): neither the loads of the old
+// usflx utflx vsflx vtflx nor the stores to them and to usflld utflld vsflld vtflld -- nothing in the step reads those arrays
+template <bool FLUX_DIAG>
 __global__ void __launch_bounds__(DT_NT) k_diffus_tile(const DevView *__restrict__ Vp, int mm, int nn, int ntx, unsigned long long move_mask) {
   const DevView &V = *Vp;
   __shared__ double sc[(4 + DT_TB) * DT_LN];                  // dp, difiso, S, T, tracer batch
@@ -79,7 +82,7 @@ __global__ void __launch_bounds__(DT_NT) k_diffus_tile(const DevView *__restrict
   const double vxc = V.f[F_scvx][c], vyic = V.f[F_scvyi][c], vxn = V.f[F_scvx][nb], vyin = V.f[F_scvyi][nb];
   const double s2 = V.f[F_scp2][c];
   gd_t o_us = V.f[F_usflx] + c + okm, o_ut = V.f[F_utflx] + c + okm, o_vs = V.f[F_vsflx] + c + okm, o_vt = V.f[F_vtflx] + c + okm;
-  const double us_o = *o_us, ut_o = *o_ut, vs_o = *o_vs, vt_o = *o_vt;
+  const double us_o = FLUX_DIAG ? *o_us : 0., ut_o = FLUX_DIAG ? *o_ut : 0., vs_o = FLUX_DIAG ? *o_vs : 0., vt_o = FLUX_DIAG ? *o_vt : 0.;
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const int m = t + r * DT_NT;
@@ -102,13 +105,13 @@ __global__ void __launch_bounds__(DT_NT) k_diffus_tile(const DevView *__restrict
     // faces without a u-/v-point keep the 0 the flux arrays hold there (phy/mod_diffusion.F90:452-500)
     const double fsw = uw ? qw * (l_s[q - 1] - l_s[q]) : 0., ftw = uw ? qw * (l_t[q - 1] - l_t[q]) : 0.;
     const double fss = vs ? qs * (l_s[q - DT_LW] - l_s[q]) : 0., fts = vs ? qs * (l_t[q - DT_LW] - l_t[q]) : 0.;
-    if (uw) {                                                // :95-96, :105-106
+    if (FLUX_DIAG && uw) {                                   // :95-96, :105-106
       V.f[F_usflld][c + okm] = fsw;
       V.f[F_utflld][c + okm] = ftw;
       *o_us = us_o + fsw;
       *o_ut = ut_o + ftw;
     }
-    if (vs) {                                                // :117-118, :127-128
+    if (FLUX_DIAG && vs) {                                   // :117-118, :127-128
       V.f[F_vsflld][c + okm] = fss;
       V.f[F_vtflld][c + okm] = fts;
       *o_vs = vs_o + fss;
@@ -251,7 +254,8 @@ int st_diffus(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   {
     TimeScope ts(c, "diffus");
     const int ntx = (h.ni + DT_TW - 1) / DT_TW, nty = (h.nj + DT_TH - 1) / DT_TH;
-    hipLaunchKernelGGL(k_diffus_tile, dim3(ntx * nty, h.kk), dim3(DT_NT), 0, c->stream, c->d, mm, nn, ntx, move_mask);
+    if (flux_diag_on(c)) hipLaunchKernelGGL((k_diffus_tile<true>), dim3(ntx * nty, h.kk), dim3(DT_NT), 0, c->stream, c->d, mm, nn, ntx, move_mask);
+    else hipLaunchKernelGGL((k_diffus_tile<false>), dim3(ntx * nty, h.kk), dim3(DT_NT), 0, c->stream, c->d, mm, nn, ntx, move_mask);
   }
   HIPCHK(c, hipGetLastError());
   return 0;

@@ -315,7 +315,8 @@ int st_eddtra(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
     else if (h.P.eitmth == 2)
       hipLaunchKernelGGL(k_eddtra_gm, plane_grid(h, 2, 64), dim3(64), 0, c->stream, c->d, n, mm, nn, errflag);
     else return ctx_fail(c, " eitmth_opt is unsupported for vcoord = 'isopyc_bulkml'!");   // :1829-1835
-    hipLaunchKernelGGL(k_eddtra_ts, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, mm);
+    // (diagnostics only: not in the steps of a blomgpu_step call that leave nothing observable in them, api.hip: flux_diag)
+    if (flux_diag_on(c)) hipLaunchKernelGGL(k_eddtra_ts, plane_grid(h, h.kk), dim3(256), 0, c->stream, c->d, mm);
   }
   HIPCHK(c, hipGetLastError());
   if (h.P.eitmth == 2 && !c->seq.defer_checks) return ctx_check_errors(c);      // :536-555, :640-660

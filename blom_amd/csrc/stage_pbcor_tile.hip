@@ -55,6 +55,9 @@ __device__ inline void face_flux(const DevView &V, const double *sc, bool wet, d
 
 // from_remap (pbcor1 inside blomgpu_step): dp, T, S and the advected tracers of the level come from the work-space planes in
 // which remap left them (stage_remap_tile.hip, FOLD), not from their fields
+// FLUX_DIAG = false (a step of blomgpu_step that leaves nothing observable in them, api.hip: flux_diag): neither the loads nor the
+// stores of the accumulated usflx utflx vsflx vtflx -- nothing in the step reads them; the mass fluxes are k_pbc_total's and stay
+template <bool FLUX_DIAG>
 __global__ void __launch_bounds__(PT_NT) k_pbc_tile(const DevView *__restrict__ Vp, int which, int offc, int offf, int ntx, int from_remap KPROF_ARGS) {
   const DevView &V = *Vp;
   __shared__ double sc[(3 + PT_TB) * PT_LN];                 // dp, saln, temp, one batch of tracers
@@ -108,7 +111,8 @@ __global__ void __launch_bounds__(PT_NT) k_pbc_tile(const DevView *__restrict__ 
   const double s2i = V.f[F_scp2i][c];
   gd_t o_uf = V.f[F_uflx] + c + okf, o_us = V.f[F_usflx] + c + okf, o_ut = V.f[F_utflx] + c + okf;
   gd_t o_vf = V.f[F_vflx] + c + okf, o_vs = V.f[F_vsflx] + c + okf, o_vt = V.f[F_vtflx] + c + okf;
-  const double uf_o = *o_uf, us_o = *o_us, ut_o = *o_ut, vf_o = *o_vf, vs_o = *o_vs, vt_o = *o_vt;
+  const double uf_o = *o_uf, vf_o = *o_vf;
+  const double us_o = FLUX_DIAG ? *o_us : 0., ut_o = FLUX_DIAG ? *o_ut : 0., vs_o = FLUX_DIAG ? *o_vs : 0., vt_o = FLUX_DIAG ? *o_vt : 0.;
 #pragma unroll
   for (int r = 0; r < 2; r++) {
     const int m = t + r * PT_NT;
@@ -129,13 +133,17 @@ __global__ void __launch_bounds__(PT_NT) k_pbc_tile(const DevView *__restrict__ 
   face_flux(V, sc, vs, vt_c, vt_c > 0. ? q - PT_LW : q, vt_c > 0. ? c - ni : c, vt_c > 0. ? pb_s : pb_c, pbvt_c, k, S);
   if (uw) {                                                  // :262-264, :608-610
     *o_uf = uf_o + W.f;
-    *o_us = us_o + W.f2;
-    *o_ut = ut_o + W.f3;
+    if (FLUX_DIAG) {
+      *o_us = us_o + W.f2;
+      *o_ut = ut_o + W.f3;
+    }
   }
   if (vs) {
     *o_vf = vf_o + S.f;
-    *o_vs = vs_o + S.f2;
-    *o_vt = vt_o + S.f3;
+    if (FLUX_DIAG) {
+      *o_vs = vs_o + S.f2;
+      *o_vt = vt_o + S.f3;
+    }
   }
   face_flux(V, sc, upd && MU(mp_e), ut_e, ut_e > 0. ? q : q + 1, ut_e > 0. ? c : e, ut_e > 0. ? pb_c : pb_e, pbut_e, k, E);
   face_flux(V, sc, upd && MV(mp_n), vt_n, vt_n > 0. ? q : q + PT_LW, vt_n > 0. ? c : nb, vt_n > 0. ? pb_c : pb_n, pbvt_n, k, N);
@@ -274,7 +282,8 @@ int pbcor_tile_launch(blomgpu_ctx *c, int which, int m, int offc, int offf, int 
   const int ntx = (h.ni + PT_TW - 1) / PT_TW, nty = (h.nj + PT_TH - 1) / PT_TH;
   {
     TimeScope tk(c, "k_pbc_tile");
-    hipLaunchKernelGGL(k_pbc_tile, dim3(ntx * nty, h.kk), dim3(PT_NT), 0, c->stream, c->d, which, offc, offf, ntx, from_remap KPROF_PASS(10));
+    if (flux_diag_on(c)) hipLaunchKernelGGL((k_pbc_tile<true>), dim3(ntx * nty, h.kk), dim3(PT_NT), 0, c->stream, c->d, which, offc, offf, ntx, from_remap KPROF_PASS(10));
+    else hipLaunchKernelGGL((k_pbc_tile<false>), dim3(ntx * nty, h.kk), dim3(PT_NT), 0, c->stream, c->d, which, offc, offf, ntx, from_remap KPROF_PASS(10));
   }
   // inside blomgpu_step pbcor1 hands S, T and the tracers to diffus through the work space, pbcor2 to tmsmt2
   // (with ltedtp = 'neutral' diffus is halo updates only: nothing to hand to it)

@@ -125,6 +125,11 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_step(self.ctx, C.byref(ns), nsteps))
         return ns.value
 
+    def keep_flux_diagnostics(self, on=1):
+        """on: every step of a step() call keeps utflx .. vsflx, u|v t|s fltd, u|v t|s flld current, not only its last two
+        (get_real("flux_diag_steps_skipped") counts the steps that did not) -- blomgpu_keep_flux_diagnostics"""
+        self._chk(self.lib.blomgpu_keep_flux_diagnostics(self.ctx, C.c_int(int(on))))
+
     def sync(self):
         self._chk(self.lib.blomgpu_sync(self.ctx))
 

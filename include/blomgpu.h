@@ -372,8 +372,17 @@ int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int n
  * Option "use_graph" = 1 (default 0: replay measures 2 % slower than plain launches on ROCm 7.2): on a single tile the
  * sequence is captured in the third step after the last change of an option or of the time step (the fourth step from rest) -- for both parities of the time levels at once -- and
  * replayed as HIP graphs from then on (steps with the stage timers on, "timing" = 1, run plain launches beside the graphs);
- * blomgpu_get_real "graph_steps" / "graph_failures" count the replays / the captures that failed. */
+ * blomgpu_get_real "graph_steps" / "graph_failures" count the replays / the captures that failed.
+ *
+ * The heat and salt flux diagnostics -- utflx usflx vtflx vsflx, utfltd usfltd vtfltd vsfltd, utflld usflld vtflld vsflld -- hold
+ * what the reference holds, on both time levels, when the call has returned.  Inside a call of more than two steps they are
+ * kept current only while something reads them every step (a diaacc selection with one of them as a source, "csdiag", a
+ * captured graph, the hybrid coordinates): nothing in a step reads them, and the steps that could leave nothing visible in them
+ * skip the passes over memory that only keep them up to date.  A call that fails part-way leaves them undefined.
+ * blomgpu_get_real "flux_diag_steps_skipped" counts the steps that skipped since the context was created;
+ * blomgpu_keep_flux_diagnostics(ctx, 1) keeps the arrays current in every step (0, the default, gives the above back). */
 int  blomgpu_step(blomgpu_ctx *, int *nstep, int nsteps);
+int  blomgpu_keep_flux_diagnostics(blomgpu_ctx *, int on);
 
 /* Tile decomposition (xcspmd/xctilr, phy/mod_xc.F90:1332-3188).  A context is one tile
  * (dims.i0/j0/itdm/jtdm).  Two transports serve blomgpu_xctilr and every halo update inside the stages:

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Timeline of one baroclinic step from a rocprofv3 kernel trace (csv): for every launch of the step its start relative to the
 step's first kernel, its duration, its queue, and how much of it overlapped with launches on other queues.  A step starts at
-a launch of k_init_fluxes* (the sequence's first kernel); the step printed is the last but one complete step of the trace."""
+a launch of k_init_fluxes* (the sequence's first kernel); the step printed is the last but one complete step of the trace, or,
+with a second argument BACK, the step BACK steps before the last one that used more than one queue (the last two steps of a
+blomgpu_step call keep the heat and salt flux diagnostics current, the ones before them do not: BACK = 3 shows one of those)."""
 import csv, re, sys
 
 rows = []
@@ -18,7 +20,8 @@ if len(starts) < 3:
 # the bench's last steps run with stage timers (every stage on one queue): take the last step that used more than one queue
 cands = [(starts[i], starts[i + 1]) for i in range(len(starts) - 1)]
 multi = [ab for ab in cands if len({r[3] for r in rows[ab[0]:ab[1]]}) > 1]
-a, b = (multi[-2] if len(multi) > 1 else multi[-1]) if multi else cands[-2]
+back = int(sys.argv[2]) if len(sys.argv) > 2 else 1
+a, b = (multi[-1 - back] if len(multi) > back else multi[-1]) if multi else cands[-2]
 step = rows[a:b]
 print("# steps in the trace (launches, queues, us): " + " ".join(f"{y - x}/{len({r[3] for r in rows[x:y]})}/{(max(r[1] for r in rows[x:y]) - rows[x][0]) / 1e3:.0f}" for x, y in cands))
 t0 = step[0][0]
