@@ -5,6 +5,7 @@
 #include "pow_libm.h"
 #include "sin_libm.h"
 #include "atan2_libm.h"
+#include <algorithm>
 #include <cstring>
 #include <string_view>
 
@@ -192,7 +193,7 @@ struct Opt {
 #define CB(nm) {#nm, O_BOOL, IN_C(nm), 0}
 #define ONE_OR_TWO(msg) [](double &v) -> const char * { return v != 1 && v != 2 ? msg : nullptr; }
 // (a declared context allocates the option's 48-level array when the option is switched on, outside the step: stage_thermf_cesm.hip)
-#define RLX(nm, fid) {#nm, O_BOOL, IN_C(nm), 0, nullptr, [](blomgpu_ctx *c) { if (c->nm && c->cesm_declared) (void)cesm_field(c, fid); }}
+#define RLX(nm, fid) {#nm, O_BOOL, IN_C(nm), 0, nullptr, [](blomgpu_ctx *c) { if (c->nm && frc_declared(c)) (void)cesm_field(c, fid); }}
 #define LMI(n) {"l" #n "mi", O_INT, [](blomgpu_ctx *c) { return Slot(c->lmi[n - 1]); }, 0, \
                 [](double &v) -> const char * { return v < 1 || v > 12 ? "blomgpu_set_int: l" #n "mi is a month, 1..12" : nullptr; }}
 static const Opt g_opts[] = {
@@ -277,6 +278,7 @@ static const Opt g_opts[] = {
 // l1ci, l2ci (cesm/mod_cesm.F90:55-103), mod_forcing's use_stream_relaxation, mod_time's nstep_in_day and nday_of_year (nstep and
 // nday_in_year stand in the table above), and the A/B switch of thermf_cesm's sums.  blomgpu_option_name lists the table above only:
 // its rows are pinned name by name (tests/test_option_table.py), and these names mean nothing until blomgpu_inifrc_cesm has been called.
+// The forced ocean-ice experiment (stage_thermf_ben02.hip) needs nstep_in_day and nday_of_year of these, and none of its own.
 static const Opt g_cesm_opts[] = {
   CB(smtfrc), CB(use_stream_relaxation), CI(nstep_in_cpl), CI(l1ci), CI(l2ci), CI(nstep_in_day), CI(nday_of_year), CI(cesm_single_sums),
 };
@@ -456,6 +458,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   ale_free(c);
   dia_free(c);
   cesm_free(c);
+  ben02_free(c);
   if (c->ale_plevel) (void)hipFree(c->ale_plevel);
   if (c->arc_strip) (void)hipFree(c->arc_strip);
   if (c->xcsum_buf) (void)hipFree(c->xcsum_buf);
@@ -509,8 +512,9 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   if (s == "flux_diag_steps_skipped") { *v = (double)c->flux_diag_skipped; return 0; }
   // thermf_cesm's correction of the virtual salt flux (cesm/mod_thermf_cesm.F90:342-343), from the sum the last thermf left on the device
   if (s == "thermf_cesm_launches") { *v = (double)c->cesm_launches; return 0; }      // (counted where they are issued, single tile)
+  if (s == "thermf_ben02_launches") { *v = c->ben02_declared ? (double)c->cesm_launches : 0.; return 0; }   // (the same counter: one family a context)
   if (s == "sflxc") {
-    if (!c->cesm_declared) return ctx_fail(c, "blomgpu_get_real: sflxc exists once blomgpu_inifrc_cesm has been called");
+    if (!frc_declared(c)) return ctx_fail(c, "blomgpu_get_real: sflxc exists once blomgpu_inifrc_cesm has been called");
     double sum = 0.;
     HIPCHK(c, hipMemcpyAsync(&sum, c->cesm_sums, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -547,7 +551,7 @@ int blomgpu_option_name(int index, char *buf, int cap, int *kind) {
 int blomgpu_field_info(blomgpu_ctx *c, const char *name, int *nlev, int *is_int) {
   auto it = c->real_ids.find(name);
   if (it != c->real_ids.end()) {
-    *nlev = c->nlev_real[it->second];
+    *nlev = ctx_real_nlev(c, it->second);
     if (std::string(name) == "trc" || std::string(name) == "trcold")
       *nlev = c->h.ntr * (std::string(name) == "trc" ? 2 : 1) * c->h.kk;
     *is_int = 0;
@@ -564,11 +568,11 @@ static int real_levels(blomgpu_ctx *c, const char *who, const char *name, int le
   if (!c || !name) return ctx_fail(c, std::string(who) + ": null argument");
   auto it = c->real_ids.find(name);
   if (it == c->real_ids.end()) return ctx_fail(c, std::string(who) + ": unknown field " + name);
-  if (lev0 < 1 || nlev < 1 || lev0 - 1 + nlev > c->nlev_real[it->second])
+  if (lev0 < 1 || nlev < 1 || lev0 - 1 + nlev > ctx_real_nlev(c, it->second))
     return ctx_fail(c, std::string(who) + ": levels out of range for field " + name + " (lev0 is 1-based)");
   if (int rc = cesm_field(c, it->second)) return rc;
-  if (!c->h.f[it->second]) return ctx_fail(c, std::string(who) + ": field " + name + " has no memory");
-  *ptr = c->h.f[it->second] + (size_t)(lev0 - 1) * c->h.nplane;
+  if (!ctx_real_ptr(c, it->second)) return ctx_fail(c, std::string(who) + ": field " + name + " has no memory");
+  *ptr = ctx_real_ptr(c, it->second) + (size_t)(lev0 - 1) * c->h.nplane;
   return 0;
 }
 
@@ -581,7 +585,7 @@ static int locate(blomgpu_ctx *c, const char *name, int nlev, void **ptr, size_t
     *bytes = sizeof(int) * (size_t)nlev * c->h.nplane;
   } else {
     if (int rc = cesm_field(c, c->real_ids[name])) return rc;      // (a 48-level array of the coupled experiment, on first use)
-    *ptr = c->h.f[c->real_ids[name]];
+    *ptr = ctx_real_ptr(c, c->real_ids[name]);
     *bytes = sizeof(double) * (size_t)nlev * c->h.nplane;
   }
   return 0;
@@ -648,13 +652,12 @@ int blomgpu_field_name(blomgpu_ctx *c, int index, char *buf, int cap) {
   const int nr = (int)c->real_ids.size(), ni = (int)c->int_ids.size();
   if (index < 0 || index >= nr + ni || cap < 2) return 1;
   const auto &m = index < nr ? c->real_ids : c->int_ids;
-  const int want = index < nr ? index : index - nr;
-  for (const auto &kv : m)
-    if (kv.second == want) {
-      snprintf(buf, cap, "%s", kv.first.c_str());
-      return 0;
-    }
-  return 1;
+  // the index-th name in the order of the ids (which have gaps once blomgpu_inifrc_ben02 has named a part of the forcing lists)
+  std::vector<std::pair<int, const std::string *>> byid;
+  for (const auto &kv : m) byid.emplace_back(kv.second, &kv.first);
+  std::sort(byid.begin(), byid.end());
+  snprintf(buf, cap, "%s", byid[index < nr ? index : index - nr].second->c_str());
+  return 0;
 }
 
 // settings of the reference's compile-time tracer switches that this library does not carry
@@ -764,6 +767,7 @@ int blomgpu_sfcstr(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
   const std::string &e = c->expcnf;
   if (e == "noforcing" || e == "fuk95" || e == "channel") return 0;
   if (cesm_on(c)) return st_sfcstr_cesm(c);
+  if (ben02_on(c)) return st_sfcstr_ben02(c);
   if (e == "cesm")
     return ctx_fail(c, " sfcstr: expcnf = " + e + " is not built on the device (sfcstr_cesm / sfcstr_ben02) until blomgpu_inifrc_cesm has been called");
   if (e == "ben02clim" || e == "ben02syn" || e == "single_column")
@@ -777,13 +781,32 @@ int blomgpu_thermf(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1
     if (int rc = check_tracer_options(c)) return rc;
     return st_thermf_cesm(c, m, n, mm, nn, k1m, k1n);
   }
+  if (ben02_on(c)) {
+    if (int rc = check_tracer_options(c)) return rc;
+    return st_thermf_ben02(c, m, n, mm, nn, k1m, k1n);
+  }
   if (c->expcnf == "cesm") return ctx_fail(c, "thermf: expcnf = cesm is not built on the device until blomgpu_inifrc_cesm has been called");
   ctx_sync_view(c);
   return st_thermf(c, m, n, mm, nn, k1m, k1n);
 }
 // The coupled experiment (expcnf = 'cesm').  blomgpu_inifrc_cesm is inifrc_cesm (cesm/mod_cesm.F90:175-200) and the declaration that the
 // coupler's forcing exists; blomgpu_getfrc_cesm is getfrc_cesm (:202-263); blomgpu_cesm_nflxdi returns mod_forcing's nflxdi(48).
-int blomgpu_inifrc_cesm(blomgpu_ctx *c) { return c ? cesm_inifrc(c) : ctx_fail(c, "blomgpu_inifrc_cesm: null argument"); }
+int blomgpu_inifrc_cesm(blomgpu_ctx *c) {
+  if (!c) return ctx_fail(c, "blomgpu_inifrc_cesm: null argument");
+  if (c->ben02_declared) return ctx_fail(c, "blomgpu_inifrc_cesm: this context has declared the forced ocean-ice experiment's forcing (blomgpu_inifrc_ben02)");
+  return cesm_inifrc(c);
+}
+// The forced ocean-ice experiment (expcnf = 'ben02clim' / 'ben02syn' / 'single_column'; stage_thermf_ben02.hip).  blomgpu_inifrc_ben02
+// declares that its forcing exists; blomgpu_ben02_ntda returns mod_ben02's ntda, the steps thermf_ben02 has accumulated into tsi_tda
+// tml_tda sml_tda alb_tda fice_tda; blomgpu_ben02_reset_tda zeroes the five planes and the count, as asflux does when it has used them
+// (ben02/mod_ben02.F90:1623-1624, :1701-1705).
+int blomgpu_inifrc_ben02(blomgpu_ctx *c) { return c ? ben02_inifrc(c) : ctx_fail(c, "blomgpu_inifrc_ben02: null argument"); }
+int blomgpu_ben02_ntda(blomgpu_ctx *c, int *n) {
+  if (!c || !n) return ctx_fail(c, "blomgpu_ben02_ntda: null argument");
+  *n = c->ntda;
+  return 0;
+}
+int blomgpu_ben02_reset_tda(blomgpu_ctx *c) { return c ? ben02_reset_tda(c) : ctx_fail(c, "blomgpu_ben02_reset_tda: null argument"); }
 int blomgpu_getfrc_cesm(blomgpu_ctx *c) { return st_getfrc_cesm(c); }
 int blomgpu_cesm_nflxdi(blomgpu_ctx *c, int *out) {
   if (!c || !out) return ctx_fail(c, "blomgpu_cesm_nflxdi: null argument");
@@ -945,7 +968,9 @@ static int step_sequence(STAGE_ARGS) {
   // reads or writes what the second stream holds at that point: the viscous chain of momtum reads no wind stress (k_mom_cor_march
   // does, behind pgforc), and thermf_cesm beside diapfl's momentum mixing reads p, dp, temp, saln, trc and writes surface planes only
   // (tools/kernel_rw_sets.py: k_diapfl_momentum / k_diapfl_dpudpv write u, v, dpu, dpv).
-  const bool cesm = cesm_on(c);
+  // The forced ocean-ice experiment, once declared (stage_thermf_ben02.hip), has no getfrc stage on the device (asflux is the host's); its
+  // sfcstr and thermf stand where the coupled experiment's do, and read and write the same arrays of the step plus planes of their own.
+  const bool cesm = cesm_on(c), ben02 = ben02_on(c), frc = cesm || ben02;
   c->seq = StepState{};
   c->seq.defer_checks = c->seq.in_sequence = true;
   {
@@ -962,12 +987,12 @@ static int step_sequence(STAGE_ARGS) {
       for (const StageId st : seq_ale) {
         if (c->tmsmt1_done_ahead && st == S_tmsmt1) { c->tmsmt1_done_ahead = false; continue; }
         if (c->eddtra_frozen && st == S_eddtra) continue;
-        if (cesm && st == S_pgforc)
+        if (frc && st == S_pgforc)
           if (int rc = stage(S_sfcstr)) return rc;
         if (int rc = stage(st)) return rc;
         if (cesm && st == S_init_fluxes)
           if (int rc = stage(S_getfrc_cesm)) return rc;
-        if (cesm && st == S_momtum)
+        if (frc && st == S_momtum)
           if (int rc = stage(S_thermf)) return rc;
       }
     } else for (const StageId st : seq) {
@@ -1000,7 +1025,7 @@ static int step_sequence(STAGE_ARGS) {
         c->seq.diapfl_mom_on_side = c->seq.updtrc_on_side = false;
         if (ctx_side_done(c, ev) || ctx_side_join(c, ev)) return 1;
       }
-      if (cesm && st == S_pgforc)
+      if (frc && st == S_pgforc)
         if (int rc = stage(S_sfcstr)) return rc;
       if (int rc = stage(run)) return rc;
       if (cesm && st == S_init_fluxes)
@@ -1039,6 +1064,8 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
   if (int rc = dia_step_check(c)) return rc;
   if (cesm_on(c) && c->use_graph)
     return ctx_fail(c, "blomgpu_step: the coupled experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
+  if (ben02_on(c) && c->use_graph)
+    return ctx_fail(c, "blomgpu_step: the forced ocean-ice experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
   // (the stage entries outside this call keep the flux diagnostics current, whichever way it returns)
   struct FluxDiagBack { blomgpu_ctx *c; ~FluxDiagBack() { c->flux_diag = true; } } flux_diag_back{c};
   // the row test walks the selection: once per call, the selection cannot change inside it

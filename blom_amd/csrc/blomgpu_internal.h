@@ -114,6 +114,17 @@
   X(tflxap, 48) X(sflxap, 48) X(tflxdi, 48) X(sflxdi, 48) X(thermf_util, NT + 1)
 #define BLOM_CESM_INT_FIELDS(X) X(ipwocn, 1)
 
+// The forced ocean-ice experiment's own planes (expcnf = 'ben02clim' / 'ben02syn' / 'single_column': ben02/mod_ben02.F90:150-214,
+// ben02/mod_thdysi.F90:32-33, phy/mod_seaice.F90; stage_thermf_ben02.hip).  They exist once blomgpu_inifrc_ben02 has declared that
+// experiment's forcing, which also gives ztx mty thermf_util ipwocn and the four 48-level arrays of the list above their names and
+// memory.  One plane each, numbered from 0 in a table of their own at the END of DevView (V.b[F_hicem]): no member of the view that an
+// undeclared context's kernels read moves.  On the host the id of such a plane is FID_BEN02 + its number (ctx_real_ptr).
+#define BLOM_BEN02_REAL_FIELDS(X)                                                                                                \
+  /* mod_seaice */ X(hicem, 1) X(hsnwm, 1) X(ustari, 1) X(tauxice, 1) X(tauyice, 1) X(iagem, 1)                                  \
+  /* mod_thdysi */ X(tsrfm, 1) X(ticem, 1)                                                                                       \
+  /* mod_ben02 */ X(tsi, 1) X(dfl, 1) X(albw, 1) X(alb, 1) X(rnfins, 1) X(rnfres, 1)                                             \
+  X(tsi_tda, 1) X(tml_tda, 1) X(sml_tda, 1) X(alb_tda, 1) X(fice_tda, 1)
+
 #define BLOM_INT_FIELDS(X) X(ip, 1) X(iu, 1) X(iv, 1) X(iq, 1) X(kfpla, 2) X(kming, 1) X(cppm_sti, 1) X(cppm_stj, 1) X(mpack, 1) \
   /* mod_difest: kmax, kfil, msku, mskv (mod_difest.F90:97-100) */ X(dfe_kmax, 1) X(dfe_kfil, 1) X(msku, K) X(mskv, K)
 
@@ -133,6 +144,13 @@ enum IFieldId {
 #undef X
       NF_INT
 };
+enum Ben02FieldId {
+#define X(name, lev) F_##name,
+  BLOM_BEN02_REAL_FIELDS(X)
+#undef X
+      NF_BEN02
+};
+constexpr int FID_BEN02 = NF_REAL + 2;      // (NF_REAL and NF_REAL + 1 name the work space and diaacc's accumulators: ctx_locate_ptr)
 
 // ---- scalar options (namelist-type module variables of the reference) ----------------
 struct Params {
@@ -214,6 +232,7 @@ struct DevView {
   double *wk;
   double *wk2d;
   int nwk;
+  PtrTable<double, NF_BEN02> b;   // the forced ocean-ice experiment's planes (BLOM_BEN02_REAL_FIELDS); null until blomgpu_inifrc_ben02
 };
 #define WK(V, w) (global_ptr((V).wk) + (size_t)(w) * (V).kk * (V).nplane)
 #define WK2(V, w) (global_ptr((V).wk2d) + (size_t)(w) * (V).nplane)
@@ -489,8 +508,13 @@ struct blomgpu_ctx {
   std::vector<double> dia_sigdia;              // blomgpu_dia_set_sigdia: the kk diagnostic density classes; empty: none (a class name is refused)
   bool cesm_declared = false;                  // blomgpu_inifrc_cesm has been called: the coupler's forcing exists (cesm/mod_cesm.F90:175-200)
   int nflxdi[48] = {};                         // mod_forcing's nflxdi: how often thermf_cesm has added to level ntld of tflxdi / sflxdi
-  long long cesm_launches = 0;                 // kernel launches of thermf_cesm so far, its batched sums included (blomgpu_get_real "thermf_cesm_launches")
+  long long cesm_launches = 0;                 // kernel launches of the declared family's thermf so far, its batched sums included (blomgpu_get_real "thermf_cesm_launches", "thermf_ben02_launches")
   double *cesm_sums = nullptr, *cesm_rows = nullptr;   // thermf_cesm's global sums (3 + ntr, on the device) and their row sums
+  // the forced ocean-ice experiment (stage_thermf_ben02.hip): blomgpu_inifrc_ben02 has been called; its planes are one allocation
+  // (NF_BEN02 planes, h.b[k] = ben02_planes + k * nplane).  The sums and the launch count use cesm_sums / cesm_rows / cesm_launches:
+  // a context declares one of the two families
+  bool ben02_declared = false;
+  double *ben02_planes = nullptr;
   int dia_alarm = -1;                          // blomgpu_dia_alarm: alarm_phy(1) as the host declared it, 0 | 1; -1: undeclared
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
@@ -551,9 +575,26 @@ int cesm_inifrc(blomgpu_ctx *);                                                 
 int cesm_field(blomgpu_ctx *, int fid);                                          // a 48-level array that is about to be used: allocate it
 void cesm_free(blomgpu_ctx *);
 static inline bool cesm_on(const blomgpu_ctx *c) { return c->cesm_declared && c->expcnf == "cesm"; }
+int frc_alloc(blomgpu_ctx *, double **p, int nlev);                              // nlev zeroed planes at *p unless it has memory already
+int frc_sum_buffers(blomgpu_ctx *);                                              // cesm_sums / cesm_rows for 3 + ntr sums
 int st_getfrc_cesm(blomgpu_ctx *);                                               // cesm/mod_cesm.F90:202-263
 int st_sfcstr_cesm(blomgpu_ctx *);                                               // cesm/mod_sfcstr_cesm.F90:33-65
 int st_thermf_cesm(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // cesm/mod_thermf_cesm.F90:58-432
+// stage_thermf_ben02.hip: the surface forcing of the forced ocean-ice experiment (Bentsen & Drange 2002)
+static inline bool ben02_expcnf(const std::string &e) { return e == "ben02clim" || e == "ben02syn" || e == "single_column"; }
+static inline bool ben02_on(const blomgpu_ctx *c) { return c->ben02_declared && ben02_expcnf(c->expcnf); }
+static inline bool frc_declared(const blomgpu_ctx *c) { return c->cesm_declared || c->ben02_declared; }
+int ben02_inifrc(blomgpu_ctx *);                                                 // the declaration: fields, names, zeroed accumulators
+int ben02_reset_tda(blomgpu_ctx *);                                              // ben02/mod_ben02.F90:1623-1624, :1701-1705
+void ben02_free(blomgpu_ctx *);
+int st_sfcstr_ben02(blomgpu_ctx *);                                              // ben02/mod_sfcstr_ben02.F90:35-72
+int st_thermf_ben02(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // ben02/mod_thermf_ben02.F90:65-703
+// a registered real field by its host id: the field table, or a plane of the forced ocean-ice experiment
+static inline double *ctx_real_ptr(const blomgpu_ctx *c, int id) {
+  if (id < FID_BEN02) return c->h.f[id];
+  return c->ben02_planes ? c->ben02_planes + (size_t)(id - FID_BEN02) * c->h.nplane : nullptr;
+}
+static inline int ctx_real_nlev(const blomgpu_ctx *c, int id) { return id < FID_BEN02 ? c->nlev_real[id] : 1; }
 // halo.hip: xcsum of nb planes at once, the sums left on the device in out[0..nb-1]; mask[q] == nullptr: ips
 int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int *const *masks, double *rows, double *out);
 int st_niw_ke_tendency(blomgpu_ctx *, int m, int mm);                           // stage_difest.hip

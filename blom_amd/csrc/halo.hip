@@ -426,11 +426,14 @@ int ctx_locate_ptr(const blomgpu_ctx *c, const double *p, size_t *offset) {
   size_t na = 0;
   if (const double *b = dia_acc_span(c, &na))
     if (p >= b && p < b + na) { *offset = (size_t)(p - b); return NF_REAL + 1; }
+  // the planes of the forced ocean-ice experiment (sfcstr_ben02 exchanges hicem): one allocation, id FID_BEN02
+  if (const double *b = c->ben02_planes)
+    if (p >= b && p < b + (size_t)NF_BEN02 * c->h.nplane) { *offset = (size_t)(p - b); return FID_BEN02; }
   return -1;
 }
 static inline double *located_base(const blomgpu_ctx *c, int fid) {
   size_t na = 0;
-  return fid == NF_REAL + 1 ? dia_acc_span(c, &na) : fid == NF_REAL ? c->h.wk : c->h.f[fid];
+  return fid == FID_BEN02 ? c->ben02_planes : fid == NF_REAL + 1 ? dia_acc_span(c, &na) : fid == NF_REAL ? c->h.wk : c->h.f[fid];
 }
 
 // closed / periodic rule of the global domain in each direction (phy/mod_xc.F90:4378,4400)

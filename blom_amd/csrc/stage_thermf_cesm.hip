@@ -16,9 +16,8 @@
 // Roofline: HBM, ~45 two-dimensional planes (plus 2 kk + 2 (kk+1) levels under the hybrid coordinate); launch-bound at channel size.
 #include "blomgpu_internal.h"
 #include "pow_libm.h"
+#include "thermf_relax.h"
 #include <cmath>
-
-#define NLEV_RLX 48      // levels of tflxap sflxap tflxdi sflxdi (phy/mod_forcing.F90:95-100)
 
 struct GetfrcPar { double w1, w2; int l1, l2; };      // l1, l2: 0-based levels of the _da pairs
 
@@ -29,20 +28,6 @@ struct ThermfCesmPar {
   int l1mi, l2mi, l3mi, l4mi, l5mi, m1, m2, m3, m4, m5, ntld;   // 1-based, as the reference's
   int use_gls, stream, aptflx, apsflx, ditflx, disflx, srxbal, hybrid;
 };
-
-// phy/mod_intp1d.F90:29-52
-__device__ inline double intp1d_cesm(double d1, double d2, double d3, double d4, double d5, double x) {
-  const double a1 = -3. / 7., a2 = -15. / 7., a3 = 3. / 2., b1 = 4. / 7., b2 = -16. / 7., b3 = 15. / 7., b4 = -5. / 7., b5 = 2. / 7.,
-               c1 = -1. / 7., c2 = 9. / 14;
-  const double a = a1 * (d1 + d5) + a2 * d3 + a3 * (d2 + d4);
-  const double b = b1 * d1 + b2 * d2 + b3 * d3 + b4 * d4 + b5 * d5;
-  const double cc = c1 * (d1 + d4) + c2 * (d2 + d3);
-  return (a * x + b) * x + cc;
-}
-__device__ inline double intp5(gcd_t a, size_t np, int l1, int l2, int l3, int l4, int l5, double x) {
-  return intp1d_cesm(a[(size_t)(l1 - 1) * np], a[(size_t)(l2 - 1) * np], a[(size_t)(l3 - 1) * np], a[(size_t)(l4 - 1) * np],
-                     a[(size_t)(l5 - 1) * np], x);
-}
 
 __global__ void k_getfrc_cesm(const DevView *__restrict__ Vp, GetfrcPar G) {
   const DevView &V = *Vp;
@@ -66,46 +51,6 @@ __global__ void k_sfcstr_cesm(const DevView *__restrict__ Vp) {
   if (j < 1 || j > V.jj || i < 1 || i > V.ii) return;
   if (V.m[I_iu][c]) V.f[F_taux][c] = V.f[F_ztx][c];
   if (V.m[I_iv][c]) V.f[F_tauy][c] = V.f[F_mty][c];
-}
-
-// The column walk of the hybrid coordinate, :218-242 (x = temp, with t0deg added at the exit) and :279-303 (x = saln): the fractions of the
-// relaxation flux that pass the kk+1 interfaces, and the mean of x over the relaxation depth.  Fortran leaves the loop at the first
-// interface whose fraction turns negative (level k), having added x(k)*frac(k) (+ t0deg), and zeroes the interfaces k+1 .. kk+1; a
-// column shallower than the relaxation depth never leaves it: nothing is zeroed and t0deg is never added.  Every interface is
-// written exactly once here, with the value the two Fortran loops leave there.  The planes are level-major: a wavefront's store
-// of a level is contiguous.  COLUMN_U levels of dp and x are requested before the first is used.
-__device__ inline double rs_walk(gcd_t dp, gcd_t x, gd_t frac, size_t np, int kk, double dprsi, bool add_t0deg) {
-  double cur = 1., mean = 0.;
-  frac[0] = 1.;
-  bool out = false;
-  for (int k0 = 0; k0 < kk; k0 += COLUMN_U) {
-    const int nu = kk - k0 < COLUMN_U ? kk - k0 : COLUMN_U;
-    double d[COLUMN_U], v[COLUMN_U];
-    if (!out) {
-#pragma unroll
-      for (int u = 0; u < COLUMN_U; u++)
-        if (u < nu) { d[u] = dp[(size_t)(k0 + u) * np]; v[u] = x[(size_t)(k0 + u) * np]; }
-    }
-#pragma unroll
-    for (int u = 0; u < COLUMN_U; u++) {
-      if (u >= nu) break;
-      double next = 0.;
-      if (!out) {
-        next = cur - d[u] * dprsi;
-        if (next < 0.) {
-          mean = mean + v[u] * cur;
-          if (add_t0deg) mean = mean + T0DEG;
-          out = true;
-          next = 0.;
-        } else {
-          mean = mean + v[u] * (cur - next);
-        }
-        cur = next;
-      }
-      frac[(size_t)(k0 + u + 1) * np] = next;
-    }
-  }
-  return mean;
 }
 
 __global__ void k_thermf_cesm_flux(const DevView *__restrict__ Vp, ThermfCesmPar T, int nn, int k1m, int k1n) {
@@ -260,7 +205,7 @@ __global__ void k_thermf_cesm_corr(const DevView *__restrict__ Vp, ThermfCesmPar
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-static int cesm_alloc(blomgpu_ctx *c, double **p, int nlev) {
+int frc_alloc(blomgpu_ctx *c, double **p, int nlev) {
   if (*p) return 0;
   const size_t bytes = sizeof(double) * (size_t)nlev * c->h.nplane;
   HIPCHK(c, hipMalloc((void **)p, bytes));
@@ -272,8 +217,18 @@ static bool cesm_lazy(int fid) { return fid == F_tflxap || fid == F_sflxap || fi
 
 int cesm_field(blomgpu_ctx *c, int fid) {
   if (fid < NF_BASE_REAL || fid >= NF_REAL || c->h.f[fid]) return 0;
-  if (!c->cesm_declared) return ctx_fail(c, "a field of the coupled experiment does not exist until blomgpu_inifrc_cesm has been called");
-  return cesm_alloc(c, &c->h.f[fid], c->nlev_real[fid]);
+  if (!frc_declared(c)) return ctx_fail(c, "a field of the coupled experiment does not exist until blomgpu_inifrc_cesm has been called");
+  return frc_alloc(c, &c->h.f[fid], c->nlev_real[fid]);
+}
+
+// the global sums of thermf (3 + ntr, on the device) and their row sums
+int frc_sum_buffers(blomgpu_ctx *c) {
+  const DevView &h = c->h;
+  const int nsum = 3 + (h.ntr > 0 ? h.ntr : 1);
+  if (!c->cesm_sums) HIPCHK(c, hipMalloc((void **)&c->cesm_sums, sizeof(double) * nsum));
+  if (!c->cesm_rows) HIPCHK(c, hipMalloc((void **)&c->cesm_rows, sizeof(double) * (size_t)nsum * h.jtdm));
+  HIPCHK(c, hipMemsetAsync(c->cesm_sums, 0, sizeof(double) * nsum, c->stream));
+  return 0;
 }
 
 // inifrc_cesm, cesm/mod_cesm.F90:175-200.  The file reads of initai / rdcsic / rdctsf / rdcsss / idarlx stay the host's (sstclm ricclm
@@ -296,25 +251,22 @@ int cesm_inifrc(blomgpu_ctx *c) {
   }
   for (int f = NF_BASE_REAL; f < NF_REAL; f++)
     if (!cesm_lazy(f))
-      if (int rc = cesm_alloc(c, &h.f[f], c->nlev_real[f])) return rc;
+      if (int rc = frc_alloc(c, &h.f[f], c->nlev_real[f])) return rc;
   for (int f = NF_BASE_INT; f < NF_INT; f++) {
     if (h.m[f]) continue;
     const size_t bytes = sizeof(int) * (size_t)c->nlev_int[f] * h.nplane;
     HIPCHK(c, hipMalloc((void **)&h.m[f], bytes));
     HIPCHK(c, hipMemsetAsync(h.m[f], 0, bytes, c->stream));
   }
-  const int nsum = 3 + (h.ntr > 0 ? h.ntr : 1);
-  if (!c->cesm_sums) HIPCHK(c, hipMalloc((void **)&c->cesm_sums, sizeof(double) * nsum));
-  if (!c->cesm_rows) HIPCHK(c, hipMalloc((void **)&c->cesm_rows, sizeof(double) * (size_t)nsum * h.jtdm));
-  HIPCHK(c, hipMemsetAsync(c->cesm_sums, 0, sizeof(double) * nsum, c->stream));
+  if (int rc = frc_sum_buffers(c)) return rc;
   // the 48-level arrays whose option is on already (one switched on later: api.hip's option table allocates it then, outside the step)
-  if (c->aptflx) if (int rc = cesm_alloc(c, &h.f[F_tflxap], NLEV_RLX)) return rc;
-  if (c->apsflx) if (int rc = cesm_alloc(c, &h.f[F_sflxap], NLEV_RLX)) return rc;
+  if (c->aptflx) if (int rc = frc_alloc(c, &h.f[F_tflxap], NLEV_RLX)) return rc;
+  if (c->apsflx) if (int rc = frc_alloc(c, &h.f[F_sflxap], NLEV_RLX)) return rc;
   if (c->ditflx || c->disflx) {                                   // phy/mod_idarlx.F90:89-114
     for (int &n : c->nflxdi) n = 0;
     for (int f : {(int)F_tflxdi, (int)F_sflxdi}) {
       if (!(f == F_tflxdi ? c->ditflx : c->disflx)) continue;
-      if (int rc = cesm_alloc(c, &h.f[f], NLEV_RLX)) return rc;
+      if (int rc = frc_alloc(c, &h.f[f], NLEV_RLX)) return rc;
       HIPCHK(c, hipMemsetAsync(h.f[f], 0, sizeof(double) * (size_t)NLEV_RLX * h.nplane, c->stream));
     }
   }

@@ -130,6 +130,19 @@ module mod_blomgpu
       type(c_ptr), value :: c
       integer(c_int), intent(out) :: out(48)
     end function
+    integer(c_int) function blomgpu_inifrc_ben02(c) bind(C, name='blomgpu_inifrc_ben02')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_ben02_ntda(c, ntda) bind(C, name='blomgpu_ben02_ntda')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), intent(out) :: ntda
+    end function
+    integer(c_int) function blomgpu_ben02_reset_tda(c) bind(C, name='blomgpu_ben02_reset_tda')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
     integer(c_int) function blomgpu_dia_name_ext(index, buf, cap, kind, grid) bind(C, name='blomgpu_dia_name_ext')
       import :: c_int, c_char
       integer(c_int), value :: index, cap
@@ -278,6 +291,7 @@ module mod_blomgpu
             cmnfld_bfsqi_ale, gpu_set_vector, difest_isobml, thermf, mxlayr, diaacc, ale_remap_diazlv
   public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext, gpu_dia_alarm
   public :: inifrc_cesm, getfrc_cesm, gpu_cesm_nflxdi, gpu_upload_level
+  public :: inifrc_ben02, gpu_ben02_ntda, gpu_ben02_reset_tda
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
@@ -656,6 +670,21 @@ contains
     integer(c_int) :: n(48)
     call gpu_check(blomgpu_cesm_nflxdi(ctx, n), 'gpu_cesm_nflxdi')
     nflxdi = int(n)
+  end subroutine
+  ! The forced ocean-ice experiment (expcnf = 'ben02clim' / 'ben02syn' / 'single_column').  inifrc_ben02 declares that its forcing
+  ! exists: until it has been called sfcstr and thermf refuse these experiments.  asflux stays the host's: it reads the five _tda planes
+  ! and gpu_ben02_ntda, uploads its fluxes by name, and calls gpu_ben02_reset_tda (ben02/mod_ben02.F90:1623-1624, :1701-1705).
+  subroutine inifrc_ben02()
+    call gpu_check(blomgpu_inifrc_ben02(ctx), 'inifrc_ben02')
+  end subroutine
+  subroutine gpu_ben02_ntda(ntda)               ! mod_ben02's ntda
+    integer, intent(out) :: ntda
+    integer(c_int) :: n
+    call gpu_check(blomgpu_ben02_ntda(ctx, n), 'gpu_ben02_ntda')
+    ntda = int(n)
+  end subroutine
+  subroutine gpu_ben02_reset_tda()
+    call gpu_check(blomgpu_ben02_reset_tda(ctx), 'gpu_ben02_reset_tda')
   end subroutine
   ! the depth levels of the *lvl names as depthslev_bnds(2,ddm) (phy/mod_dia.F90:119-128); refused while a *lvl name is selected
   subroutine gpu_dia_set_levels(bnds, ddm)

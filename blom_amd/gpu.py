@@ -190,6 +190,23 @@ class BlomGpu:
         self._chk(self.lib.blomgpu_cesm_nflxdi(self.ctx, out.ctypes.data_as(C.c_void_p)))
         return out
 
+    # -- the forced ocean-ice experiment (expcnf = 'ben02clim' / 'ben02syn' / 'single_column') --------
+    def inifrc_ben02(self):
+        """the declaration that the forced ocean-ice experiment's forcing exists: creates hicem hsnwm ustari tauxice tauyice iagem tsrfm
+        ticem tsi dfl albw alb rnfins rnfres, the five _tda accumulators, ztx mty, ipwocn ... -- blomgpu_inifrc_ben02"""
+        self._chk(self.lib.blomgpu_inifrc_ben02(self.ctx))
+        self._info = {}
+
+    def ben02_ntda(self):
+        """mod_ben02's ntda: the steps thermf_ben02 has accumulated into the _tda planes -- blomgpu_ben02_ntda"""
+        n = C.c_int(0)
+        self._chk(self.lib.blomgpu_ben02_ntda(self.ctx, C.byref(n)))
+        return n.value
+
+    def ben02_reset_tda(self):
+        """the five _tda planes and ntda to zero, as asflux leaves them -- blomgpu_ben02_reset_tda"""
+        self._chk(self.lib.blomgpu_ben02_reset_tda(self.ctx))
+
     def exp(self, x):
         """exp() as the kernels evaluate it (blom_amd/csrc/exp_libm.h), elementwise."""
         x = np.ascontiguousarray(x, dtype=np.float64).ravel()

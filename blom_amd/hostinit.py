@@ -543,6 +543,71 @@ def put_cesm_forcing(be, case, forcing=None, seed=0):
     return f
 
 
+BEN02_FLUXES = "swa nsf dfl lip sop eva rfi rnfins ustarw tsi albw ztx mty ustari tauxice tauyice".split()    # what asflux leaves (ben02/mod_ben02.F90:1602-1918)
+BEN02_ICE = "ficem hicem hsnwm tsrfm iagem rnfres".split()                                             # the state thermf_ben02 carries
+
+
+def ben02_forcing(case, seed=0):
+    """Synthetic forcing and ice state for expcnf = 'ben02clim' / 'ben02syn', seeded and deterministic: the fluxes asflux would leave
+    (BEN02_FLUXES), an ice / snow state (BEN02_ICE), a latitude of both signs, and the climatologies, applied relaxation fluxes,
+    corrections and world-ocean mask of `cesm_forcing`.  The ice state is laid out in twelve classes, (i + 3 j) mod 12, so that every
+    part of a grid holds every regime thermf_ben02 distinguishes: no ice (0-3, one of them with a remainder below the 1e-5 threshold),
+    a snow layer under a cold / a melting surface (4, 5), thin or no snow on ice of 0.3 .. 5 m under a cold / a melting surface (6, 7:
+    albi_h on either side of albi_f and albi_m), ice of millimetres (8), a snow load that floods (9), dfl = fcond / (2 - fice)
+    (10: the degenerate solution for the surface temperature) and a closed or all but closed cover (11).  Whole padded planes.  Returns {name: array};
+    `put_ben02_forcing` uploads it."""
+    rng = np.random.default_rng(1000 + seed)
+    nj, ni = case.jdm + 2 * NBDY, case.idm + 2 * NBDY
+    y, x = np.arange(nj)[:, None] / nj, 2 * np.pi * (np.arange(ni)[None, :] - NBDY) / case.idm
+    dt = float(case.params["baclin"])
+
+    def fld(mean, amp, phase=0.0):
+        return (mean + amp * (np.sin(x + phase) * (0.5 + y) + 0.5 * rng.standard_normal((nj, ni))))[None]
+    f = {k: v for k, v in cesm_forcing(case, seed).items() if k in ("sstclm", "ricclm", "sssclm", "tflxap", "sflxap", "salt_corr", "trc_corr", "ipwocn")}
+    f.update(swa=np.abs(fld(120.0, 100.0, 2.3)), nsf=fld(-60.0, 160.0, 3.3), dfl=-np.abs(fld(14.0, 6.0, 0.4)) - 1.0,
+             lip=np.abs(fld(3e-5, 3e-5, 1.0)), sop=np.abs(fld(2e-5, 2e-5, 2.0)), eva=-np.abs(fld(4e-5, 3e-5, 3.0)),
+             rfi=np.abs(fld(2e-7, 4e-7, 5.0)), rnfins=np.abs(fld(1e-6, 2e-6, 4.0)), ustarw=np.abs(fld(0.008, 0.004)) + 1e-4,
+             tsi=fld(262.0, 8.0, 1.4), albw=0.065 + 0.02 * rng.random((1, nj, ni)), ztx=fld(0.05, 0.1, 0.6), mty=fld(0.0, 0.05, 1.6),
+             ustari=np.abs(fld(0.006, 0.006, 2.6)), tauxice=fld(0.02, 0.05, 3.6), tauyice=fld(0.0, 0.03, 4.6))
+    cls = (np.arange(ni)[None, :] + 3 * np.arange(nj)[:, None]) % 12
+    fice = 0.3 + 0.69 * rng.random((nj, ni))
+    hice = 0.3 + 4.7 * rng.random((nj, ni))
+    hsnw = np.zeros((nj, ni))
+    tsrf = 250.0 + 20.0 * rng.random((nj, ni))
+    hsnw[(cls == 4) | (cls == 5)] = 0.3
+    hice[(cls == 4) | (cls == 5)] = 1.5
+    tsrf[cls == 5] = 273.12
+    tsrf[cls == 7] = 273.0
+    hsnw[cls == 7] = 1.0e-4
+    hice[cls == 8] = 1.0e-3 * (1.0 + 4.0 * rng.random((nj, ni)))[cls == 8]
+    fice[cls == 8] = 0.5
+    hice[cls == 9], hsnw[cls == 9] = 0.3, 0.3
+    fice[cls == 11], hice[cls == 11] = 1.0, 2.0
+    fice[(cls == 11) & (np.arange(nj)[:, None] % 2 == 1)] = 0.9949        # (new ice in the lead takes it past fice_max)
+    fice[cls < 4], hice[cls < 4] = 0.0, 0.0
+    fice[cls == 3], hice[cls == 3] = 0.01, 5.0e-4
+    fcond = 2.04 * 0.31 / (0.31 * hice + 2.04 * (hsnw + f["sop"][0] * dt / 330.0))
+    f["dfl"][0][cls == 10] = (fcond / (2.0 - fice))[cls == 10]
+    # a warm surface gets the heat to melt, every second one of them
+    warm = ((cls == 5) | (cls == 7)) & (np.arange(nj)[:, None] % 2 == 0)
+    f["nsf"][0][warm] = 150.0
+    f.update(ficem=fice[None], hicem=hice[None], hsnwm=hsnw[None], tsrfm=tsrf[None], iagem=300.0 * rng.random((1, nj, ni)) * (fice > 0.0),
+             rnfres=1e-3 * rng.random((1, nj, ni)), plat=(70.0 * np.sin(2 * np.pi * (np.arange(nj)[:, None] - NBDY + 0.5) / case.jdm) + 0.0 * x)[None])
+    return f
+
+
+def put_ben02_forcing(be, case, forcing=None, seed=0):
+    """upload `ben02_forcing` (after be.inifrc_ben02()); ipwocn is cut to the wet points"""
+    f = dict(forcing if forcing is not None else ben02_forcing(case, seed))
+    nj, ni = case.jdm + 2 * NBDY, case.idm + 2 * NBDY
+    f["ipwocn"] = (f["ipwocn"].reshape(1, nj, ni) * (np.asarray(be.masks["ip"]).reshape(1, nj, ni) > 0)).astype(np.int32)
+    for nm, a in f.items():
+        if nm == "trc_corr" and not case.ntr:
+            continue
+        be.put(nm, a)
+    return f
+
+
 def ocean_area(be, case):
     """mod_grid's area: the sum of scp2 over ips (ip without the seam row of an arctic patch) of the WHOLE domain `be` holds"""
     ip = be.masks["ip"] if hasattr(be, "masks") else None

@@ -74,6 +74,18 @@ FULL_STAGES_LIVE_CESM = _cesm(FULL_STAGES_LIVE)
 HYBRID_STAGES_CESM = _cesm(HYBRID_STAGES, thermf_after="momtum")
 
 
+# The forced ocean-ice experiment (expcnf = 'ben02clim' / 'ben02syn' / 'single_column'), once BlomGpu.inifrc_ben02 has declared its forcing:
+# sfcstr in front of pgforc and thermf at phy/mod_blom_step.F90:188, as above; no getfrc stage (asflux stays on the host).
+def _ben02(stages, thermf_after=None):
+    return tuple(s for s in _cesm(stages, thermf_after) if s != "getfrc_cesm")
+
+
+DYNCORE_STAGES_BEN02 = _ben02(DYNCORE_STAGES)
+FULL_STAGES_BEN02 = _ben02(FULL_STAGES)
+FULL_STAGES_LIVE_BEN02 = _ben02(FULL_STAGES_LIVE)
+HYBRID_STAGES_BEN02 = _ben02(HYBRID_STAGES, thermf_after="momtum")
+
+
 def dyncore_step(be, nstep, baclin, stages=DYNCORE_STAGES, hook=None):
     """Advance backend `be` from step count nstep to nstep+1.  `hook(stage, sextuple)` is
     called before each stage (tests use it to snapshot stage inputs)."""

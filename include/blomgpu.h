@@ -197,6 +197,34 @@ int  blomgpu_upload_level(blomgpu_ctx *, const char *name, const void *host, int
 int  blomgpu_getfrc_cesm(blomgpu_ctx *);
 int  blomgpu_cesm_nflxdi(blomgpu_ctx *, int out[48]);
 int  blomgpu_xcsum_batch(blomgpu_ctx *, const char *name, int lev0, int nlev, const char *mask, double *sums);
+/* The surface forcing of the forced ocean-ice experiment, expcnf = 'ben02clim' / 'ben02syn' / 'single_column' (Bentsen & Drange 2002;
+ * blom_amd/csrc/stage_thermf_ben02.hip): the one family in which BLOM itself carries sea ice.
+ * blomgpu_inifrc_ben02: the declaration that this forcing exists.  Refused unless expcnf is one of the three, on a context that has
+ *                       called blomgpu_inifrc_cesm (and the other way round), and with "use_graph" = 1.  It creates, all zero:
+ *   hicem hsnwm ustari tauxice tauyice iagem                          (phy/mod_seaice.F90:35-42; ficem exists)
+ *   tsrfm ticem                                                       (ben02/mod_thdysi.F90:32-33)
+ *   tsi dfl albw alb rnfins rnfres, tsi_tda tml_tda sml_tda alb_tda fice_tda   (ben02/mod_ben02.F90:150-214)
+ *   ztx mty, thermf_util (1 + ntr planes), ipwocn (integer), tflxap sflxap tflxdi sflxdi (48 levels; memory on first use)
+ *   Until it has been called nothing of this exists and blomgpu_sfcstr / blomgpu_thermf refuse the three experiments as before.
+ *   Afterwards:
+ *   blomgpu_sfcstr       ben02/mod_sfcstr_ben02.F90:35-72 sfcstr_ben02: ficem, hicem with a halo of one, then
+ *                        taux = ztx (1 - facice) + tauxice facice at u-points, tauy likewise at v-points
+ *   blomgpu_thermf       ben02/mod_thermf_ben02.F90:65-703 thermf_ben02, both vertical coordinates: the slab ice / snow thermodynamics
+ *                        with ben02/mod_thdysi.F90:60-78's parameters, lead freezing and lateral melt, the runoff reservoir
+ *                        (rnfins -> rnfres -> rnf), fmltfz sfl brnflx salflx hmltfz surflx sswflx, trflx, the relaxation (sstclm in
+ *                        kelvin, ricclm sssclm; "trxday" .. "srxlim", "aptflx" "apsflx" "ditflx" "disflx" "srxbal", "nstep_in_day",
+ *                        "nday_of_year"), iagem, ustar; it adds to the five _tda planes and to ntda (:356-360, :671) and to nflxdi (:115).
+ *                        swtfrz: drivers/nocoupler/mod_swtfrz.F with phy/mod_eos.F90:137-141's coefficients.  Four launches a call up to
+ *                        32 planes in the batch (blomgpu_get_real "thermf_ben02_launches"); "srxbal" is refused on tiles.
+ *   blomgpu_step         runs sfcstr in front of pgforc (phy/mod_blom_step.F90:163) and thermf at :188 (full_physics and the hybrid
+ *                        sequence); there is no getfrc stage: asflux (ben02/mod_ben02.F90:1602-1918) stays the host's, which uploads
+ *                        swa nsf dfl lip sop eva rfi rnfins ustarw tsi albw ztx mty ustari tauxice tauyice by name.  A call of N steps keeps
+ *                        them fixed and leaves ntda = N.
+ * blomgpu_ben02_ntda: mod_ben02's ntda.  blomgpu_ben02_reset_tda: the five _tda planes and ntda to zero (ben02/mod_ben02.F90:1623-1624,
+ * :1701-1705: what asflux does once it has used the averages). */
+int  blomgpu_inifrc_ben02(blomgpu_ctx *);
+int  blomgpu_ben02_ntda(blomgpu_ctx *, int *ntda);
+int  blomgpu_ben02_reset_tda(blomgpu_ctx *);
 /* phy/mod_mxlayr.F90:130 mxlayr(m,n,mm,nn,k1m,k1n): the bulk mixed layer of vcoord_type = 'isopyc_bulkml' (turbulent kinetic
  * energy balance, detrainment / entrainment, surface forcing, the new layer structure at the velocity points), called after
  * thermf (phy/mod_blom_step.F90:188-192).  Reads the surface fluxes surflx, surrlx, sswflx, salflx, brnflx, salrlx, trflx, the

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Which arrays a kernel of blom_amd/csrc reads and writes, from its source text: the fields V.f[F_*], the integer fields V.m[I_*], the
+"""Which arrays a kernel of blom_amd/csrc reads and writes, from its source text: the fields V.f[F_*] (and V.b[F_*]), the integer fields V.m[I_*], the
 work-space slots WK(V, slot) / WK2(V, slot) (slot names resolved to numbers through the enums and #defines of the file and of the
 headers it includes with "...", so that slots of different stages compare).  An array counts as WRITTEN when it is bound to a mutable
 pointer (gd_t / gi_t) or stored through directly; every other mention is a read.  Used by tests/test_side_by_side_sets.py to check the pairs blomgpu_step runs side by side on its two
@@ -106,7 +106,7 @@ def rw_sets(path, kernel):
         m = re.search(r"\b(gd_t|gi_t|double\s*\*|int\s*\*)(?:\s*const)?\s*(?:__restrict__\s*)?\w+\s*=(.*)", stmt, re.S)
         if m:                                            # mutable pointer(s): every array named on the right-hand side(s)
             writes |= set(_names(m.group(2), val))
-        for m in re.finditer(r"(?:V\.[fm]\[[^\]]*\]|WK2?\([^)]*\))(?:\s*\+[^;=\[]*)?\[[^;]*?\]\s*(?:=(?!=)|[-+*/]=)", stmt):
+        for m in re.finditer(r"(?:V\.[fmb]\[[^\]]*\]|WK2?\([^)]*\))(?:\s*\+[^;=\[]*)?\[[^;]*?\]\s*(?:=(?!=)|[-+*/]=)", stmt):
             writes |= set(_names(m.group(0).split("]")[0] + "]" if m.group(0).startswith("V.") else m.group(0), val))
     for fn, outs in OUT_ARGS.items():
         for m in re.finditer(r"\b%s\s*\(" % fn, body):
