@@ -128,7 +128,7 @@ int ctx_check_errors(blomgpu_ctx *c) {
     if (ctx_check_errors(G)) { c->err = G->err; return 1; }
   if (c->ale && c->h.P.vcoord_tag != 1)
     if (int rc = ale_check_deferred(c)) return rc;
-  if (!c->err_dev) return 0;
+  if (!c->err_dev) return stepend_check_errors(c);
   int e[5] = {0, 0, 0, 0, 0};          // (word 3: convec's iteration limit, which the reference only prints: not an error)
   HIPCHK(c, hipMemcpyAsync(e, c->err_dev, sizeof(e), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -140,7 +140,7 @@ int ctx_check_errors(blomgpu_ctx *c) {
   if (e[1] & 2) return ctx_fail(c, "blom: eddtra_gm_isopyc_bulkml: flux bound violated");          // mod_eddtra.F90:640-660
   if (e[4]) return ctx_fail(c, "ndiff: a face found more neutral layers than its record space holds");
   if (e[2]) return ctx_fail(c, "barotp: a tile of the persistent substep kernel timed out waiting for its neighbours");
-  return 0;
+  return stepend_check_errors(c);                          // chkvar, the step's last call (phy/mod_chkvar.F90:77-141)
 }
 
 // an option that the cached ALE structures depend on has changed: report what the engine still holds of earlier steps (its deferred
@@ -181,7 +181,7 @@ struct Opt {
   void (*after)(blomgpu_ctx *);       // what else follows from the new value
   // O_STR: what the refusal says in front of the value, and the accepted words with their codes (none: the string itself is stored)
   const char *refuse;
-  struct { const char *word; int code; } words[3];
+  struct { const char *word; int code; } words[5];
 };
 #define IN_P(m) [](blomgpu_ctx *c) { return Slot(c->h.P.m); }
 #define IN_C(m) [](blomgpu_ctx *c) { return Slot(c->m); }
@@ -282,6 +282,16 @@ static const Opt g_opts[] = {
 static const Opt g_cesm_opts[] = {
   CB(smtfrc), CB(use_stream_relaxation), CI(nstep_in_cpl), CI(l1ci), CI(l2ci), CI(nstep_in_day), CI(nday_of_year), CI(cesm_single_sums),
 };
+// The end of blom_step (stage_stepend.hip), likewise a table of its own that blomgpu_option_name does not list: the clock (step_time),
+// mod_swabs' swamth, jwtype, chlopt (phy/mod_swabs.F90:92-94; refused in iniswa's words), mod_forcing's sprfac and prfac
+// (phy/mod_forcing.F90:48, :115), and chkvar.  A new swamth wants blomgpu_iniswa again; sprfac = 1 does what inivar_forcing does for it.
+static const Opt g_stepend_opts[] = {
+  CB(step_time), CB(chkvar), CI(jwtype), {"chlopt", O_STR, IN_C(chlopt), 0},
+  {"swamth", O_STR, IN_C(swamth), 0, nullptr, nullptr, " iniswa: swamth = ",                               // phy/mod_swabs.F90:601-606
+   {{"top-layer", SWA_TOP_LAYER}, {"jerlov", SWA_JERLOV}, {"chlorophyll_ma94", SWA_MA94}, {"chlorophyll_ohl03", SWA_OHL03}, {"spatial_frac_attlen", SWA_SPATIAL}}},
+  {"sprfac", O_BOOL, IN_C(sprfac), 0, nullptr, [](blomgpu_ctx *c) { (void)stepend_set_sprfac(c); }},
+  {"prfac", O_REAL, IN_C(prfac), READABLE},
+};
 #undef IN_P
 #undef IN_C
 #undef PR
@@ -297,6 +307,8 @@ static const Opt *find_opt(std::string_view name, unsigned kinds) {      // kind
   for (const Opt &o : g_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   for (const Opt &o : g_cesm_opts)
+    if (name == o.name && (kinds >> o.kind & 1)) return &o;
+  for (const Opt &o : g_stepend_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   return nullptr;
 }
@@ -459,6 +471,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   dia_free(c);
   cesm_free(c);
   ben02_free(c);
+  stepend_free(c);
   if (c->ale_plevel) (void)hipFree(c->ale_plevel);
   if (c->arc_strip) (void)hipFree(c->arc_strip);
   if (c->xcsum_buf) (void)hipFree(c->xcsum_buf);
@@ -490,6 +503,7 @@ int blomgpu_set_str(blomgpu_ctx *c, const char *name, const char *val) {
   for (const auto &w : o->words)
     if (w.word && v == w.word) {
       if (o->at) o->at(c).put(w.code);
+      if (o->at && o->at(c).i == &c->swamth) c->swa_ready = false;      // (blomgpu_iniswa once more)
       return o->flags & ALE_RESET ? ale_reset(c) : 0;
     }
   return ctx_fail(c, o->refuse + v + " is unsupported!");
@@ -513,6 +527,12 @@ int blomgpu_get_real(blomgpu_ctx *c, const char *name, double *v) {
   // thermf_cesm's correction of the virtual salt flux (cesm/mod_thermf_cesm.F90:342-343), from the sum the last thermf left on the device
   if (s == "thermf_cesm_launches") { *v = (double)c->cesm_launches; return 0; }      // (counted where they are issued, single tile)
   if (s == "thermf_ben02_launches") { *v = c->ben02_declared ? (double)c->cesm_launches : 0.; return 0; }   // (the same counter: one family a context)
+  // the clock, while blomgpu_step keeps it (step_time = 1; stage_stepend.hip): what the last step's step_time left where the setters write
+  if (c->step_time) {
+    if (s == "xmi") { *v = c->xmi; return 0; }
+    if (s == "nday_of_year") { *v = c->nday_of_year; return 0; }
+    if (s.size() == 4 && s[0] == 'l' && s[1] >= '1' && s[1] <= '5' && s.compare(2, 2, "mi") == 0) { *v = c->lmi[s[1] - '1']; return 0; }
+  }
   if (s == "sflxc") {
     if (!frc_declared(c)) return ctx_fail(c, "blomgpu_get_real: sflxc exists once blomgpu_inifrc_cesm has been called");
     double sum = 0.;
@@ -808,6 +828,17 @@ int blomgpu_ben02_ntda(blomgpu_ctx *c, int *n) {
 }
 int blomgpu_ben02_reset_tda(blomgpu_ctx *c) { return c ? ben02_reset_tda(c) : ctx_fail(c, "blomgpu_ben02_reset_tda: null argument"); }
 int blomgpu_getfrc_cesm(blomgpu_ctx *c) { return st_getfrc_cesm(c); }
+// The end of blom_step (stage_stepend.hip).  Each returns at once unless its option has declared it.
+int blomgpu_iniswa(blomgpu_ctx *c) { return c ? stepend_iniswa(c) : ctx_fail(c, "blomgpu_iniswa: null argument"); }   // phy/mod_swabs.F90:216
+int blomgpu_updswa(blomgpu_ctx *c) { return c ? st_updswa(c) : ctx_fail(c, "blomgpu_updswa: null argument"); }        // phy/mod_swabs.F90:611
+int blomgpu_fwbbal(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {                                   // phy/mod_forcing.F90:361
+  (void)m; (void)n; (void)mm; (void)nn; (void)k1m; (void)k1n;
+  return c ? st_fwbbal(c) : ctx_fail(c, "blomgpu_fwbbal: null argument");
+}
+int blomgpu_chkvar(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {                                   // phy/mod_chkvar.F90:77
+  (void)m; (void)n; (void)mm; (void)k1m; (void)k1n;
+  return c ? st_chkvar(c, nn) : ctx_fail(c, "blomgpu_chkvar: null argument");
+}
 int blomgpu_cesm_nflxdi(blomgpu_ctx *c, int *out) {
   if (!c || !out) return ctx_fail(c, "blomgpu_cesm_nflxdi: null argument");
   for (int k = 0; k < 48; k++) out[k] = c->nflxdi[k];
@@ -931,7 +962,8 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
   X(mxlayr_tail, blomgpu_mxlayr_tail(c, nn, k1n)) X(mxlayr, blomgpu_mxlayr(ALL6)) X(thermf, blomgpu_thermf(ALL6))                 \
   X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
   X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6)) \
-  X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6)) X(getfrc_cesm, blomgpu_getfrc_cesm(c))
+  X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6)) X(getfrc_cesm, blomgpu_getfrc_cesm(c)) \
+  X(updswa, blomgpu_updswa(c)) X(fwbbal, blomgpu_fwbbal(ALL6)) X(chkvar, blomgpu_chkvar(ALL6))
 enum StageId {
 #define X(nm, call) S_##nm,
   BLOM_STAGES(X)
@@ -970,7 +1002,10 @@ static int step_sequence(STAGE_ARGS) {
   // (tools/kernel_rw_sets.py: k_diapfl_momentum / k_diapfl_dpudpv write u, v, dpu, dpv).
   // The forced ocean-ice experiment, once declared (stage_thermf_ben02.hip), has no getfrc stage on the device (asflux is the host's); its
   // sfcstr and thermf stand where the coupled experiment's do, and read and write the same arrays of the step plus planes of their own.
-  const bool cesm = cesm_on(c), ben02 = ben02_on(c), frc = cesm || ben02;
+  // updswa (stage_stepend.hip) behind getfrc (:122) whenever a chlorophyll method is declared, for every expcnf: it writes the four band
+  // planes and chl10 only, which nothing between the lean init_fluxes and advect touches (thermf and ale_forcing read them, far behind),
+  // and nothing runs on the second stream at that point (tools/kernel_rw_sets.py: k_updswa).
+  const bool cesm = cesm_on(c), ben02 = ben02_on(c), frc = cesm || ben02, swa = swa_chlorophyll(c);
   c->seq = StepState{};
   c->seq.defer_checks = c->seq.in_sequence = true;
   {
@@ -992,6 +1027,8 @@ static int step_sequence(STAGE_ARGS) {
         if (int rc = stage(st)) return rc;
         if (cesm && st == S_init_fluxes)
           if (int rc = stage(S_getfrc_cesm)) return rc;
+        if (swa && st == S_init_fluxes)
+          if (int rc = stage(S_updswa)) return rc;
         if (frc && st == S_momtum)
           if (int rc = stage(S_thermf)) return rc;
       }
@@ -1030,6 +1067,8 @@ static int step_sequence(STAGE_ARGS) {
       if (int rc = stage(run)) return rc;
       if (cesm && st == S_init_fluxes)
         if (int rc = stage(S_getfrc_cesm)) return rc;
+      if (swa && st == S_init_fluxes)
+        if (int rc = stage(S_updswa)) return rc;
       // cmnfld2's kernels still alone on the second stream (frozen diffusivities: difest_isobml did not wait for them): eddtra reads the slopes
       if (st == S_halo_difest && c->seq.cmn_on_side) {
         c->seq.cmn_on_side = false;
@@ -1049,7 +1088,18 @@ static int step_sequence(STAGE_ARGS) {
   // diaacc (:239) with a selection: on the context's stream, behind everything the step put on the second one (the last of it
   // is joined in front of pbcor2).  Its sources are arrays of the finished step; the tmsmt1 that tmsmt_ahead folded into tmsmt2
   // wrote *old arrays only (diavfl reads dpold: with its group selected nothing is folded, blomgpu_step).  blomgpu_step counts the step (a capture passes here without executing)
-  if (dia_active(c)) return st_diaacc(ALL6);
+  if (dia_active(c))
+    if (int rc = st_diaacc(ALL6)) return rc;
+  // fwbbal (:242) and chkvar (:252), each only where its option has declared it (stage_stepend.hip); chkvar leaves its words on the
+  // device for blomgpu_step's check, like every stage of the sequence
+  if (c->sprfac)
+    if (int rc = st_fwbbal(c)) return rc;
+  if (c->chkvar) {
+    c->seq.defer_checks = true;
+    const int rc = st_chkvar(c, nn);
+    c->seq.defer_checks = false;
+    return rc;
+  }
   return 0;
 }
 #undef ALL6
@@ -1066,6 +1116,7 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     return ctx_fail(c, "blomgpu_step: the coupled experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
   if (ben02_on(c) && c->use_graph)
     return ctx_fail(c, "blomgpu_step: the forced ocean-ice experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
+  if (int rc = stepend_step_check(c)) return rc;
   // (the stage entries outside this call keep the flux diagnostics current, whichever way it returns)
   struct FluxDiagBack { blomgpu_ctx *c; ~FluxDiagBack() { c->flux_diag = true; } } flux_diag_back{c};
   // the row test walks the selection: once per call, the selection cannot change inside it
@@ -1075,6 +1126,10 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     const int m = ns % 2 + 1, n = (ns + 1) % 2 + 1;
     const int mm = (m - 1) * kk, nn = (n - 1) * kk, k1m = 1 + mm, k1n = 1 + nn;
     c->h.P.nstep = ns + 1;                             // read by host code only: no upload of the view for it
+    // step_time (phy/mod_time.F90:182-219; stage_stepend.hip): the day of the year and the interpolation scalars of this step, where the
+    // setters put them -- context members that host code reads, no upload of the view either
+    if (c->step_time)
+      if (int rc = stepend_step_time(c, ns + 1)) return rc;
     ctx_sync_view(c);
     // (not while diavfl's group is selected: its dp(km) - dpold(km) needs the dpold the PREVIOUS step's tmsmt1 left, and the fold
     // would have tmsmt2 overwrite it in front of diaacc.  The cost of the launch it brings back: DESIGN 3.13)

@@ -125,6 +125,12 @@
   /* mod_ben02 */ X(tsi, 1) X(dfl, 1) X(albw, 1) X(alb, 1) X(rnfins, 1) X(rnfres, 1)                                             \
   X(tsi_tda, 1) X(tml_tda, 1) X(sml_tda, 1) X(alb_tda, 1) X(fice_tda, 1)
 
+// What the end of blom_step adds (stage_stepend.hip): mod_swabs' chlorophyll climatology (log10 of the concentration, 12 months, with
+// halos) and its interpolation in time (phy/mod_swabs.F90:185-187), allocated by blomgpu_iniswa for the chlorophyll methods; fwbbal's two
+// accumulators (phy/mod_forcing.F90:128-132, restart variables), allocated when sprfac is set.  A table of their own behind V.b (V.e[E_chl10]):
+// no member of the view that today's kernels read moves.  On the host the id of such a field is FID_STEPEND + its number (ctx_real_ptr).
+#define BLOM_STEPEND_REAL_FIELDS(X) X(chl10c, 12) X(chl10, 1) X(eiacc, 1) X(pracc, 1)
+
 #define BLOM_INT_FIELDS(X) X(ip, 1) X(iu, 1) X(iv, 1) X(iq, 1) X(kfpla, 2) X(kming, 1) X(cppm_sti, 1) X(cppm_stj, 1) X(mpack, 1) \
   /* mod_difest: kmax, kfil, msku, mskv (mod_difest.F90:97-100) */ X(dfe_kmax, 1) X(dfe_kfil, 1) X(msku, K) X(mskv, K)
 
@@ -150,7 +156,20 @@ enum Ben02FieldId {
 #undef X
       NF_BEN02
 };
+enum StepEndFieldId {
+#define X(name, lev) E_##name,
+  BLOM_STEPEND_REAL_FIELDS(X)
+#undef X
+      NF_STEPEND
+};
 constexpr int FID_BEN02 = NF_REAL + 2;      // (NF_REAL and NF_REAL + 1 name the work space and diaacc's accumulators: ctx_locate_ptr)
+
+constexpr int FID_STEPEND = FID_BEN02 + NF_BEN02;
+constexpr int kStepEndLevels[NF_STEPEND] = {
+#define X(name, lev) lev,
+  BLOM_STEPEND_REAL_FIELDS(X)
+#undef X
+};
 
 // ---- scalar options (namelist-type module variables of the reference) ----------------
 struct Params {
@@ -233,6 +252,7 @@ struct DevView {
   double *wk2d;
   int nwk;
   PtrTable<double, NF_BEN02> b;   // the forced ocean-ice experiment's planes (BLOM_BEN02_REAL_FIELDS); null until blomgpu_inifrc_ben02
+  PtrTable<double, NF_STEPEND> e; // updswa's and fwbbal's fields (BLOM_STEPEND_REAL_FIELDS); null until blomgpu_iniswa / sprfac = 1
 };
 #define WK(V, w) (global_ptr((V).wk) + (size_t)(w) * (V).kk * (V).nplane)
 #define WK2(V, w) (global_ptr((V).wk2d) + (size_t)(w) * (V).nplane)
@@ -515,6 +535,19 @@ struct blomgpu_ctx {
   // a context declares one of the two families
   bool ben02_declared = false;
   double *ben02_planes = nullptr;
+  // ---- the end of blom_step (stage_stepend.hip; api.hip: g_stepend_opts) ----
+  bool step_time = false;                      // blomgpu_step advances mod_time's nday_of_year, xmi, l1mi..l5mi in front of every step (phy/mod_time.F90:182-219)
+  int swamth = 0;                              // mod_swabs' swamth: 0 none declared, then SWA_* below; jwtype, chlopt (phy/mod_swabs.F90:92-94)
+  int jwtype = 0;
+  std::string chlopt = "climatology";
+  bool swa_ready = false;                      // blomgpu_iniswa has run for the present swamth
+  double *swa_lut = nullptr;                   // chlorophyll_ohl03: a1_lut a2_lut b1_lut b2_lut, 401 entries each (:188-189)
+  double swa_log10chl_min = 0., swa_dlog10chl = 0.;   // (:190)
+  bool sprfac = false;                         // mod_forcing's sprfac (phy/mod_forcing.F90:58); prfac: the correction factor fwbbal maintains
+  double prfac = 1.;
+  bool chkvar = false;                         // blomgpu_step ends every step with chkvar (phy/mod_blom_step.F90:252)
+  double *fwb_buf = nullptr;                   // fwbbal's year end: [0..1] totei, totpr, then the row sums of both
+  unsigned long long *chk_dev = nullptr;       // chkvar's words: [0] the error word, [1] the key of the first hit in the serial reference's order
   int dia_alarm = -1;                          // blomgpu_dia_alarm: alarm_phy(1) as the host declared it, 0 | 1; -1: undeclared
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
@@ -589,12 +622,26 @@ int ben02_reset_tda(blomgpu_ctx *);                                             
 void ben02_free(blomgpu_ctx *);
 int st_sfcstr_ben02(blomgpu_ctx *);                                              // ben02/mod_sfcstr_ben02.F90:35-72
 int st_thermf_ben02(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);   // ben02/mod_thermf_ben02.F90:65-703
-// a registered real field by its host id: the field table, or a plane of the forced ocean-ice experiment
+// stage_stepend.hip: the end of blom_step -- updswa (phy/mod_swabs.F90:611-732) behind getfrc, fwbbal (phy/mod_forcing.F90:361-441) behind
+// diaacc, chkvar (phy/mod_chkvar.F90:77-141) last; step_time (phy/mod_time.F90:182-219) on the host in front of the step
+enum { SWA_NONE = 0, SWA_TOP_LAYER, SWA_JERLOV, SWA_MA94, SWA_OHL03, SWA_SPATIAL };
+static inline bool swa_chlorophyll(const blomgpu_ctx *c) { return c->swamth == SWA_MA94 || c->swamth == SWA_OHL03; }
+int stepend_iniswa(blomgpu_ctx *);                                               // phy/mod_swabs.F90:216-609
+int stepend_set_sprfac(blomgpu_ctx *);                                           // phy/mod_forcing.F90:345-357
+int stepend_step_time(blomgpu_ctx *, int ns1);                                   // phy/mod_time.F90:193-217 with nstep = ns1
+int stepend_step_check(blomgpu_ctx *);                                           // what blomgpu_step refuses before its first step
+int stepend_check_errors(blomgpu_ctx *);                                         // chkvar's words: the reference's line, or 0
+void stepend_free(blomgpu_ctx *);
+int st_updswa(blomgpu_ctx *);
+int st_fwbbal(blomgpu_ctx *);
+int st_chkvar(blomgpu_ctx *, int nn);
+// a registered real field by its host id: the field table, a plane of the forced ocean-ice experiment, or a field of the step's end
 static inline double *ctx_real_ptr(const blomgpu_ctx *c, int id) {
   if (id < FID_BEN02) return c->h.f[id];
+  if (id >= FID_STEPEND) return c->h.e[id - FID_STEPEND];
   return c->ben02_planes ? c->ben02_planes + (size_t)(id - FID_BEN02) * c->h.nplane : nullptr;
 }
-static inline int ctx_real_nlev(const blomgpu_ctx *c, int id) { return id < FID_BEN02 ? c->nlev_real[id] : 1; }
+static inline int ctx_real_nlev(const blomgpu_ctx *c, int id) { return id < FID_BEN02 ? c->nlev_real[id] : id >= FID_STEPEND ? kStepEndLevels[id - FID_STEPEND] : 1; }
 // halo.hip: xcsum of nb planes at once, the sums left on the device in out[0..nb-1]; mask[q] == nullptr: ips
 int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int *const *masks, double *rows, double *out);
 int st_niw_ke_tendency(blomgpu_ctx *, int m, int mm);                           // stage_difest.hip

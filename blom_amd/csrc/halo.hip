@@ -429,10 +429,15 @@ int ctx_locate_ptr(const blomgpu_ctx *c, const double *p, size_t *offset) {
   // the planes of the forced ocean-ice experiment (sfcstr_ben02 exchanges hicem): one allocation, id FID_BEN02
   if (const double *b = c->ben02_planes)
     if (p >= b && p < b + (size_t)NF_BEN02 * c->h.nplane) { *offset = (size_t)(p - b); return FID_BEN02; }
+  // updswa's and fwbbal's fields (stage_stepend.hip; a host exchanges the halos of chl10c): one allocation each, id FID_STEPEND + e
+  for (int e = 0; e < NF_STEPEND; e++)
+    if (const double *b = c->h.e[e])
+      if (p >= b && p < b + (size_t)kStepEndLevels[e] * c->h.nplane) { *offset = (size_t)(p - b); return FID_STEPEND + e; }
   return -1;
 }
 static inline double *located_base(const blomgpu_ctx *c, int fid) {
   size_t na = 0;
+  if (fid >= FID_STEPEND) return c->h.e[fid - FID_STEPEND];
   return fid == FID_BEN02 ? c->ben02_planes : fid == NF_REAL + 1 ? dia_acc_span(c, &na) : fid == NF_REAL ? c->h.wk : c->h.f[fid];
 }
 

@@ -12,7 +12,7 @@
 // so that thermf_cesm is four launches up to 32 planes in the batch (ntr' <= 31, 29 with srxbal; two more per further 32).  The per-step scalars (w1; y, m1..m5, ntld of :74-84) are
 // formed on the host and passed as kernel arguments.  swtfrz is the stand-alone driver's (drivers/nocoupler/mod_swtfrz.F:
 // atf*s+btf+ctf*p with inieos' coefficients for 'cesm', phy/mod_eos.F90:133-136); the NUOPC driver's form needs CESM's share code.
-// Not built: the coupler fields no device stage reads (hmat slp abswnd lamult lasl ustokes vstokes atm*), updswa.
+// Not built: the coupler fields no device stage reads (hmat slp abswnd lamult lasl ustokes vstokes atm*).
 // Roofline: HBM, ~45 two-dimensional planes (plus 2 kk + 2 (kk+1) levels under the hybrid coordinate); launch-bound at channel size.
 #include "blomgpu_internal.h"
 #include "pow_libm.h"

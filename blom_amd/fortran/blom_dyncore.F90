@@ -257,6 +257,7 @@ contains
       ! vcoord_type = 'cntiso_hybrid' or 'plevel', phy/mod_blom_step.F90:126-233 as far as the device library has it
       ! (DESIGN.md 3h; difest_*_hybrid and thermf are left out: what they produce stays as uploaded)
       call init_fluxes(m,n,mm,nn,k1m,k1n)
+      call updswa()                                ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
       call tmsmt1(nn)
       call ale_regrid_remap(m,n,mm,nn,k1m,k1n)
       call cmnfld2(m,n,mm,nn,k1m,k1n)
@@ -279,6 +280,8 @@ contains
       call tmsmt2(m,mm,nn,k1m)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
       call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
+      call fwbbal(m,n,mm,nn,k1m,k1n)               ! :242 (nothing without sprfac)
+      call chkvar(m,n,mm,nn,k1m,k1n)               ! :252 (nothing without the option chkvar)
       call gpu_set('delt1', baclin+baclin)
       return
     end if
@@ -286,6 +289,7 @@ contains
       ! phy/mod_blom_step.F90:96-253 for isopyc_bulkml, every stage the device library has (DESIGN.md 3i); of difest_isobml the
       ! part in front of the diffusivity estimates
       call init_fluxes(m,n,mm,nn,k1m,k1n)
+      call updswa()                                ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
       call tmsmt1(nn)
       call cmnfld2(m,n,mm,nn,k1m,k1n)
       call difest_isobml(m,n,mm,nn,k1m,k1n)
@@ -306,10 +310,13 @@ contains
       call tmsmt2(m,mm,nn,k1m)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
       call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
+      call fwbbal(m,n,mm,nn,k1m,k1n)               ! :242 (nothing without sprfac)
+      call chkvar(m,n,mm,nn,k1m,k1n)               ! :252 (nothing without the option chkvar)
       call gpu_set('delt1', baclin+baclin)
       return
     end if
     call init_fluxes(m,n,mm,nn,k1m,k1n)
+    call updswa()                                  ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
     call tmsmt1(nn)
     call halo_cmnfld2(n)
     call halo_difest(nn)
@@ -328,6 +335,8 @@ contains
     call pbcor2(m,n,mm,nn,k1m,k1n)
     call tmsmt2(m,mm,nn,k1m)
     call diaacc(m,n,mm,nn,k1m,k1n)                 ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
+    call fwbbal(m,n,mm,nn,k1m,k1n)                 ! :242 (nothing without sprfac)
+    call chkvar(m,n,mm,nn,k1m,k1n)                 ! :252 (nothing without the option chkvar)
     call gpu_set('delt1', baclin+baclin)           ! phy/mod_blom_step.F90:300
   end subroutine blom_step
 

@@ -125,6 +125,24 @@ module mod_blomgpu
       import :: c_ptr, c_int
       type(c_ptr), value :: c
     end function
+    integer(c_int) function blomgpu_iniswa(c) bind(C, name='blomgpu_iniswa')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_updswa(c) bind(C, name='blomgpu_updswa')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_fwbbal(c, m, n, mm, nn, k1m, k1n) bind(C, name='blomgpu_fwbbal')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), value :: m, n, mm, nn, k1m, k1n
+    end function
+    integer(c_int) function blomgpu_chkvar(c, m, n, mm, nn, k1m, k1n) bind(C, name='blomgpu_chkvar')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), value :: m, n, mm, nn, k1m, k1n
+    end function
     integer(c_int) function blomgpu_cesm_nflxdi(c, out) bind(C, name='blomgpu_cesm_nflxdi')
       import :: c_ptr, c_int
       type(c_ptr), value :: c
@@ -292,6 +310,7 @@ module mod_blomgpu
   public :: gpu_dia_select, gpu_dia_get, gpu_dia_finalize, gpu_dia_reset, gpu_dia_nacc, gpu_dia_name_ext, gpu_dia_alarm
   public :: inifrc_cesm, getfrc_cesm, gpu_cesm_nflxdi, gpu_upload_level
   public :: inifrc_ben02, gpu_ben02_ntda, gpu_ben02_reset_tda
+  public :: iniswa, updswa, fwbbal, chkvar
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
 
@@ -670,6 +689,52 @@ contains
     integer(c_int) :: n(48)
     call gpu_check(blomgpu_cesm_nflxdi(ctx, n), 'gpu_cesm_nflxdi')
     nflxdi = int(n)
+  end subroutine
+  ! The end of blom_step (phy/mod_blom_step.F90:96-252), each with the reference's call line; updswa, fwbbal and chkvar return at once
+  ! unless their options (swamth, sprfac, chkvar) have declared them.
+  ! iniswa (phy/mod_swabs.F90:216): for the method gpu_set('swamth', ...) names.  chl: the monthly chlorophyll concentration the
+  ! reference reads from ccfile, for the chlorophyll methods -- log10 where it is positive inside the tile (:391-402), uploaded as
+  ! chl10c, halos updated (:405).
+  subroutine iniswa(chl)
+    real(8), intent(in), optional :: chl(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,12)
+    real(8), allocatable :: c10(:,:,:)
+    integer :: i, j, k
+    call gpu_check(blomgpu_iniswa(ctx), 'iniswa')
+    if (.not. present(chl)) return
+    allocate(c10(1-nbdy:idm+nbdy,1-nbdy:jdm+nbdy,12))
+    c10 = chl
+    do k = 1, 12
+      do j = 1, jdm
+        do i = 1, idm
+          if (c10(i,j,k) > 0._8) c10(i,j,k) = log10(c10(i,j,k))
+        end do
+      end do
+    end do
+    call gpu_upload('chl10c', c10, 12)
+    call gpu_halo('chl10c', 1, 1, 12, nbdy, nbdy, 1)
+    deallocate(c10)
+  end subroutine
+  ! updswa (phy/mod_swabs.F90:611); with csdiag the four checksum lines of :722-730, which the chlorophyll methods alone reach
+  subroutine updswa(csdiag)
+    logical, intent(in), optional :: csdiag
+    integer(c_int) :: nl, ii_
+    call gpu_check(blomgpu_updswa(ctx), 'updswa')
+    if (.not. present(csdiag)) return
+    if (.not. csdiag) return
+    if (blomgpu_field_info(ctx, cz('chl10'), nl, ii_) /= 0) return
+    if (mnproc == 1) write (*,*) 'updswa:'
+    call gpu_chksum('swfc1', 1, 1, 'swfc1')
+    call gpu_chksum('swfc2', 1, 1, 'swfc2')
+    call gpu_chksum('swal1', 1, 1, 'swal1')
+    call gpu_chksum('swal2', 1, 1, 'swal2')
+  end subroutine
+  subroutine fwbbal(m,n,mm,nn,k1m,k1n)              ! phy/mod_forcing.F90:361
+    integer, intent(in) :: m,n,mm,nn,k1m,k1n
+    call gpu_check(blomgpu_fwbbal(ctx, m, n, mm, nn, k1m, k1n), 'fwbbal')
+  end subroutine
+  subroutine chkvar(m,n,mm,nn,k1m,k1n)              ! phy/mod_chkvar.F90:77
+    integer, intent(in) :: m,n,mm,nn,k1m,k1n
+    call gpu_check(blomgpu_chkvar(ctx, m, n, mm, nn, k1m, k1n), 'chkvar')
   end subroutine
   ! The forced ocean-ice experiment (expcnf = 'ben02clim' / 'ben02syn' / 'single_column').  inifrc_ben02 declares that its forcing
   ! exists: until it has been called sfcstr and thermf refuse these experiments.  asflux stays the host's: it reads the five _tda planes

@@ -6,6 +6,7 @@ meaning (phy/mod_blom_step.F90:89-253).  There is no CPU fallback: if the HIP li
 missing or no device is present, construction raises.
 """
 import ctypes as C
+import math
 import os
 import numpy as np
 
@@ -206,6 +207,32 @@ class BlomGpu:
     def ben02_reset_tda(self):
         """the five _tda planes and ntda to zero, as asflux leaves them -- blomgpu_ben02_reset_tda"""
         self._chk(self.lib.blomgpu_ben02_reset_tda(self.ctx))
+
+    # -- the end of blom_step: updswa, fwbbal, chkvar (options "swamth", "sprfac", "chkvar"; the clock: "step_time") --------
+    def iniswa(self, chl=None):
+        """iniswa (phy/mod_swabs.F90:216-609) for the method set("swamth", ...) names -- blomgpu_iniswa.  chl: for the chlorophyll methods,
+        the monthly concentration (12, nj, ni) with halos; uploaded as chl10c = log10(chl) where chl is positive, as the reference's
+        array holds it after iniswa."""
+        self._chk(self.lib.blomgpu_iniswa(self.ctx))
+        self._info = {}
+        if chl is not None:
+            a = np.array(chl, dtype=np.float64)
+            pos = a > 0.0
+            a[pos] = [math.log10(v) for v in a[pos]]      # (the C library's log10, element by element: the reference's call)
+            self.put("chl10c", a)
+
+    def updswa(self):
+        """updswa (phy/mod_swabs.F90:611-732); returns at once unless a chlorophyll method is declared -- blomgpu_updswa"""
+        self._chk(self.lib.blomgpu_updswa(self.ctx))
+
+    def fwbbal(self, m, n, mm, nn, k1m, k1n):
+        """fwbbal (phy/mod_forcing.F90:361-441); returns at once unless sprfac is set -- blomgpu_fwbbal"""
+        self._chk(self.lib.blomgpu_fwbbal(self.ctx, m, n, mm, nn, k1m, k1n))
+
+    def chkvar(self, m, n, mm, nn, k1m, k1n):
+        """chkvar (phy/mod_chkvar.F90:77-141): raises BlomGpuError with the reference's line for the first NaN or Inf in dp, temp, saln of
+        time level n; returns at once unless the option chkvar is set -- blomgpu_chkvar"""
+        self._chk(self.lib.blomgpu_chkvar(self.ctx, m, n, mm, nn, k1m, k1n))
 
     def exp(self, x):
         """exp() as the kernels evaluate it (blom_amd/csrc/exp_libm.h), elementwise."""

@@ -86,6 +86,26 @@ FULL_STAGES_LIVE_BEN02 = _ben02(FULL_STAGES_LIVE)
 HYBRID_STAGES_BEN02 = _ben02(HYBRID_STAGES, thermf_after="momtum")
 
 
+# The end of blom_step, once its options declare it (BlomGpu.set "swamth" + iniswa, "sprfac", "chkvar"): updswa behind getfrc
+# (phy/mod_blom_step.F90:122), fwbbal behind diaacc (:242), chkvar last (:252).  Each stage returns at once unless declared, so the tuples
+# may carry all three.  step_time (:99) is the host's in a stage-by-stage step (stepend_ref.step_time restates it; BlomGpu.step does it
+# itself with the option "step_time").
+def with_step_end(stages):
+    out = []
+    for s in stages:
+        out.append(s)
+        if s == ("getfrc_cesm" if "getfrc_cesm" in stages else "init_fluxes"):
+            out.append("updswa")
+    return tuple(out) + ("fwbbal", "chkvar")
+
+
+FULL_STAGES_LIVE_END = with_step_end(FULL_STAGES_LIVE)
+FULL_STAGES_LIVE_CESM_END = with_step_end(FULL_STAGES_LIVE_CESM)
+HYBRID_STAGES_CESM_END = with_step_end(HYBRID_STAGES_CESM)
+FULL_STAGES_LIVE_BEN02_END = with_step_end(FULL_STAGES_LIVE_BEN02)
+HYBRID_STAGES_BEN02_END = with_step_end(HYBRID_STAGES_BEN02)
+
+
 def dyncore_step(be, nstep, baclin, stages=DYNCORE_STAGES, hook=None):
     """Advance backend `be` from step count nstep to nstep+1.  `hook(stage, sextuple)` is
     called before each stage (tests use it to snapshot stage inputs)."""

@@ -390,6 +390,39 @@ int  blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
 int  blomgpu_dia_alarm(blomgpu_ctx *, int alarm);
 int  blomgpu_ale_remap_diazlv(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 
+/* The end of blom_step (phy/mod_blom_step.F90:96-252).  Everything here is off until an option declares it; an undeclared context steps
+ * as before.  The options are set like every other (blomgpu_set_int / _real / _str); blomgpu_option_name does not list them.
+ *
+ * "step_time" = 1: blomgpu_step does step_time (phy/mod_time.F90:182-219) on the host in front of every step.  With ns1 the incremented
+ *   step number, sd = "nstep_in_day" and nd = "nday_in_year": where ns1 % sd == 0 the day moves on, nday_of_year = nday_of_year % nd + 1;
+ *   then xmi = (nday_of_year - 1 + (ns1 % sd)/double(sd))*12./double(nd), l3mi = int(xmi) + 1, xmi = xmi - (l3mi - 1), and l1mi l2mi
+ *   l4mi l5mi the months around l3mi -- in double, in the reference's order, written where the setters write "nday_of_year", "xmi",
+ *   "l1mi" .. "l5mi".  The day rule equals date_offset + set_day_of_year inside a year and across a year's end whose successor has the
+ *   same length: a host on a leap calendar ends its call at the year's last step and sets "nday_in_year" in between.  Refused with
+ *   nstep_in_day < 1 or nday_in_year < 1.  One blomgpu_step of nstep_in_cpl steps then equals that many steps of the reference.
+ * blomgpu_iniswa: iniswa (phy/mod_swabs.F90:216-609) for the method "swamth" names -- "top-layer" and "jerlov" ("jwtype" 1..5) fill swfc1
+ *   swfc2 swal1 swal2 at the owned wet p-points; "spatial_frac_attlen" leaves the four planes to the host's uploads; "chlorophyll_ma94"
+ *   and "chlorophyll_ohl03" ("chlopt" = "climatology") create the fields "chl10c" (12 levels: log10 of the monthly chlorophyll
+ *   concentration, halos included, uploaded by name) and "chl10", and the second builds Ohlmann's four 401-entry tables.  Another word,
+ *   a jwtype outside 1..5 and another chlopt are refused in the reference's words.
+ * blomgpu_updswa: updswa (:611-732) -- chl10 interpolated in time from chl10c with l1mi..l5mi and xmi, clamped to [-2, 1], then the
+ *   four planes from Morel and Antoine's polynomials or Ohlmann's table; returns at once for the other methods.  blomgpu_step runs it
+ *   behind getfrc (phy/mod_blom_step.F90:122) while a chlorophyll method is declared.
+ * blomgpu_fwbbal: fwbbal (phy/mod_forcing.F90:361-441).  "sprfac" = 1 creates and zeroes the fields "eiacc" and "pracc" (restart
+ *   variables: up and down by name) and sets "prfac" = 1 (inivar_forcing, :345-357); it creates "ipwocn" where the context has none
+ *   and expects an upload.  Each call accumulates eva + fmltfz and lip + sop + rnf + rfi times baclin; when nday_of_year == 1 and
+ *   nstep % nstep_in_day == 0 it weights both with scp2, sums them under ipwocn in xcsum's order, sets prfac = -prfac*totei/totpr
+ *   (blomgpu_get_real "prfac") and zeroes both.  blomgpu_step runs it behind diaacc (:242) while sprfac is set.
+ * blomgpu_chkvar: chkvar (phy/mod_chkvar.F90:77-141) with "chkvar" = 1 -- NaN (a /= a) or Inf (a*0 /= 0) in dp, temp or saln of time
+ *   level n at an owned wet p-point fails the call with the reference's line and global indices, "blom: chkvar: dp is NaN at (i =   7,
+ *   j =  12, k =   3)": of several hits the one the serial reference meets first (j, then k, then i, then dp NaN, dp Inf, temp NaN,
+ *   temp Inf, saln NaN, saln Inf).  blomgpu_step runs it last in every step (:252) and reads its words back every "check_period" steps.
+ * "use_graph" = 1 beside any of the four is refused: their per-step scalars are kernel arguments. */
+int  blomgpu_iniswa(blomgpu_ctx *);
+int  blomgpu_updswa(blomgpu_ctx *);
+int  blomgpu_fwbbal(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
+int  blomgpu_chkvar(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
+
 /* Generic dispatcher over the entries above ("advect", "tmsmt1", ...). */
 int  blomgpu_stage(blomgpu_ctx *, const char *stage, int m, int n, int mm, int nn,
                    int k1m, int k1n);
