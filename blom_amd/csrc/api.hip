@@ -292,6 +292,11 @@ static const Opt g_stepend_opts[] = {
   {"sprfac", O_BOOL, IN_C(sprfac), 0, nullptr, [](blomgpu_ctx *c) { (void)stepend_set_sprfac(c); }},
   {"prfac", O_REAL, IN_C(prfac), READABLE},
 };
+// mod_budget inside blomgpu_step (stage_budget.hip), likewise unlisted: with cnsvdi = 1 (the listed table's) the step runs budget_sums'
+// seven calls and budget_output's sums where blom_step has them and keeps a record per step
+static const Opt g_budget_opts[] = {
+  CI(budget_step),
+};
 #undef IN_P
 #undef IN_C
 #undef PR
@@ -309,6 +314,8 @@ static const Opt *find_opt(std::string_view name, unsigned kinds) {      // kind
   for (const Opt &o : g_cesm_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   for (const Opt &o : g_stepend_opts)
+    if (name == o.name && (kinds >> o.kind & 1)) return &o;
+  for (const Opt &o : g_budget_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   return nullptr;
 }
@@ -472,6 +479,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   cesm_free(c);
   ben02_free(c);
   stepend_free(c);
+  budget_free(c);
   if (c->ale_plevel) (void)hipFree(c->ale_plevel);
   if (c->arc_strip) (void)hipFree(c->arc_strip);
   if (c->xcsum_buf) (void)hipFree(c->xcsum_buf);
@@ -776,9 +784,28 @@ int blomgpu_difest_isobml(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m,
   return st_difest_isobml(c, m, n, mm, nn);
 }
 int blomgpu_budget_sums(blomgpu_ctx *c, int ncall, int n, int nn) { ctx_sync_view(c); return st_budget_sums(c, ncall, n, nn); }
-// which: 0 sdp, 1 tdp, 2 trdp, 3 tkedp (phy/mod_budget.F90:50-59)
+int blomgpu_budget_init(blomgpu_ctx *c) { ctx_sync_view(c); return st_budget_init(c); }
+int blomgpu_budget_output(blomgpu_ctx *c, int m) { ctx_sync_view(c); return st_budget_output(c, m); }
+int blomgpu_budget_steps(blomgpu_ctx *c, int *first, int *count) {
+  if (!c || !first || !count) return ctx_fail(c, "blomgpu_budget_steps: null argument");
+  return budget_steps(c, first, count);
+}
+int blomgpu_budget_mass0(blomgpu_ctx *c, double *mass0) { return budget_mass0(c, mass0); }
+int blomgpu_budget_record(blomgpu_ctx *c, int nstep, double *rec) {
+  if (!c || !rec) return ctx_fail(c, "blomgpu_budget_record: null argument");
+  return budget_record(c, nstep, rec);
+}
+int blomgpu_budget_files(blomgpu_ctx *c, int *mask) {
+  if (!c || !mask) return ctx_fail(c, "blomgpu_budget_files: null argument");
+  return budget_files(c, mask);
+}
+int blomgpu_budget_line(blomgpu_ctx *c, int nstep, int file, double *terms, int *nterms) {
+  if (!c || !terms || !nterms) return ctx_fail(c, "blomgpu_budget_line: null argument");
+  return budget_line(c, nstep, file, terms, nterms);
+}
+// which: 0 sdp, 1 tdp, 2 trdp, 3 tkedp, 4 glsdp (phy/mod_budget.F90:50-59)
 int blomgpu_budget_get(blomgpu_ctx *c, int which, int ncall, int n, double *v) {
-  if (which < 0 || which > 3 || ncall < 1 || ncall > 7 || n < 1 || n > 2) return ctx_fail(c, "blomgpu_budget_get: index out of range");
+  if (which < 0 || which > 4 || ncall < 1 || ncall > 7 || n < 1 || n > 2) return ctx_fail(c, "blomgpu_budget_get: index out of range");
   *v = c->budget[which][ncall - 1][n - 1];
   return 0;
 }
@@ -963,7 +990,12 @@ int blomgpu_halo_difest(blomgpu_ctx *c, int nn) {     // phy/mod_difest.F90:750-
   X(ale_regrid_remap, blomgpu_ale_regrid_remap(ALL6)) X(ale_forcing, blomgpu_ale_forcing(ALL6))                                   \
   X(cmnfld_bfsqi_ale, blomgpu_cmnfld_bfsqi_ale(ALL6)) X(ale_vdifft, blomgpu_ale_vdifft(ALL6)) X(ale_vdiffm, blomgpu_ale_vdiffm(ALL6)) \
   X(diaacc, blomgpu_diaacc(ALL6)) X(ale_remap_diazlv, blomgpu_ale_remap_diazlv(ALL6)) X(getfrc_cesm, blomgpu_getfrc_cesm(c)) \
-  X(updswa, blomgpu_updswa(c)) X(fwbbal, blomgpu_fwbbal(ALL6)) X(chkvar, blomgpu_chkvar(ALL6))
+  X(updswa, blomgpu_updswa(c)) X(fwbbal, blomgpu_fwbbal(ALL6)) X(chkvar, blomgpu_chkvar(ALL6))                                    \
+  /* mod_budget's calls by their number (phy/mod_blom_step.F90:96-230: 1..5 on level n, 6 and 7 on level m) and budget_output (:245) */ \
+  X(budget_sums1, blomgpu_budget_sums(c, 1, n, nn)) X(budget_sums2, blomgpu_budget_sums(c, 2, n, nn))                           \
+  X(budget_sums3, blomgpu_budget_sums(c, 3, n, nn)) X(budget_sums4, blomgpu_budget_sums(c, 4, n, nn))                           \
+  X(budget_sums5, blomgpu_budget_sums(c, 5, n, nn)) X(budget_sums6, blomgpu_budget_sums(c, 6, m, mm))                           \
+  X(budget_sums7, blomgpu_budget_sums(c, 7, m, mm)) X(budget_output, blomgpu_budget_output(c, m))
 enum StageId {
 #define X(nm, call) S_##nm,
   BLOM_STAGES(X)
@@ -1018,6 +1050,14 @@ static int step_sequence(STAGE_ARGS) {
         if (failed) c->tmsmt1_done_ahead = false;
       }
     } leave{c};
+    // mod_budget (option budget_step with cnsvdi; stage_budget.hip): budget_sums' calls by their number where blom_step has them (:96,
+    // :132/:156, :159/:177, :183/:205, :215, :224, :230), each behind the last writer of dp, temp, saln, trc of its level on the context's
+    // stream.  What runs on the second stream beside them writes none of the four (momtum's viscous chain: its own work space; diapfl's
+    // momentum mixing: u, v, dpu, dpv) but for what raises updtrc_on_side -- updtrc's ideal-age step (a tracer that can be tracer 1) and,
+    // with phys_dag bit 8, mxlayr's copy-back clamp (saln and the tracers) -- which call 5 joins (tests/test_budget_sets.py).  pbcor2 stores its
+    // level m itself with the option on (stage_pbcor_tile.hip), so that call 6 reads it where the reference does.
+    const auto bud = [&](int ncall) { return st_budget_instep(c, ncall, ncall <= 5 ? nn : mm); };
+    if (int rc = bud(1)) return rc;                                         // :96 (blomgpu_step has advanced the clock already: the sums read no clock scalar)
     if (ale) {
       for (const StageId st : seq_ale) {
         if (c->tmsmt1_done_ahead && st == S_tmsmt1) { c->tmsmt1_done_ahead = false; continue; }
@@ -1025,6 +1065,8 @@ static int step_sequence(STAGE_ARGS) {
         if (frc && st == S_pgforc)
           if (int rc = stage(S_sfcstr)) return rc;
         if (int rc = stage(st)) return rc;
+        if (const int ncall = st == S_ale_regrid_remap ? 2 : st == S_diffus ? 3 : st == S_ale_vdiffm ? 4 : st == S_updtrc ? 5 : st == S_pbcor2 ? 6 : st == S_tmsmt2 ? 7 : 0)
+          if (int rc = bud(ncall)) return rc;
         if (cesm && st == S_init_fluxes)
           if (int rc = stage(S_getfrc_cesm)) return rc;
         if (swa && st == S_init_fluxes)
@@ -1065,6 +1107,13 @@ static int step_sequence(STAGE_ARGS) {
       if (frc && st == S_pgforc)
         if (int rc = stage(S_sfcstr)) return rc;
       if (int rc = stage(run)) return rc;
+      if (const int ncall = st == S_diffus ? 2 : st == S_convec ? 3 : st == S_diapfl ? 4 : st == S_updtrc ? 5 : st == S_pbcor2 ? 6 : st == S_tmsmt2 ? 7 : 0) {
+        if (ncall == 5 && budget_on(c) && c->seq.updtrc_on_side) {        // k_idlage_step may write tracer 1, k_mxl_clamp writes saln and the tracers
+          c->seq.updtrc_on_side = false;
+          if (ctx_side_done(c, 9) || ctx_side_join(c, 9)) return 1;
+        }
+        if (int rc = bud(ncall)) return rc;
+      }
       if (cesm && st == S_init_fluxes)
         if (int rc = stage(S_getfrc_cesm)) return rc;
       if (swa && st == S_init_fluxes)
@@ -1094,6 +1143,7 @@ static int step_sequence(STAGE_ARGS) {
   // device for blomgpu_step's check, like every stage of the sequence
   if (c->sprfac)
     if (int rc = st_fwbbal(c)) return rc;
+  if (int rc = st_budget_output_instep(c)) return rc;                       // :245
   if (c->chkvar) {
     c->seq.defer_checks = true;
     const int rc = st_chkvar(c, nn);
@@ -1117,6 +1167,9 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
   if (ben02_on(c) && c->use_graph)
     return ctx_fail(c, "blomgpu_step: the forced ocean-ice experiment's per-step scalars are kernel arguments, which a captured graph would freeze (set use_graph = 0)");
   if (int rc = stepend_step_check(c)) return rc;
+  // mod_budget (stage_budget.hip): the records of this call's steps on the device; one copy brings them back in front of the last check
+  const int ns0 = *nstep;
+  if (int rc = budget_call_begin(c, ns0, nsteps)) return rc;
   // (the stage entries outside this call keep the flux diagnostics current, whichever way it returns)
   struct FluxDiagBack { blomgpu_ctx *c; ~FluxDiagBack() { c->flux_diag = true; } } flux_diag_back{c};
   // the row test walks the selection: once per call, the selection cannot change inside it
@@ -1131,6 +1184,7 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     if (c->step_time)
       if (int rc = stepend_step_time(c, ns + 1)) return rc;
     ctx_sync_view(c);
+    budget_call_slot(c, it);
     // (not while diavfl's group is selected: its dp(km) - dpold(km) needs the dpold the PREVIOUS step's tmsmt1 left, and the fold
     // would have tmsmt2 overwrite it in front of diaacc.  The cost of the launch it brings back: DESIGN 3.13)
     c->tmsmt1_ahead = !c->use_graph && !c->csdiag && it < nsteps - 1 && c->tmsmt_ahead && !dia_reads_dpold(c);
@@ -1143,7 +1197,8 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     // sequence writes these arrays inside fused kernels (eddtra_ale, ndiff) and keeps today's form.
     c->flux_diag = !(flux_diag_lazy && !c->use_graph && !c->csdiag && it < nsteps - 2);
     // (the hybrid-coordinate sequence too: the engine's status of ale_regrid_remap stays on the device until the check below)
-    bool graph = c->use_graph && !c->timing && !c->tiling.multi() && c->steps_warm >= 2;
+    // (nor a budgeted step: its record changes every step)
+    bool graph = c->use_graph && !c->timing && !c->tiling.multi() && c->steps_warm >= 2 && !budget_on(c);
     hipGraphExec_t &ge = c->step_graph[ns & 1];
     if (graph && !ge) {
       // Capture; nothing executes while capturing, so on any failure the step is simply run with plain launches.  Both parities are
@@ -1186,6 +1241,8 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     // the stages' error words are sticky: one read-back (a host synchronisation) per check_period steps (every step with
     // csdiag or stage timing, where the reference's stop-in-the-failing-step matters) and at the end of the call
     const int period = (c->csdiag || c->timing) ? 1 : c->check_period;
+    if (it == nsteps - 1)
+      if (int rc = budget_call_fetch(c)) return rc;
     if (it == nsteps - 1 || (it + 1) % period == 0)
       if (int rc = ctx_check_errors(c)) {
         const int first = ns + 1 - (it % period);
@@ -1197,7 +1254,7 @@ int blomgpu_step(blomgpu_ctx *c, int *nstep, int nsteps) {
     if (c->h.P.delt1 != delt2) { c->h.P.delt1 = delt2; c->dirty = true; }   // changes after the first step only
     *nstep = ns + 1;
   }
-  return 0;
+  return budget_call_commit(c, ns0);
 }
 
 // debug (builds with -DBT_PROFILE only record anything): host == nullptr allocates and zeroes nwords of timestamps for the

@@ -297,6 +297,7 @@ struct TileGroup;            // in-process transport: several tiles (contexts) o
 struct RcclComm;             // one process per GPU, neighbour ncclSend/ncclRecv over xGMI
 struct BtGlobal;             // RCCL tiles: the barotropic solve replicated on every rank (comm_rccl.hip)
 struct DiaState;             // the selected time-mean diagnostics and their accumulators (stage_diaacc.hip)
+struct BudgetState;          // mod_budget's records, on the device and on the host (stage_budget.hip)
 // The general tile table of xcspmd (phy/mod_xc.F90:1332-1720), kept for ragged layouts only: tile rows cut differently,
 // tiles shrunk to their sea points, all-land tiles eliminated (ii = 0).  Tensor-product layouts never carry one.
 struct TileTable {
@@ -522,7 +523,9 @@ struct blomgpu_ctx {
   size_t arc_cap = 0;
   double *xcsum_dev = nullptr;                 // sums that stay on the device (thermf), 8 slots
   double *xcsum_buf = nullptr;                 // [0] the sum, [1..jj] the row sums of xcsum
-  double budget[4][7][2] = {};                 // sdp, tdp, trdp, tkedp (ncall, n)
+  double budget[5][7][2] = {};                 // sdp, tdp, trdp, tkedp, glsdp (ncall, n)
+  int budget_step = 0;                         // blomgpu_step runs mod_budget's seven sums and budget_output's sums where blom_step has them (with cnsvdi = 1)
+  BudgetState *bud = nullptr;                  // the records and their buffers; nullptr until a budget routine runs with cnsvdi = 1
   DiaState *dia = nullptr;                     // blomgpu_dia_select's selection; nullptr: none (nothing allocated, nothing launched)
   std::vector<double> dia_edges;               // blomgpu_dia_set_levels: the ddm + 1 edges of the depth levels; empty: the 35-level table
   std::vector<double> dia_sigdia;              // blomgpu_dia_set_sigdia: the kk diagnostic density classes; empty: none (a class name is refused)
@@ -647,7 +650,25 @@ int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int
 int st_niw_ke_tendency(blomgpu_ctx *, int m, int mm);                           // stage_difest.hip
 int st_difest_isobml_pre(blomgpu_ctx *, int m, int n, int mm, int nn);
 int st_difest_isobml(blomgpu_ctx *, int m, int n, int mm, int nn);               // stage_difest_iso.hip: the whole routine
+// stage_budget.hip: mod_budget (phy/mod_budget.F90).  st_budget_sums / _init / _output: for a host that sequences the stages itself (the
+// reference's util planes, the result on the host at once); st_budget_instep / _output_instep: blomgpu_step's, two launches a call, the
+// numbers into the running step's record on the device; budget_call_*: the records of one blomgpu_step call and their one copy to the host
+static inline bool budget_on(const blomgpu_ctx *c) { return c->budget_step && c->cnsvdi; }
 int st_budget_sums(blomgpu_ctx *, int ncall, int n, int nn);
+int st_budget_init(blomgpu_ctx *);
+int st_budget_output(blomgpu_ctx *, int m);
+int st_budget_instep(blomgpu_ctx *, int ncall, int off);
+int st_budget_output_instep(blomgpu_ctx *);
+int budget_call_begin(blomgpu_ctx *, int ns, int nsteps);
+void budget_call_slot(blomgpu_ctx *, int it);
+int budget_call_fetch(blomgpu_ctx *);
+int budget_call_commit(blomgpu_ctx *, int ns);
+int budget_steps(blomgpu_ctx *, int *first, int *count);
+int budget_mass0(blomgpu_ctx *, double *mass0);
+int budget_record(blomgpu_ctx *, int nstep, double *rec);
+int budget_line(blomgpu_ctx *, int nstep, int file, double *terms, int *nterms);
+int budget_files(blomgpu_ctx *, int *mask);
+void budget_free(blomgpu_ctx *);
 int st_barotp(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int st_eddtra(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 int st_eddtra_ale(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);

@@ -287,7 +287,8 @@ int pbcor_tile_launch(blomgpu_ctx *c, int which, int m, int offc, int offf, int 
   }
   // inside blomgpu_step pbcor1 hands S, T and the tracers to diffus through the work space, pbcor2 to tmsmt2
   // (with ltedtp = 'neutral' diffus is halo updates only: nothing to hand to it)
-  const int move = !c->seq.in_sequence || (which == 1 && h.P.ltedtp_opt == 2);
+  // (nor pbcor2 with mod_budget in the step: its call 6 reads dp, temp, saln, trc of level m between the two stages, stage_budget.hip)
+  const int move = !c->seq.in_sequence || (which == 1 && h.P.ltedtp_opt == 2) || (which == 2 && budget_on(c));
   (which == 1 ? c->seq.pbcor1_handed_over : c->seq.pbcor2_handed_over) = !move;
   // pbcor2 inside blomgpu_step: tmsmt2, the next stage, rewrites dp of level m pointwise from what this pass would store and
   // recomputes p: it takes the unscaled thicknesses from the work space and forms the factor itself (stage_simple.hip: k_tmsmt2_fac)

@@ -137,6 +137,7 @@ program blom_dyncore
   ! the step counter starts at nstep1 = nday1*nstep_in_day (its parity decides the time levels and the order of cppm's sweeps)
   nstep = nstep1
   if (advect_cppm) call init_cppm()
+  call budget_init()                               ! phy/mod_blom_init.F90 (nothing unless cnsvdi)
   if (hybrid_coordinate) then
     ! blom_init's cmnfld1 (phy/mod_blom_init.F90): the mixed layer depth the first eddtra and ale_forcing read
     ! with blom_init's time level indices (phy/mod_blom_init.F90:256-261: m = mod(nstep1+1,2)+1, n = mod(nstep1,2)+1)
@@ -256,16 +257,19 @@ contains
     if (hybrid_coordinate) then
       ! vcoord_type = 'cntiso_hybrid' or 'plevel', phy/mod_blom_step.F90:126-233 as far as the device library has it
       ! (DESIGN.md 3h; difest_*_hybrid and thermf are left out: what they produce stays as uploaded)
+      call budget_sums(1,n,nn)                     ! phy/mod_blom_step.F90:96 (nothing unless cnsvdi)
       call init_fluxes(m,n,mm,nn,k1m,k1n)
       call updswa()                                ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
       call tmsmt1(nn)
       call ale_regrid_remap(m,n,mm,nn,k1m,k1n)
+      call budget_sums(2,n,nn)
       call cmnfld2(m,n,mm,nn,k1m,k1n)
       call stage6('halo_difest_hyb',m,n,mm,nn,k1m,k1n)
       call eddtra(m,n,mm,nn,k1m,k1n)
       call advect(m,n,mm,nn,k1m,k1n)
       call pbcor1(m,n,mm,nn,k1m,k1n)
       call diffus(m,n,mm,nn,k1m,k1n)
+      call budget_sums(3,n,nn)
       call sfcstr(m,n,mm,nn,k1m,k1n)
       call pgforc(m,n,mm,nn,k1m,k1n)
       call momtum(m,n,mm,nn,k1m,k1n)
@@ -274,13 +278,18 @@ contains
       call stage6('halo_difest_vert',m,n,mm,nn,k1m,k1n)
       call ale_vdifft(m,n,mm,nn,k1m,k1n)
       call ale_vdiffm(m,n,mm,nn,k1m,k1n)
+      call budget_sums(4,n,nn)
       call updtrc(m,n,mm,nn,k1m,k1n)
+      call budget_sums(5,n,nn)
       call barotp(m,n,mm,nn,k1m,k1n)
       call pbcor2(m,n,mm,nn,k1m,k1n)
+      call budget_sums(6,m,mm)
       call tmsmt2(m,mm,nn,k1m)
+      call budget_sums(7,m,mm)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
       call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
       call fwbbal(m,n,mm,nn,k1m,k1n)               ! :242 (nothing without sprfac)
+      call budget_output(m)                        ! :245
       call chkvar(m,n,mm,nn,k1m,k1n)               ! :252 (nothing without the option chkvar)
       call gpu_set('delt1', baclin+baclin)
       return
@@ -288,6 +297,7 @@ contains
     if (full_physics) then
       ! phy/mod_blom_step.F90:96-253 for isopyc_bulkml, every stage the device library has (DESIGN.md 3i); of difest_isobml the
       ! part in front of the diffusivity estimates
+      call budget_sums(1,n,nn)                     ! phy/mod_blom_step.F90:96 (nothing unless cnsvdi)
       call init_fluxes(m,n,mm,nn,k1m,k1n)
       call updswa()                                ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
       call tmsmt1(nn)
@@ -297,24 +307,32 @@ contains
       call advect(m,n,mm,nn,k1m,k1n)
       call pbcor1(m,n,mm,nn,k1m,k1n)
       call diffus(m,n,mm,nn,k1m,k1n)
+      call budget_sums(2,n,nn)
       call sfcstr(m,n,mm,nn,k1m,k1n)
       call pgforc(m,n,mm,nn,k1m,k1n)
       call momtum(m,n,mm,nn,k1m,k1n)
       call convec(m,n,mm,nn,k1m,k1n)
+      call budget_sums(3,n,nn)
       call diapfl(n,nn,k1n)
+      call budget_sums(4,n,nn)
       call thermf(m,n,mm,nn,k1m,k1n)
       call mxlayr(m,n,mm,nn,k1m,k1n)
       call updtrc(m,n,mm,nn,k1m,k1n)
+      call budget_sums(5,n,nn)
       call barotp(m,n,mm,nn,k1m,k1n)
       call pbcor2(m,n,mm,nn,k1m,k1n)
+      call budget_sums(6,m,mm)
       call tmsmt2(m,mm,nn,k1m)
+      call budget_sums(7,m,mm)
       call cmnfld1(m,n,mm,nn,k1m,k1n)
       call diaacc(m,n,mm,nn,k1m,k1n)               ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
       call fwbbal(m,n,mm,nn,k1m,k1n)               ! :242 (nothing without sprfac)
+      call budget_output(m)                        ! :245
       call chkvar(m,n,mm,nn,k1m,k1n)               ! :252 (nothing without the option chkvar)
       call gpu_set('delt1', baclin+baclin)
       return
     end if
+    call budget_sums(1,n,nn)                     ! phy/mod_blom_step.F90:96 (nothing unless cnsvdi)
     call init_fluxes(m,n,mm,nn,k1m,k1n)
     call updswa()                                  ! phy/mod_blom_step.F90:122 (nothing without a chlorophyll swamth)
     call tmsmt1(nn)
@@ -324,18 +342,25 @@ contains
     call advect(m,n,mm,nn,k1m,k1n)
     call pbcor1(m,n,mm,nn,k1m,k1n)
     call diffus(m,n,mm,nn,k1m,k1n)
+    call budget_sums(2,n,nn)
     call sfcstr(m,n,mm,nn,k1m,k1n)
     call pgforc(m,n,mm,nn,k1m,k1n)
     call momtum(m,n,mm,nn,k1m,k1n)
     call convec(m,n,mm,nn,k1m,k1n)
+    call budget_sums(3,n,nn)
     call diapfl(n,nn,k1n)
+    call budget_sums(4,n,nn)
     call mxlayr_tail(nn,k1n)
     call updtrc(m,n,mm,nn,k1m,k1n)
+    call budget_sums(5,n,nn)
     call barotp(m,n,mm,nn,k1m,k1n)
     call pbcor2(m,n,mm,nn,k1m,k1n)
+    call budget_sums(6,m,mm)
     call tmsmt2(m,mm,nn,k1m)
+    call budget_sums(7,m,mm)
     call diaacc(m,n,mm,nn,k1m,k1n)                 ! phy/mod_blom_step.F90:239 (nothing without gpu_dia_select)
     call fwbbal(m,n,mm,nn,k1m,k1n)                 ! :242 (nothing without sprfac)
+    call budget_output(m)                        ! :245
     call chkvar(m,n,mm,nn,k1m,k1n)                 ! :252 (nothing without the option chkvar)
     call gpu_set('delt1', baclin+baclin)           ! phy/mod_blom_step.F90:300
   end subroutine blom_step

@@ -236,6 +236,32 @@ module mod_blomgpu
       integer(c_int), value :: which, ncall, n
       real(c_double), intent(out) :: v
     end function
+    integer(c_int) function blomgpu_budget_init(c) bind(C, name='blomgpu_budget_init')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_budget_output(c, m) bind(C, name='blomgpu_budget_output')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), value :: m
+    end function
+    integer(c_int) function blomgpu_budget_steps(c, first, count) bind(C, name='blomgpu_budget_steps')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), intent(out) :: first, count
+    end function
+    integer(c_int) function blomgpu_budget_files(c, mask) bind(C, name='blomgpu_budget_files')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+      integer(c_int), intent(out) :: mask
+    end function
+    integer(c_int) function blomgpu_budget_line(c, nstep, file, terms, nterms) bind(C, name='blomgpu_budget_line')
+      import :: c_ptr, c_int, c_double
+      type(c_ptr), value :: c
+      integer(c_int), value :: nstep, file
+      real(c_double), intent(out) :: terms(*)
+      integer(c_int), intent(out) :: nterms
+    end function
     integer(c_int) function blomgpu_sync(c) bind(C, name='blomgpu_sync')
       import :: c_ptr, c_int
       type(c_ptr), value :: c
@@ -301,7 +327,7 @@ module mod_blomgpu
   public :: gpu_init_tile, gpu_upload_global, gpu_upload_int_global, gpu_nlev_global, gpu_rccl_unique_id, gpu_rccl_init, &
             gpu_attach_barotp_global, gpu_rccl_init_table, gpu_attach_barotp_table
   public :: gpu_init, gpu_finalize, gpu_set, gpu_upload, gpu_upload_int, gpu_download, gpu_nlev, &
-            gpu_halo, gpu_chksum, gpu_sync, gpu_xcsum, budget_sums, gpu_budget
+            gpu_halo, gpu_chksum, gpu_sync, gpu_xcsum, budget_init, budget_sums, budget_output, gpu_budget
   public :: stage6
   public :: init_fluxes, tmsmt1, tmsmt2, advect, pbcor1, pbcor2, diffus, pgforc, momtum, &
             diapfl, barotp, eddtra, convec, sfcstr, updtrc, init_cppm, halo_cmnfld2, halo_difest, mxlayr_tail, &
@@ -526,7 +552,36 @@ contains
     integer, intent(in) :: ncall, n, nn
     call gpu_check(blomgpu_budget_sums(ctx, ncall, n, nn), 'budget_sums')
   end subroutine
-  function gpu_budget(which, ncall, n) result(v)   ! sdp/tdp/trdp(ncall,n), phy/mod_budget.F90:50-59
+  subroutine budget_init()                     ! phy/mod_budget.F90:73 (nothing unless gpu_set('cnsvdi', 1))
+    call gpu_check(blomgpu_budget_init(ctx), 'budget_init')
+  end subroutine
+  ! phy/mod_budget.F90:198: the sums sf tf trf of this step into its record, and -- on rank 1, once the step before has a record, the
+  ! reference's nstep > nstep1 + 1 -- the step's line appended to each of salbud tembud tkebud glsbud trcbud trcbudtot that the tracer
+  ! set calls for (:213-268), the numbers blomgpu_budget_line evaluates in the reference's order
+  subroutine budget_output(m)
+    integer, intent(in) :: m
+    character(len=9), parameter :: files(0:5) = [character(len=9) :: 'salbud', 'tembud', 'tkebud', 'glsbud', 'trcbud', 'trcbudtot']
+    integer(c_int) :: first, count, nterms, mask
+    real(c_double) :: terms(7)
+    integer :: f, nfu, nstep
+    call gpu_check(blomgpu_budget_output(ctx, m), 'budget_output')
+    call gpu_check(blomgpu_budget_steps(ctx, first, count), 'budget_output')
+    if (mnproc /= 1 .or. count < 2) return     ! (count = 0: cnsvdi is off)
+    nstep = first+count-1
+    call gpu_check(blomgpu_budget_files(ctx, mask), 'budget_output')
+    do f = 0, 5
+      if (.not. btest(mask, f)) cycle                      ! a file the tracer set does not call for (:231-268)
+      call gpu_check(blomgpu_budget_line(ctx, nstep, f, terms, nterms), 'budget_output')
+      open (newunit = nfu, file = trim(files(f)), position = 'append')
+      if (nterms == 7) then
+        write (nfu, '(i8,7e18.10)') nstep-1, terms(1:7)
+      else
+        write (nfu, '(i8,6e12.4)') nstep-1, terms(1:6)
+      end if
+      close (nfu)
+    end do
+  end subroutine
+  function gpu_budget(which, ncall, n) result(v)   ! sdp/tdp/trdp/tkedp/glsdp(ncall,n), phy/mod_budget.F90:49-57
     integer, intent(in) :: which, ncall, n
     real(c_double) :: v
     call gpu_check(blomgpu_budget_get(ctx, which, ncall, n, v), 'budget_get')

@@ -284,8 +284,70 @@ class BlomGpu:
 
     def budget_get(self, which, ncall, n):
         v = C.c_double(0.0)
-        self._chk(self.lib.blomgpu_budget_get(self.ctx, {"sdp": 0, "tdp": 1, "trdp": 2, "tkedp": 3}[which], ncall, n, C.byref(v)))
+        which = which if isinstance(which, int) else {"sdp": 0, "tdp": 1, "trdp": 2, "tkedp": 3, "glsdp": 4}[which]
+        self._chk(self.lib.blomgpu_budget_get(self.ctx, which, ncall, n, C.byref(v)))
         return v.value
+
+    BUDGET_SUMS = ("sdp", "tdp", "trdp", "tkedp", "glsdp")
+    BUDGET_FILES = ("salbud", "tembud", "tkebud", "glsbud", "trcbud", "trcbudtot")
+
+    def budget_init(self):
+        """budget_init (phy/mod_budget.F90:73): the global mass sum mass0; does nothing unless the option cnsvdi is set."""
+        self._chk(self.lib.blomgpu_budget_init(self.ctx))
+
+    def budget_output(self, m):
+        """budget_output's sums sf tf trf (phy/mod_budget.F90:335-352) into the record of the step the option nstep names -- for a host
+        that sequences the stages itself; step() with the option budget_step does it by itself."""
+        self._chk(self.lib.blomgpu_budget_output(self.ctx, m))
+
+    def budget_mass0(self):
+        v = C.c_double(0.0)
+        self._chk(self.lib.blomgpu_budget_mass0(self.ctx, C.byref(v)))
+        return v.value
+
+    def budget_steps(self):
+        """(first step, number of steps) the library holds records of: the last step() call's and the one of the step before it"""
+        first, count = C.c_int(0), C.c_int(0)
+        self._chk(self.lib.blomgpu_budget_steps(self.ctx, C.byref(first), C.byref(count)))
+        return first.value, count.value
+
+    def budget_record(self, nstep):
+        """the record of one step: the five sums of the seven calls as {name: array of 7}, sc, and sf tf trf as computed at its end"""
+        r = np.zeros(39)
+        self._chk(self.lib.blomgpu_budget_record(self.ctx, nstep, r.ctypes.data_as(C.c_void_p)))
+        out = {nm: r[:35].reshape(7, 5)[:, q].copy() for q, nm in enumerate(self.BUDGET_SUMS)}
+        out.update(sc=r[35], sf=r[36], tf=r[37], trf=r[38])
+        return out
+
+    def budget_records(self):
+        """every record held, as a dict of arrays with the steps along the first axis (key "nstep": the step numbers)"""
+        first, count = self.budget_steps()
+        recs = [self.budget_record(first + k) for k in range(count)]
+        out = {"nstep": np.arange(first, first + count)}
+        for nm in self.BUDGET_SUMS + ("sc", "sf", "tf", "trf"):
+            out[nm] = np.array([r[nm] for r in recs]) if recs else np.zeros((0, 7) if nm in self.BUDGET_SUMS else (0,))
+        return out
+
+    def budget_line(self, nstep, file):
+        """the terms budget_output writes for step nstep into `file` (phy/mod_budget.F90:211-331); the file's first column is nstep - 1"""
+        t, n = np.zeros(7), C.c_int(0)
+        self._chk(self.lib.blomgpu_budget_line(self.ctx, nstep, self.BUDGET_FILES.index(file), t.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return t[:n.value].copy()
+
+    def budget_files(self):
+        """the files the tracer set calls for (phy/mod_budget.F90:231-268)"""
+        mask = C.c_int(0)
+        self._chk(self.lib.blomgpu_budget_files(self.ctx, C.byref(mask)))
+        return [f for k, f in enumerate(self.BUDGET_FILES) if mask.value >> k & 1]
+
+    def budget_lines(self):
+        """{file: (nstep - 1 of every line, terms[line, term])} for the files the tracer set calls for and the steps that have a line"""
+        first, count = self.budget_steps()
+        out = {}
+        for f in self.budget_files() if count else ():
+            rows = [self.budget_line(s, f) for s in range(first + 1, first + count)]
+            out[f] = (np.arange(first, first + len(rows)), np.array(rows).reshape(len(rows), 7 if f == "trcbudtot" else 6))
+        return out
 
     # -- time-mean diagnostics (diaacc, phy/mod_dia.F90) -------------------------------------
     def dia_names(self):

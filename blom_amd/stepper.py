@@ -106,6 +106,25 @@ FULL_STAGES_LIVE_BEN02_END = with_step_end(FULL_STAGES_LIVE_BEN02)
 HYBRID_STAGES_BEN02_END = with_step_end(HYBRID_STAGES_BEN02)
 
 
+# mod_budget's conservation diagnostics (phy/mod_budget.F90; the option cnsvdi): budget_sums' seven calls as pseudo-stages budget_sums1..7
+# where blom_step has them (phy/mod_blom_step.F90:96, :132/:156, :159/:177, :183/:205, :215, :224, :230) and budget_output behind fwbbal and
+# in front of chkvar (:245).  Each returns at once unless cnsvdi is set.  BlomGpu.step places them itself with the option "budget_step".
+def with_budget(stages):
+    hybrid = "ale_regrid_remap" in stages
+    behind = {("ale_regrid_remap" if hybrid else "diffus"): 2, ("diffus" if hybrid else "convec"): 3, ("ale_vdiffm" if hybrid else "diapfl"): 4,
+              "updtrc": 5, "pbcor2": 6, "tmsmt2": 7}
+    out = ["budget_sums1"]
+    for s in stages:
+        if s == "chkvar":
+            out.append("budget_output")
+        out.append(s)
+        if s in behind:
+            out.append("budget_sums%d" % behind[s])
+    if "chkvar" not in stages:
+        out.append("budget_output")
+    return tuple(out)
+
+
 def dyncore_step(be, nstep, baclin, stages=DYNCORE_STAGES, hook=None):
     """Advance backend `be` from step count nstep to nstep+1.  `hook(stage, sextuple)` is
     called before each stage (tests use it to snapshot stage inputs)."""

@@ -96,11 +96,38 @@ int  blomgpu_momtum (blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k
 int  blomgpu_convec (blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);      /* phy/mod_convec.F90:43   */
 /* xcsum (phy/mod_xc.F90:4116): reproducible masked sum of one level of a device field (strips of 9 points per
  * row, rows added serially); itype selects the mask as for xctilr (p-grid: the mask of the global sums, ips).
- * budget_sums (phy/mod_budget.F90:95; active with the option cnsvdi = 1): mass weighted global sums of S, T and
- * tracer 1 after call `ncall` of the step; blomgpu_budget_get(which = 0 sdp | 1 tdp | 2 trdp | 3 tkedp). */
+ * budget_sums (phy/mod_budget.F90:95-196; active with the option cnsvdi = 1): mass weighted global sums of S, T, tracer 1, the
+ * TKE tracer (itrtke >= 1) and the GLS tracer (gls, itrgls >= 1) after call `ncall` of the step, and with call 5 (isopyc_bulkml) or 4
+ * (the other coordinates) the salt correction's sum sc (:182-194); the column sums are left in util1..util4 as the reference leaves
+ * them.  The numbers are also filed into the record of the step the option "nstep" names (below).
+ * blomgpu_budget_get(which = 0 sdp | 1 tdp | 2 trdp | 3 tkedp | 4 glsdp) (:49-57). */
 int  blomgpu_xcsum(blomgpu_ctx *, const char *name, int lev, int itype, double *sum);
 int  blomgpu_budget_sums(blomgpu_ctx *, int ncall, int n, int nn);
 int  blomgpu_budget_get(blomgpu_ctx *, int which, int ncall, int n, double *value);
+/* The rest of mod_budget.  blomgpu_budget_init (:73-93): mass0 = xcsum(pb(:,:,1)*scp2), kept in the context (blomgpu_budget_mass0).
+ * blomgpu_budget_output(ctx, m) (:335-352), for a host that sequences the stages itself: the sums sf tf trf of (salflx+salrlx),
+ * (surflx+surrlx) and trflx(1) times scp2*delt1 into the record of step "nstep"; the line of the step is blomgpu_budget_line's.
+ *
+ * blomgpu_set_int "budget_step" = 1 (with "cnsvdi" = 1): blomgpu_step runs the seven calls and budget_output's sums itself, where
+ * blom_step has them (phy/mod_blom_step.F90:96-245), two launches a call and no host synchronisation; the records of a call's steps
+ * come back in one copy at its end.  Such a call does not leave util1..util4 as the reference leaves them (scratch planes); with
+ * use_graph = 1 a budgeted step runs as plain launches; over RCCL ranks the option is refused at the first step.
+ *
+ * A record is 39 doubles: [(ncall-1)*5 + which] the five sums of the seven calls, [35] sc, [36..38] sf tf trf as computed at the END of
+ * that step.  The library holds the records of the last blomgpu_step call and the one of the step before it (a stage-by-stage host:
+ * the last 64 steps): blomgpu_budget_steps gives the first step and the count, blomgpu_budget_record fails for any other step.
+ * blomgpu_budget_line: the terms budget_output(m) writes at step nstep (:211-331; nstep - 1 is the line's first column) into file
+ * 0 salbud | 1 tembud | 2 tkebud | 3 glsbud | 4 trcbud (6 terms each) | 5 trcbudtot (7 terms): calls 1..5, sc, sf, tf, trf of step
+ * nstep - 1, calls 6 and 7 of step nstep, the surface flux in the 4th difference (isopyc_bulkml) or the 3rd.  It fails if step
+ * nstep - 1 has no record (the reference's nstep > nstep1 + 1) or the tracer set does not call for the file: blomgpu_budget_files gives
+ * the files it calls for (:231-268) as a mask, bit `file` set. */
+int  blomgpu_budget_init(blomgpu_ctx *);
+int  blomgpu_budget_output(blomgpu_ctx *, int m);
+int  blomgpu_budget_mass0(blomgpu_ctx *, double *mass0);
+int  blomgpu_budget_steps(blomgpu_ctx *, int *first_step, int *count);
+int  blomgpu_budget_record(blomgpu_ctx *, int nstep, double *rec39);
+int  blomgpu_budget_files(blomgpu_ctx *, int *mask);
+int  blomgpu_budget_line(blomgpu_ctx *, int nstep, int file, double *terms, int *nterms);
 /* exp() as the kernels evaluate it -- the algorithm and bits of the glibc libm that the reference's compiled Fortran
  * calls (blom_amd/csrc/exp_libm.h; phy/mod_barotp.F90:183,205, phy/mod_diapfl.F90:204) -- elementwise on host arrays. */
 int  blomgpu_exp(blomgpu_ctx *, int n, const double *x, double *y);
