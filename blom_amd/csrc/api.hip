@@ -230,7 +230,8 @@ static const Opt g_opts[] = {
   {"timing", O_BOOL, IN_C(timing), KEEP_GRAPHS},
   CI(barotp_fused),
   {"barotp_tile", O_INT, IN_C(barotp_tile), 0, [](double &v) -> const char * {
-     for (int ok : {0, 3216, 3208, 1608, 4016, 2616, 2615, 4015}) if (v == ok) return nullptr;
+     if (v == 0) return nullptr;
+     for (const BtShape &s : kBtShapes) if (v == 100 * s.ti + s.tj) return nullptr;
      return "blomgpu_set_int: barotp_tile must be 0, 3216, 3208, 1608, 4016, 2616, 2615 or 4015"; }},
   CI(barotp_persist), CI(barotp_block), CI(barotp_overlap), CI(barotp_rimbuf), CI(barotp_arctic_fused), CI(barotp_arctic_persist),
   CI(eddtra_frozen), CI(pgf_uv_pair), CI(pgf_uv_ring), CI(pgf_reuse), CI(pgf_copy_fused), CI(kprof_sel), CI(mom_aw_split),

@@ -345,6 +345,16 @@ struct StepState {
   bool pscan_done_ahead = false;     // st_cmnfld2 has launched the pressure scan of difest_isobml's front part (blomgpu_halo_difest consumes)
 };
 
+// The tile shapes of barotp's LDS-tiled kernels (stage_barotp_pair.hip) and the forms each serves.  Every shape has a kernel of the
+// pair-per-launch form (k_bt_steps<false>): pair_pref is its place in the choice by tile count, 0 where only the option barotp_tile
+// gives it.  persist: the persistent form (k_bt_steps<true>) has this shape, preferred in the order of the table; block: so has the
+// blocked form (k_bt_steps4).  The option's validator (api.hip) accepts 100 * ti + tj of these shapes.
+struct BtShape { int ti, tj, pair_pref; bool persist, block; };
+constexpr int BT_NSHAPES = 7;
+constexpr BtShape kBtShapes[BT_NSHAPES] = {{32, 16, 4, false, false}, {32, 8, 2, false, false}, {16, 8, 1, false, false},
+                                           {26, 16, 3, true, true},   {26, 15, 0, true, true},  {40, 16, 5, true, false},
+                                           {40, 15, 0, true, false}};
+
 struct blomgpu_ctx {
   // ==== options: what blomgpu_set_real / _int / _str store outside Params (api.hip: g_opts names each of them once) ====================
   // ---- namelist-type variables of the reference ----
@@ -432,7 +442,7 @@ struct blomgpu_ctx {
                                  // (bit-identical; ON by default since round 4, the arctic patch included -- in self-send on one GPU it
                                  // costs 0.2 ms, 9.78 against 9.59 ms per step; what it buys over xGMI has not been measured)
   int barotp_fused = 1;          // 1: LDS-tiled substep pairs (stage_barotp_pair.hip), 0: one kernel per equation
-  int barotp_tile = 0;           // tile shape of the pair kernel, 100*TI + TJ (3216, 3208, 1608); 0: chosen from the tile count
+  int barotp_tile = 0;           // tile shape of the tiled barotp kernels, 100*TI + TJ of an entry of kBtShapes; 0: chosen from the tile count
   int barotp_persist = 1;        // 1: one launch per barotropic phase where all tiles are resident (stage_barotp_pair.hip)
   int barotp_block = 1;          // 1: four substeps per hand-off where the persistent form runs (k_bt_steps4: no arctic patch, one process); 2: the same
                                  // kernel with one launch per four substeps (any number of tiles; the host emulation); 0: off
@@ -514,8 +524,8 @@ struct blomgpu_ctx {
   unsigned *bt_flags = nullptr;  // abort word + per-tile completion counts of the persistent barotp kernel
   int bt_flags_words = 0;        // words bt_flags holds (the persistent forms differ in their tile counts: it grows on demand)
   int num_cus = 0;
-  int bt4_blocks_per_cu[2] = {-1, -1};          // the same for the temporally blocked kernel (k_bt_steps4)
-  int bt_blocks_per_cu[4] = {-1, -1, -1, -1};   // occupancy query results for the persistent barotp kernel's shapes (-1: not asked yet)
+  // occupancy query results per entry of kBtShapes (-1: not asked yet): [0] the persistent pair kernel, [1] the blocked kernel (k_bt_steps4)
+  int bt_blocks_per_cu[BT_NSHAPES][2] = {{-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}, {-1, -1}};
   long long *bt_prof = nullptr;   // debug: phase timestamps of k_bt_pair
   long long *kprof = nullptr;     // debug (builds with -DBLOM_KPROF): per-wavefront phase timestamps of a column kernel, 8 words a wave (blomgpu_dbg_kprof)
   int kprof_words = 0;
@@ -757,20 +767,52 @@ unsigned host_crc_bytes(const unsigned char *p, size_t n, unsigned init);
 // of it that reads 3-D fields
 int st_barotp_on(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n, bool with_bounds);
 int st_barotp_bounds(blomgpu_ctx *, int m, int nn);
-// stage_barotp_pair.hip: the LDS-tiled forms of barotp's substeps, launched by stage_barotp.hip (the definitions say what each does)
-int bt_pair_halo(blomgpu_ctx *, int set);
-int bt_pair_halo_landed(blomgpu_ctx *, int set, RcclLanded *landed);
-int bt_pair_launch(blomgpu_ctx *, int m, int n, int ml, int nl, const double *wo, const double *wm, const double *wn, int do_odd, int do_even,
-                   int src, int tsel, RcclLanded *rim);
-bool bt_phase_usable(blomgpu_ctx *);
-int bt_phase_launch(blomgpu_ctx *, int m, int n, int ml, int nl, double woa, double wob, double wna, double wnb, int lll0, int last, int src,
-                    int *src_out, int *ml_out, int *nl_out);
-int bt_phase_check(blomgpu_ctx *);
-int bt_overlap_usable(blomgpu_ctx *);
+// The forms of barotp's subcycling.  bt_form (stage_barotp_pair.hip) holds the conditions; DESIGN.md 3.3 has the table.
+enum BtForm {
+  BT_EQUATIONS,           // one kernel per equation (stage_barotp.hip)
+  BT_PAIRS,               // one launch per odd+even substep pair (k_bt_steps<false>)
+  BT_PHASE,               // one persistent launch per phase (k_bt_steps<true>)
+  BT_PHASE_ARCTIC,        // the same over the whole pairs of a phase, lone substeps in front and behind as launches of their own
+  BT_BLOCKED_PERSISTENT,  // one launch for all five phases, four substeps per hand-off (k_bt_steps4)
+  BT_BLOCKED_PER_LAUNCH   // the same kernel, one launch per four substeps
+};
+// One of the five phases of a barotp call (phy/mod_barotp.F90:352-360): the substeps first..last, with the time weights
+// wo = woa * l + wob, wn = wna * l + wnb, wm = 1 - wo - wn of substep l, in the reference's order of operations.
+struct BtPhase {
+  int first, last;
+  double woa, wob, wna, wnb;
+  void weights(int l, double &wo, double &wm, double &wn) const {
+    wo = woa * l + wob;
+    wn = wna * l + wnb;
+    wm = 1. - wo - wn;
+  }
+};
+// Where the subcycling stands: the next substep, the buffer set (*_t / *_t2) that holds the state, the two barotropic time levels.  A
+// launch of the tiled forms takes an odd substep together with the even one behind it unless the phase ends in between; every launch
+// writes the other buffer set, and an odd number of substeps exchanges the time levels.
+struct BtCursor {
+  int lll = 1, set = 0, ml = 1, nl = 2;
+  bool odd() const { return lll % 2 == 1; }
+  bool both(int last) const { return odd() && lll + 1 <= last; }
+  void step(int nsub) {
+    set ^= 1;
+    if (nsub & 1) { const int ll = ml; ml = nl; nl = ll; }
+    lll += nsub;
+  }
+  void advance(int last) { step(both(last) ? 2 : 1); }
+};
+// stage_barotp_pair.hip: which form serves this context's next barotp call, and the drivers of the LDS-tiled ones (five BtPhase each)
+BtForm bt_form(blomgpu_ctx *);
 int bt_block_mode(blomgpu_ctx *);            // 1: the persistent blocked form serves this context, 2: one launch per iteration, 0: neither
 int bt_shape_code(blomgpu_ctx *);            // 100 * ti + tj of the tile shape of the next barotp call
-int bt_block_launch(blomgpu_ctx *, int mode, int m, int n, int ml, int nl, const int *ph_last, const double (*ph_w)[4], int src, int *src_out,
-                    int *ml_out, int *nl_out);
+int bt_run_pairs(blomgpu_ctx *, int m, int n, const BtPhase *ph);
+int bt_run_phases(blomgpu_ctx *, int m, int n, const BtPhase *ph);
+int bt_run_phases_arctic(blomgpu_ctx *, int m, int n, const BtPhase *ph);
+int bt_run_blocked(blomgpu_ctx *, BtForm form, int m, int n, const BtPhase *ph);
+int bt_phase_check(blomgpu_ctx *, BtForm form);
+// stage_barotp.hip: a phase's flux sums set to zero, and its epilogue
+void bt_zero_sums(blomgpu_ctx *);
+void bt_epilogue(blomgpu_ctx *, int nb, int m, int n, const BtCursor &q);
 
 // XCD-aware block order.  Workgroups are dealt round-robin over the 8 XCDs (linear id % 8), each with its own
 // 4 MB L2, so with the natural order the rows j-1, j, j+1 of a stencil land in three different L2s and are

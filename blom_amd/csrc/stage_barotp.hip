@@ -307,13 +307,69 @@ int st_barotp(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n) {
   if (c->tiling.rccl && c->bt_global) return rccl_barotp_replicated(c, m, n, mm, nn, k1m, k1n);
   return st_barotp_on(c, m, n, mm, nn, k1m, k1n, true);
 }
+
+// the five phases' substeps and time weights, :352-360 and below
+static void bt_schedule(int lstep, BtPhase *ph) {
+  int lll0 = 1;
+  double woa = 0., wob = 0., wna = 0., wnb = 0.;
+  for (int nb = 1; nb <= 5; nb++) {
+    if (nb == 1) { woa = -1. / lstep; wob = .5 + (lll0 - .5) / lstep; wna = 0.; wnb = 0.; }
+    else if (nb == 2) { woa = 0.; wob = 0.; wna = 1. / lstep; wnb = -(lll0 - .5) / lstep; }
+    else if (nb == 4) { wna = 0.; wnb = 1.; }
+    ph[nb - 1] = BtPhase{lll0, lll0 + lstep / 2 - 1, woa, wob, wna, wnb};
+    lll0 = lll0 + lstep / 2;
+  }
+}
+void bt_zero_sums(blomgpu_ctx *c) { hipLaunchKernelGGL(k_bt_zero_sums, plane_grid(c->h), dim3(256), 0, c->stream, c->d); }
+void bt_epilogue(blomgpu_ctx *c, int nb, int m, int n, const BtCursor &q) {
+  hipLaunchKernelGGL(k_bt_epilogue, plane_grid(c->h), dim3(256), 0, c->stream, c->d, nb, m, n, q.ml, q.nl, q.set);
+}
+
+// one kernel per equation, the state in buffer set 0 throughout
+static int bt_run_equations(blomgpu_ctx *c, int m, int n, const BtPhase *ph) {
+  const DevView &h = c->h;
+  const int ii = h.ii, jj = h.jj;
+  const dim3 g = plane_grid(h), b(256);
+  BtCursor q;
+  for (int nb = 1; nb <= 5; nb++) {
+    bt_zero_sums(c);
+    for (; q.lll <= ph[nb - 1].last; q.step(1), q.set = 0) {      // (these kernels update the state in place: always set 0)
+      BtArgs a;
+      a.m = m; a.n = n; a.ml = q.ml; a.nl = q.nl;
+      ph[nb - 1].weights(q.lll, a.wo, a.wm, a.wn);
+      if (q.odd()) {
+        {                                                                          // :395-397, one launch
+          double *ptrs[3] = {h.f[F_pb_t], h.f[F_ubflx_t], h.f[F_vbflx_t]};
+          const int nl3[3] = {2, 2, 2}, mh3[3] = {2, 2, 2}, nh3[3] = {2, 2, 3}, it3[3] = {1, 13, 14};
+          if (int rc = st_xctilr_arctic_multi(c, 3, ptrs, nl3, mh3, nh3, it3)) return rc;
+        }
+        a.j0 = -1; a.j1 = jj + 2; a.i0 = -1; a.i1 = ii + 1; a.lv = 0;
+        hipLaunchKernelGGL(k_bt_cont, g, b, 0, c->stream, c->d, a);
+        a.j0 = -1; a.j1 = jj + 2; a.i0 = 0; a.i1 = ii + 1; a.lv = q.ml;
+        hipLaunchKernelGGL(k_bt_umom, g, b, 0, c->stream, c->d, a);
+        a.j0 = 0; a.j1 = jj + 2; a.i0 = 0; a.i1 = ii; a.lv = q.nl;
+        hipLaunchKernelGGL(k_bt_vmom, g, b, 0, c->stream, c->d, a);
+      } else {
+        a.j0 = 0; a.j1 = jj + 1; a.i0 = 0; a.i1 = ii; a.lv = 0;
+        hipLaunchKernelGGL(k_bt_cont, g, b, 0, c->stream, c->d, a);
+        a.j0 = 1; a.j1 = jj + 1; a.i0 = 0; a.i1 = ii; a.lv = q.ml;
+        hipLaunchKernelGGL(k_bt_vmom, g, b, 0, c->stream, c->d, a);
+        a.j0 = 1; a.j1 = jj; a.i0 = 1; a.i1 = ii; a.lv = q.nl;
+        hipLaunchKernelGGL(k_bt_umom, g, b, 0, c->stream, c->d, a);
+      }
+    }
+    bt_epilogue(c, nb, m, n, q);
+  }
+  return 0;
+}
+
 // with_bounds = false: the velocity bounds and wave-breaking coefficients (:177-224, the part that reads 3-D fields) are
 // already in umaxb.., uglue.. (the global barotropic context of RCCL tiles holds no 3-D state)
 int st_barotp_on(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n, bool with_bounds) {
   (void)mm; (void)k1m; (void)k1n;
   const DevView &h = c->h;
   const size_t np = h.nplane;
-  const int ii = h.ii, jj = h.jj, lstep = h.P.lstep;
+  const int lstep = h.P.lstep;
   if (lstep < 2 || lstep % 2) return ctx_fail(c, "barotp: lstep must be even (phy/mod_time.F90:137-139)");
   const dim3 g = plane_grid(h), b(256);
   if (with_bounds) hipLaunchKernelGGL(k_bt_bounds, plane_grid(h, 1, 64), dim3(64), 0, c->stream, c->d, m, nn);
@@ -336,172 +392,20 @@ int st_barotp_on(blomgpu_ctx *c, int m, int n, int mm, int nn, int k1m, int k1n,
   if (h.nreg == 2) hipLaunchKernelGGL(k_bt_arctic_swap, g, b, 0, c->stream, c->d, n);       // :290-325
   if (int rc = ctx_err_words(c)) return rc;
   c->bt_restart = true;
-  int lll0 = 1, ml = 1, nl = 2, set = 0;     // set: which buffer set (*_t / *_t2) holds the current state
-  double woa = 0., wob = 0., wna = 0., wnb = 0.;
-  if (c->barotp_fused && h.nreg != 2 && bt_block_mode(c)) {
-    // k_bt_steps4: ONE launch walks the substeps of all five phases, four per hand-off, zeroing each phase's flux sums and doing its
-    // epilogue itself (the time weights of the phases, :352-360 and below, as a table)
-    int ph_last[5];
-    double ph_w[5][4];
-    for (int nb = 1; nb <= 5; nb++) {
-      if (nb == 1) { lll0 = 1; woa = -1. / lstep; wob = .5 + (lll0 - .5) / lstep; wna = 0.; wnb = 0.; }
-      else if (nb == 2) { woa = 0.; wob = 0.; wna = 1. / lstep; wnb = -(lll0 - .5) / lstep; }
-      else if (nb == 4) { wna = 0.; wnb = 1.; }
-      ph_w[nb - 1][0] = woa; ph_w[nb - 1][1] = wob; ph_w[nb - 1][2] = wna; ph_w[nb - 1][3] = wnb;
-      ph_last[nb - 1] = lll0 + lstep / 2 - 1;
-      lll0 = lll0 + lstep / 2;
-    }
-    hipLaunchKernelGGL(k_bt_load, g, b, 0, c->stream, c->d);
-    int so, mo, no;
-    if (int rc = bt_block_launch(c, bt_block_mode(c), m, n, 1, 2, ph_last, ph_w, 0, &so, &mo, &no)) return rc;
-    HIPCHK(c, hipGetLastError());
-    if (c->barotp_persist && bt_phase_usable(c)) return bt_phase_check(c);
-    return 0;
+  BtPhase ph[5];
+  bt_schedule(lstep, ph);
+  hipLaunchKernelGGL(k_bt_load, g, b, 0, c->stream, c->d);          // :339-348, phase 1
+  const BtForm form = bt_form(c);
+  int rc = 0;
+  switch (form) {
+    case BT_EQUATIONS: rc = bt_run_equations(c, m, n, ph); break;
+    case BT_PAIRS: rc = bt_run_pairs(c, m, n, ph); break;
+    case BT_PHASE: rc = bt_run_phases(c, m, n, ph); break;
+    case BT_PHASE_ARCTIC: rc = bt_run_phases_arctic(c, m, n, ph); break;
+    case BT_BLOCKED_PERSISTENT:
+    case BT_BLOCKED_PER_LAUNCH: rc = bt_run_blocked(c, form, m, n, ph); break;
   }
-  for (int nb = 1; nb <= 5; nb++) {
-    if (nb == 1) {
-      lll0 = 1; ml = 1; nl = 2;
-      woa = -1. / lstep;
-      wob = .5 + (lll0 - .5) / lstep;
-      wna = 0.; wnb = 0.;
-      hipLaunchKernelGGL(k_bt_load, g, b, 0, c->stream, c->d);
-    } else if (nb == 2) {
-      woa = 0.; wob = 0.;
-      wna = 1. / lstep;
-      wnb = -(lll0 - .5) / lstep;
-    } else if (nb == 4) {
-      wna = 0.; wnb = 1.;
-    }
-    const int last = lll0 + lstep / 2 - 1;
-    // With the arctic patch the halo update also rewrites the seam row jj, an interior row, so it must
-    // happen exactly where the reference has it: before odd substeps only.  The fused kernels then publish
-    // the margins they computed (PairArgs::write_margin), which is what the reference's arrays hold before
-    // a lone even substep and before the epilogue; single tile only.
-    const bool arctic1 = h.nreg == 2 && (!c->tiling.multi() || c->barotp_arctic_fused);
-    const bool fused = c->barotp_fused && (h.nreg != 2 || arctic1);
-    bool halo_done = false;
-    hipLaunchKernelGGL(k_bt_zero_sums, g, b, 0, c->stream, c->d);
-    if (fused && arctic1 && !c->tiling.multi() && c->barotp_persist && bt_phase_usable(c)) {
-      // arctic patch, single tile: the halo update -- which also rewrites the seam row -- belongs in front of odd substeps
-      // only, so the persistent launch takes the whole odd+even pairs of the phase (its tiles re-read rim and seam at the
-      // top of every pair), and a lone even substep at the start or a lone odd one at the end of a phase is its own launch
-      int lll = lll0;
-      double wo[2], wm[2], wn[2];
-      auto weights = [&](int l) {
-        wo[0] = wo[1] = woa * l + wob;
-        wn[0] = wn[1] = wna * l + wnb;
-        wm[0] = wm[1] = 1. - wo[0] - wn[0];
-      };
-      if (lll % 2 == 0) {                                                  // lone even substep: reads the published margins
-        weights(lll);
-        bt_pair_launch(c, m, n, ml, nl, wo, wm, wn, 0, 1, set, 0, nullptr);
-        set ^= 1;
-        { const int ll = ml; ml = nl; nl = ll; }
-        lll++;
-      }
-      const int npair = (last - lll + 1) / 2;
-      if (npair > 0) {
-        int so, mo, no;
-        if (int rc = bt_phase_launch(c, m, n, ml, nl, woa, wob, wna, wnb, lll, lll + 2 * npair - 1, set, &so, &mo, &no)) return rc;
-        set = so; ml = mo; nl = no;
-        lll += 2 * npair;
-      }
-      if (lll <= last) {                                                   // lone odd substep: folds while loading
-        weights(lll);
-        bt_pair_launch(c, m, n, ml, nl, wo, wm, wn, 1, 0, set, 0, nullptr);
-        set ^= 1;
-        { const int ll = ml; ml = nl; nl = ll; }
-      }
-    } else if (fused && !arctic1 && c->barotp_persist && bt_phase_usable(c)) {
-      // the whole phase in one launch (k_bt_steps<true>): coefficients stay on chip, tiles hand each other
-      // their edge values through memory
-      int so, mo, no;
-      if (int rc = bt_phase_launch(c, m, n, ml, nl, woa, wob, wna, wnb, lll0, last, set, &so, &mo, &no)) return rc;
-      set = so; ml = mo; nl = no;
-    } else if (fused) {
-      // fused odd+even substep pairs per LDS tile (stage_barotp_pair.hip); single substeps only
-      // where a pair would straddle a phase boundary (epilogue + sum reset sit in between)
-      int lll = lll0;
-      const bool ovl = bt_overlap_usable(c) != 0;
-      halo_done = false;
-      RcclLanded landed;          // .prepacked carries over from launch to launch within the phase
-      while (lll <= last) {
-        const bool odd = lll % 2 == 1;
-        const bool both = odd && lll + 1 <= last;
-        double wo[2], wm[2], wn[2];
-        for (int x = 0; x < 2; x++) {
-          const int l = both ? lll + x : lll;
-          wo[x] = woa * l + wob;
-          wn[x] = wna * l + wnb;
-          wm[x] = 1. - wo[x] - wn[x];
-        }
-        if (!both && !odd) { wo[1] = wo[0]; wm[1] = wm[0]; wn[1] = wn[0]; }
-        // single tile: the pair kernel applies the halo rule while loading; otherwise exchange first
-        // RCCL tiles along i: the received strips stay in the transport's buffers and the kernel loads its
-        // E/W rim from there (c->barotp_rimbuf), saving the unpack launch of every exchange
-        const bool rimbuf = c->tiling.rccl && c->barotp_rimbuf && c->tiling.npy == 1 && !ovl && h.nreg != 2 && !c->tiling.tab;
-        // (single tile with the arctic patch: the pair kernel applies xctilr's seam rule while loading, before odd substeps)
-        if ((arctic1 ? odd && c->tiling.multi() : c->tiling.multi()) && !halo_done) {
-          if (rimbuf) { if (int rc = bt_pair_halo_landed(c, set, &landed)) return rc; }
-          else if (int rc = bt_pair_halo(c, set)) return rc;
-        }
-        if (ovl) {
-          // fork: outer tile columns + exchange of the new state on xstream, inner columns on stream; join
-          HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
-          HIPCHK(c, hipStreamWaitEvent(c->xstream, c->ev_fork, 0));
-          bt_pair_launch(c, m, n, ml, nl, wo, wm, wn, odd ? 1 : 0, (both || !odd) ? 1 : 0, set, 1, nullptr);
-          set ^= 1;
-          c->halo_stream = c->xstream;
-          const int rc = bt_pair_halo(c, set);
-          c->halo_stream = nullptr;
-          if (rc) return rc;
-          HIPCHK(c, hipEventRecord(c->ev_join, c->xstream));
-          HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-          halo_done = true;
-        } else {
-          bt_pair_launch(c, m, n, ml, nl, wo, wm, wn, odd ? 1 : 0, (both || !odd) ? 1 : 0, set, 0, rimbuf ? &landed : nullptr);
-          set ^= 1;
-        }
-        if (!both) { const int ll = ml; ml = nl; nl = ll; }
-        lll += both ? 2 : 1;
-      }
-    } else
-    for (int lll = lll0; lll <= lll0 + lstep / 2 - 1; lll++) {
-      BtArgs a;
-      a.m = m; a.n = n; a.ml = ml; a.nl = nl;
-      a.wo = woa * lll + wob;
-      a.wn = wna * lll + wnb;
-      a.wm = 1. - a.wo - a.wn;
-      if (lll % 2 == 1) {
-        {                                                                          // :395-397, one launch
-          double *ptrs[3] = {h.f[F_pb_t], h.f[F_ubflx_t], h.f[F_vbflx_t]};
-          const int nl3[3] = {2, 2, 2}, mh3[3] = {2, 2, 2}, nh3[3] = {2, 2, 3}, it3[3] = {1, 13, 14};
-          if (int rc = st_xctilr_arctic_multi(c, 3, ptrs, nl3, mh3, nh3, it3)) return rc;
-        }
-        a.j0 = -1; a.j1 = jj + 2; a.i0 = -1; a.i1 = ii + 1; a.lv = 0;
-        hipLaunchKernelGGL(k_bt_cont, g, b, 0, c->stream, c->d, a);
-        a.j0 = -1; a.j1 = jj + 2; a.i0 = 0; a.i1 = ii + 1; a.lv = ml;
-        hipLaunchKernelGGL(k_bt_umom, g, b, 0, c->stream, c->d, a);
-        a.j0 = 0; a.j1 = jj + 2; a.i0 = 0; a.i1 = ii; a.lv = nl;
-        hipLaunchKernelGGL(k_bt_vmom, g, b, 0, c->stream, c->d, a);
-      } else {
-        a.j0 = 0; a.j1 = jj + 1; a.i0 = 0; a.i1 = ii; a.lv = 0;
-        hipLaunchKernelGGL(k_bt_cont, g, b, 0, c->stream, c->d, a);
-        a.j0 = 1; a.j1 = jj + 1; a.i0 = 0; a.i1 = ii; a.lv = ml;
-        hipLaunchKernelGGL(k_bt_vmom, g, b, 0, c->stream, c->d, a);
-        a.j0 = 1; a.j1 = jj; a.i0 = 1; a.i1 = ii; a.lv = nl;
-        hipLaunchKernelGGL(k_bt_umom, g, b, 0, c->stream, c->d, a);
-      }
-      const int ll = ml; ml = nl; nl = ll;
-    }
-    lll0 = lll0 + lstep / 2;
-    // the epilogue reads pb_t(i-1,j), pb_t(i,j-1); the fused kernels write tile interiors only
-    if (fused && !halo_done && !arctic1)
-      if (int rc = bt_pair_halo(c, set)) return rc;
-    halo_done = false;
-    hipLaunchKernelGGL(k_bt_epilogue, g, b, 0, c->stream, c->d, nb, m, n, ml, nl, set);
-  }
+  if (rc) return rc;
   HIPCHK(c, hipGetLastError());
-  if (c->barotp_fused && !c->tiling.multi() && c->barotp_persist && bt_phase_usable(c)) return bt_phase_check(c);
-  return 0;
+  return bt_phase_check(c, form);
 }

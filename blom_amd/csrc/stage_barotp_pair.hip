@@ -12,6 +12,7 @@
 // buffer set and writes go to the other (ping-pong), since a neighbour may still be loading.
 // All values are per-point identical to the unfused kernels (same expressions, same order).
 #include "blomgpu_internal.h"
+#include <utility>
 
 // Tile shapes: 32 x 16 (836 points with the rim, 14 wavefronts) is the persistent form's and the default; the smaller ones
 // serve contexts whose domain is only a few of those tiles -- the tiles of a multi-GPU decomposition, small grids -- where a
@@ -24,35 +25,34 @@
 // (where the rows do not come out -- 193 = 12 x 16 + 1 leaves a last tile row of one -- 26 x 15; 40 x 16 / 40 x 15, which
 // spill 15 registers, for domains of more than 256 such tiles.)
 constexpr int bt_threads(int ti, int tj) { return ((ti + 2 * HB) * (tj + 2 * HB) + 63) / 64 * 64; }
-struct BtShape { int ti, tj; };
-
+// Every member's default is what a form that does not use it passes; bt_args sets what all forms share and each launcher its own.
 struct PairArgs {
-  int m, n, ml, nl;          // baroclinic levels m,n; barotropic levels at the start of the launch
-  double wo[2], wm[2], wn[2];  // time weights of the odd [0] and even [1] substep
-  int do_odd, do_even;
-  int src;                   // 0: read *_t write *_t2, 1: the other way round
-  int fold_halo;             // single tile: apply the xctilr rule (wrap / vland) while loading
-  long long *prof;           // debug: per-block phase timestamps (nullptr in production)
+  int m = 0, n = 0, ml = 0, nl = 0;   // baroclinic levels m,n; barotropic levels at the start of the launch
+  double wo[2] = {0., 0.}, wm[2] = {0., 0.}, wn[2] = {0., 0.};  // time weights of the odd [0] and even [1] substep
+  int do_odd = 0, do_even = 0;
+  int src = 0;               // 0: read *_t write *_t2, 1: the other way round
+  int fold_halo = 1;         // single tile: apply the xctilr rule (wrap / vland) while loading
+  long long *prof = nullptr; // debug: per-block phase timestamps (nullptr in production)
   // persistent form (k_bt_steps<true>): the launch walks substeps lll0..last itself
-  int lll0, last;            // first and last substep of the phase
-  double woa, wob, wna, wnb; // time weights wo = woa*l + wob, wn = wna*l + wnb, wm = 1 - wo - wn (:352-360)
-  unsigned *flags;           // one word per tile: epoch_base + number of iterations this tile has completed and published
-  unsigned epoch_base;       // flags are never reset: every launch counts on from where the previous one stopped
-  unsigned *abort_word;      // set by any tile whose wait ran out; every spin also watches it
+  int lll0 = 0, last = 0;    // first and last substep of the phase
+  double woa = 0., wob = 0., wna = 0., wnb = 0.; // time weights wo = woa*l + wob, wn = wna*l + wnb, wm = 1 - wo - wn (:352-360)
+  unsigned *flags = nullptr; // one word per tile: epoch_base + number of iterations this tile has completed and published
+  unsigned epoch_base = 0;   // flags are never reset: every launch counts on from where the previous one stopped
+  unsigned *abort_word = nullptr; // set by any tile whose wait ran out; every spin also watches it
   // split launches (PERSIST = false, RCCL tiles): 0 all tile columns, 1 only the west-most and east-most
   // column of tiles (they produce the E/W strips the exchange sends), 2 only the columns in between
-  int tsel, nbx;
+  int tsel = 0, nbx = 0;
   // arctic patch: also publish the halo cells this tile computed redundantly (the reference's margins,
   // :420-457 etc. run over j = -1..jj+2), so that a following launch needs no halo update -- which with
   // the arctic patch would rewrite the seam row at a point where the reference does not
-  int write_margin;
+  int write_margin = 0;
   // RCCL tiles: the E/W rim comes straight from the transport's receive buffers (no unpack launch)
-  const double *rim_w, *rim_e;
-  int rim_has_w, rim_has_e, rim_per, rim_on;
+  const double *rim_w = nullptr, *rim_e = nullptr;
+  int rim_has_w = 0, rim_has_e = 0, rim_per = 0, rim_on = 0;
   // ... and the tiles that hold the outermost HB columns write their part of the next exchange's send
   // strips themselves (no pack launch); N/S rim cells of the columns 1..ii then follow the local rule at load
-  double *pack_w, *pack_e;
-  int pack_on;
+  double *pack_w = nullptr, *pack_e = nullptr;
+  int pack_on = 0;
   // k_bt_steps4 walks the substeps of ALL five barotropic phases (:352-977): phase x ends with substep ph_last[x] and has the time weights
   // wo = ph_w[x][0] l + ph_w[x][1], wn = ph_w[x][2] l + ph_w[x][3]; the kernel starts a phase's flux sums at zero (k_bt_zero_sums, :361-379)
   // and ends it with its epilogue (k_bt_epilogue, :847-977) itself
@@ -878,20 +878,170 @@ __global__ void k_bt_halo3(const DevView *__restrict__ Vp, int set, int mhl, int
   }
 }
 
-// RCCL tiles: exchange without the unpack launch; the strips stay in the transport's receive buffers
-int bt_pair_halo_landed(blomgpu_ctx *c, int set, RcclLanded *landed) {
-  const DevView &h = c->h;
-  double *f[3] = {set ? h.f[F_pb_t2] : h.f[F_pb_t], set ? h.f[F_ubflx_t2] : h.f[F_ubflx_t],
-                  set ? h.f[F_vbflx_t2] : h.f[F_vbflx_t]};
-  return rccl_xctilr_multi_ex(c, f, 3, 2, 3, 3, landed);
+// The instantiations kBtShapes asks for (7 + 4 + 2), in the order the object file has always had them: bt_shape_kernel below would
+// instantiate the same ones implicitly, but in the order of its own expansion, which reorders the device code.
+#define BT_INSTANTIATE(...) template __global__ void __VA_ARGS__(const DevView *, PairArgs)
+BT_INSTANTIATE(k_bt_steps<false, 32, 16>); BT_INSTANTIATE(k_bt_steps<false, 32, 8>);  BT_INSTANTIATE(k_bt_steps<false, 16, 8>);
+BT_INSTANTIATE(k_bt_steps<false, 40, 16>); BT_INSTANTIATE(k_bt_steps<false, 26, 16>); BT_INSTANTIATE(k_bt_steps<false, 26, 15>);
+BT_INSTANTIATE(k_bt_steps<false, 40, 15>);
+BT_INSTANTIATE(k_bt_steps<true, 26, 16>);  BT_INSTANTIATE(k_bt_steps<true, 26, 15>);  BT_INSTANTIATE(k_bt_steps<true, 40, 16>);
+BT_INSTANTIATE(k_bt_steps<true, 40, 15>);
+BT_INSTANTIATE(k_bt_steps4<26, 16>);       BT_INSTANTIATE(k_bt_steps4<26, 15>);
+#undef BT_INSTANTIATE
+
+// ==== host side: shapes, forms, launchers, one driver per form ==========================================================================
+// The one place that names the kernels' instantiations: kernel `k` of shape `sh` is launched with *a, or, without a, asked how many
+// of its workgroups a CU takes (*blocks_per_cu; 0 where the runtime cannot say).  false: the table has no such kernel.
+enum BtKernel { BT_K_PAIR, BT_K_PERSIST, BT_K_BLOCK };
+template <size_t... X>
+static bool bt_shape_kernel(std::index_sequence<X...>, blomgpu_ctx *c, BtShape sh, BtKernel k, dim3 grid, hipStream_t st, const PairArgs *a,
+                            int *blocks_per_cu) {
+  auto entry = [&](auto x) {
+    constexpr BtShape S = kBtShapes[decltype(x)::value];
+    if (S.ti != sh.ti || S.tj != sh.tj) return false;
+    if (k == BT_K_PAIR && a) {
+      hipLaunchKernelGGL((k_bt_steps<false, S.ti, S.tj>), grid, dim3(bt_threads(S.ti, S.tj)), 0, st, c->d, *a);
+      return true;
+    }
+    if constexpr (S.persist)
+      if (k == BT_K_PERSIST) {
+        if (a) hipLaunchKernelGGL((k_bt_steps<true, S.ti, S.tj>), grid, dim3(bt_threads(S.ti, S.tj)), 0, st, c->d, *a);
+        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_bt_steps<true, S.ti, S.tj>, bt_threads(S.ti, S.tj), 0) != hipSuccess)
+          *blocks_per_cu = 0;
+        return true;
+      }
+    if constexpr (S.block)
+      if (k == BT_K_BLOCK) {
+        if (a) hipLaunchKernelGGL((k_bt_steps4<S.ti, S.tj>), grid, dim3(BT4_NT), 0, st, c->d, *a);
+        else if (hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k_bt_steps4<S.ti, S.tj>, BT4_NT, 0) != hipSuccess)
+          *blocks_per_cu = 0;
+        return true;
+      }
+    return false;
+  };
+  return (entry(std::integral_constant<size_t, X>{}) || ...);
+}
+static int bt_launch(blomgpu_ctx *c, BtShape sh, BtKernel k, dim3 grid, hipStream_t st, const PairArgs &a) {
+  if (bt_shape_kernel(std::make_index_sequence<BT_NSHAPES>{}, c, sh, k, grid, st, &a, nullptr)) return 0;
+  return ctx_fail(c, "barotp: tile shape must be 3216, 3208, 1608, 4016, 2616, 2615 or 4015");
+}
+// the tiles wait for each other inside a persistent launch: every one of them must be resident.  Ask the runtime how many
+// workgroups of the kernel a CU takes (registers, LDS) instead of assuming one; asked once per shape and kernel.
+static int bt_resident_blocks(blomgpu_ctx *c, int x, BtKernel k) {
+  int &nb = c->bt_blocks_per_cu[x][k == BT_K_BLOCK];
+  if (nb < 0 && !bt_shape_kernel(std::make_index_sequence<BT_NSHAPES>{}, c, kBtShapes[x], k, dim3(), nullptr, nullptr, &nb)) nb = 0;
+  return nb;
+}
+// the device's CU count, asked once; -1: the query failed (0 on the host emulation: nothing is resident there)
+static int bt_num_cus(blomgpu_ctx *c) {
+  if (c->num_cus <= 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return -1;
+    c->num_cus = prop.multiProcessorCount;
+  }
+  return c->num_cus;
 }
 
-int bt_pair_halo(blomgpu_ctx *c, int set) {
+constexpr BtShape kNoShape{0, 0, 0, false, false};
+static int bt_ntiles(int n, int t) { return (n + t - 1) / t; }
+static bool bt_tile_allowed(const blomgpu_ctx *c, const BtShape &s) { return !c->barotp_tile || c->barotp_tile == 100 * s.ti + s.tj; }
+
+// Can the persistent form be used, and with which tile shape?  Every tile must be resident (one workgroup per CU) and a
+// tile's rim must come from its direct neighbours only (also across the periodic seam; with the arctic patch from the
+// mirror tiles of the last tile row too).  Shapes in the order of preference: 26 x 16 and 26 x 15 stay below 768 threads
+// (168 VGPRs: no spills); 40 x 16 / 40 x 15 serve domains that need more than 256 of those (the tnx1v4 dimensions).
+// {0, 0}: not usable -- one launch per substep pair then.
+static BtShape bt_phase_shape(blomgpu_ctx *c) {
+  const DevView &h = c->h;
+  if (c->tiling.multi()) return kNoShape;
+  const int cus = bt_num_cus(c);
+  for (int x = 0; x < BT_NSHAPES; x++) {
+    const BtShape &s = kBtShapes[x];
+    if (!s.persist || !bt_tile_allowed(c, s)) continue;
+    const int nbx = bt_ntiles(h.ii, s.ti), nby = bt_ntiles(h.jj, s.tj);
+    if (nbx * nby > cus) continue;
+    if (h.ii - (nbx - 1) * s.ti < HB || h.jj - (nby - 1) * s.tj < HB) continue;
+    // arctic patch: the fold reads the rows jj-1-HB..jj, which must lie in the last tile row; at least two tile columns,
+    // the last one wider than the sampling step with which the kernel finds its mirror tiles
+    if (h.nreg == 2 && (h.jj - (nby - 1) * s.tj < 2 * HB || nbx < 2 || h.ii - (nbx - 1) * s.ti < (s.ti + 2 * HB + 3) / 3 + 1 || !c->barotp_arctic_persist)) continue;
+    if (bt_resident_blocks(c, x, BT_K_PERSIST) < 1) continue;
+    return s;
+  }
+  return kNoShape;
+}
+static bool bt_phase_usable(blomgpu_ctx *c) { return bt_phase_shape(c).ti != 0; }
+
+// The temporally blocked form (k_bt_steps4): shape 26 x 16 or 26 x 15, no arctic patch, one process; the last tile row and
+// column at least as wide as the high rim (a tile's rim comes from its direct neighbours only).  persistent: all tiles
+// resident.  {0, 0}: not usable.
+static BtShape bt_block_shape(blomgpu_ctx *c, bool persistent) {
+  const DevView &h = c->h;
+  if (c->tiling.multi() || h.nreg == 2) return kNoShape;
+  const int cus = persistent ? bt_num_cus(c) : 0;
+  for (int x = 0; x < BT_NSHAPES; x++) {
+    const BtShape &s = kBtShapes[x];
+    if (!s.block || !bt_tile_allowed(c, s)) continue;
+    const int nbx = bt_ntiles(h.ii, s.ti), nby = bt_ntiles(h.jj, s.tj);
+    if (h.ii - (nbx - 1) * s.ti < BT4_RH || h.jj - (nby - 1) * s.tj < BT4_RH) continue;
+    if (persistent && (nbx * nby > cus || bt_resident_blocks(c, x, BT_K_BLOCK) < 1)) continue;
+    return s;
+  }
+  return kNoShape;
+}
+
+// Which form serves this context's next barotp call (DESIGN.md 3.3 has the table)
+BtForm bt_form(blomgpu_ctx *c) {
+  if (!c->barotp_fused) return BT_EQUATIONS;
+  if (c->barotp_block == 1 && c->barotp_persist && bt_block_shape(c, true).ti) return BT_BLOCKED_PERSISTENT;
+  if (c->barotp_block && c->barotp_block != 1 && bt_block_shape(c, false).ti) return BT_BLOCKED_PER_LAUNCH;
+  // With the arctic patch the halo update also rewrites the seam row jj, an interior row, so it must
+  // happen exactly where the reference has it: before odd substeps only.  The fused kernels then publish
+  // the margins they computed (PairArgs::write_margin), which is what the reference's arrays hold before
+  // a lone even substep and before the epilogue; single tile, or several with barotp_arctic_fused.
+  const bool arctic = c->h.nreg == 2;
+  if (arctic && c->tiling.multi() && !c->barotp_arctic_fused) return BT_EQUATIONS;
+  if (c->barotp_persist && bt_phase_usable(c)) return arctic ? BT_PHASE_ARCTIC : BT_PHASE;
+  return BT_PAIRS;
+}
+int bt_block_mode(blomgpu_ctx *c) {
+  const BtForm f = bt_form(c);
+  return f == BT_BLOCKED_PERSISTENT ? 1 : f == BT_BLOCKED_PER_LAUNCH ? 2 : 0;
+}
+
+// Tile shape of the one-pair-per-launch form.  Where the persistent form runs, its shape; otherwise chosen from the
+// number of tiles (option barotp_tile overrides).
+static BtShape bt_pair_shape(blomgpu_ctx *c) {
+  if (c->barotp_tile) return BtShape{c->barotp_tile / 100, c->barotp_tile % 100, 0, false, false};
+  const DevView &h = c->h;
+  if (c->barotp_persist && bt_phase_usable(c)) return bt_phase_shape(c);
+  const int asked = bt_num_cus(c), cus = asked < 0 ? 256 : asked;
+  // the smallest shape whose tiles all find a CU of their own (measured on the 180 x 193 tripolar grid: 32x16 = 78 tiles
+  // 16.4 us per launch, 32x8 = 150 tiles 13.5 us, 16x8 = 300 tiles on 256 CUs 22.7 us)
+  // 40x16 (1012 of the 1024 threads a workgroup may have): for domains whose 32x16 tiles outnumber the CUs -- the tnx1v4
+  // dimensions, 360 x 385: 300 tiles of 32x16 take two rounds on 256 CUs (42 us per pair), 225 tiles of 40x16 one
+  for (int pref = 1; pref <= BT_NSHAPES; pref++)
+    for (const BtShape &s : kBtShapes)
+      if (s.pair_pref == pref && bt_ntiles(h.ii, s.ti) * bt_ntiles(h.jj, s.tj) <= cus) return s;
+  return kBtShapes[0];
+}
+// 100 * ti + tj of the tile shape that serves this context's next barotp call (blomgpu_get_real "barotp_shape"): the blocked
+// form's where bt_form selects it, otherwise the shape of the pair forms (with one kernel per equation no tile kernel runs and
+// the value is the shape the fused form would take)
+int bt_shape_code(blomgpu_ctx *c) {
+  const BtForm f = bt_form(c);
+  const BtShape sh = f == BT_BLOCKED_PERSISTENT || f == BT_BLOCKED_PER_LAUNCH ? bt_block_shape(c, f == BT_BLOCKED_PERSISTENT) : bt_pair_shape(c);
+  return 100 * sh.ti + sh.tj;
+}
+
+// ---- halo of the state planes in front of a launch or an epilogue --------------------------------------------------------------------
+// landed (RCCL tiles): exchange without the unpack launch; the strips stay in the transport's receive buffers
+static int bt_pair_halo(blomgpu_ctx *c, int set, RcclLanded *landed = nullptr) {
   const DevView &h = c->h;
   if (c->tiling.multi() || h.nreg == 2) {   // neighbour exchange through the tile transport / the arctic rule of xctilr
     double *f[3] = {set ? h.f[F_pb_t2] : h.f[F_pb_t], set ? h.f[F_ubflx_t2] : h.f[F_ubflx_t],
                     set ? h.f[F_vbflx_t2] : h.f[F_vbflx_t]};
     static const int it[3] = {1, 13, 14};
+    if (landed) return rccl_xctilr_multi_ex(c, f, 3, 2, 3, 3, landed);
     if (h.nreg == 2) {                                                     // single tile, RCCL (batched), tiles of one process
       const int nl3[3] = {2, 2, 2}, w3[3] = {3, 3, 3};
       return st_xctilr_arctic_multi(c, 3, f, nl3, w3, w3, it);
@@ -905,142 +1055,53 @@ int bt_pair_halo(blomgpu_ctx *c, int set) {
   hipLaunchKernelGGL(k_bt_halo3, dim3((ntarget + 255) / 256, 3), dim3(256), 0, c->stream, c->d, set, 3, 3);
   return 0;
 }
-
-// Tile shape of the one-pair-per-launch form.  Where the persistent form runs, its shape; otherwise chosen from the
-// number of tiles (option barotp_tile = 3216 / 3208 / 1608 overrides).
-static BtShape bt_phase_shape(blomgpu_ctx *c);
-static BtShape bt_shape(blomgpu_ctx *c) {
-  if (c->barotp_tile) return BtShape{c->barotp_tile / 100, c->barotp_tile % 100};
-  const DevView &h = c->h;
-  if (c->barotp_persist && bt_phase_usable(c)) return bt_phase_shape(c);
-  if (c->num_cus <= 0) {
-    hipDeviceProp_t prop;
-    c->num_cus = hipGetDeviceProperties(&prop, c->device) == hipSuccess ? prop.multiProcessorCount : 256;
-  }
-  // the smallest shape whose tiles all find a CU of their own (measured on the 180 x 193 tripolar grid: 32x16 = 78 tiles
-  // 16.4 us per launch, 32x8 = 150 tiles 13.5 us, 16x8 = 300 tiles on 256 CUs 22.7 us)
-  // 40x16 (1012 of the 1024 threads a workgroup may have): for domains whose 32x16 tiles outnumber the CUs -- the tnx1v4
-  // dimensions, 360 x 385: 300 tiles of 32x16 take two rounds on 256 CUs (42 us per pair), 225 tiles of 40x16 one
-  static const BtShape shapes[5] = {{16, 8}, {32, 8}, {26, 16}, {32, 16}, {40, 16}};
-  for (const BtShape &sh : shapes) {
-    const int nt = ((h.ii + sh.ti - 1) / sh.ti) * ((h.jj + sh.tj - 1) / sh.tj);
-    if (nt <= c->num_cus) return sh;
-  }
-  return shapes[3];
-}
-static int bt_launch_pair(blomgpu_ctx *c, BtShape sh, dim3 grid, hipStream_t st, const PairArgs &a) {
-  if (sh.ti == 32 && sh.tj == 16) hipLaunchKernelGGL((k_bt_steps<false, 32, 16>), grid, dim3(bt_threads(32, 16)), 0, st, c->d, a);
-  else if (sh.ti == 32 && sh.tj == 8) hipLaunchKernelGGL((k_bt_steps<false, 32, 8>), grid, dim3(bt_threads(32, 8)), 0, st, c->d, a);
-  else if (sh.ti == 16 && sh.tj == 8) hipLaunchKernelGGL((k_bt_steps<false, 16, 8>), grid, dim3(bt_threads(16, 8)), 0, st, c->d, a);
-  else if (sh.ti == 40 && sh.tj == 16) hipLaunchKernelGGL((k_bt_steps<false, 40, 16>), grid, dim3(bt_threads(40, 16)), 0, st, c->d, a);
-  else if (sh.ti == 26 && sh.tj == 16) hipLaunchKernelGGL((k_bt_steps<false, 26, 16>), grid, dim3(bt_threads(26, 16)), 0, st, c->d, a);
-  else if (sh.ti == 26 && sh.tj == 15) hipLaunchKernelGGL((k_bt_steps<false, 26, 15>), grid, dim3(bt_threads(26, 15)), 0, st, c->d, a);
-  else if (sh.ti == 40 && sh.tj == 15) hipLaunchKernelGGL((k_bt_steps<false, 40, 15>), grid, dim3(bt_threads(40, 15)), 0, st, c->d, a);
-  else return ctx_fail(c, "barotp: tile shape must be 3216, 3208, 1608, 4016, 2616, 2615 or 4015");
+// a phase ends with its epilogue, which reads pb_t(i-1,j), pb_t(i,j-1); the tiled kernels write tile interiors only (halo = false: the
+// exchange behind the last launch has already run, or, with the arctic patch, the kernels have published their margins)
+static int bt_end_phase(blomgpu_ctx *c, int nb, int m, int n, const BtCursor &q, bool halo) {
+  if (halo)
+    if (int rc = bt_pair_halo(c, q.set)) return rc;
+  bt_epilogue(c, nb, m, n, q);
   return 0;
 }
 
-int bt_pair_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, const double *wo, const double *wm, const double *wn,
-                   int do_odd, int do_even, int src, int tsel, RcclLanded *rim) {
-  const DevView &h = c->h;
+// ---- launchers -------------------------------------------------------------------------------------------------------------------------
+// what the launches of all forms share
+static PairArgs bt_args(blomgpu_ctx *c, int m, int n, const BtCursor &q) {
   PairArgs a;
-  a.m = m; a.n = n; a.ml = ml; a.nl = nl;
-  for (int x = 0; x < 2; x++) { a.wo[x] = wo[x]; a.wm[x] = wm[x]; a.wn[x] = wn[x]; }
-  a.do_odd = do_odd; a.do_even = do_even; a.src = src;
+  a.m = m; a.n = n; a.ml = q.ml; a.nl = q.nl; a.src = q.set; a.prof = c->bt_prof;
+  return a;
+}
+
+// One launch of the pair form: the substep at the cursor, with the even one behind an odd one unless the phase ends in between.
+// tsel, rim: PairArgs (RCCL tiles).  The caller advances the cursor.
+static int bt_pair_launch(blomgpu_ctx *c, int m, int n, const BtPhase &p, const BtCursor &q, int tsel, RcclLanded *rim) {
+  const DevView &h = c->h;
+  auto a = bt_args(c, m, n, q);
+  for (int x = 0; x < 2; x++) p.weights(q.both(p.last) ? q.lll + x : q.lll, a.wo[x], a.wm[x], a.wn[x]);
+  a.do_odd = q.odd() ? 1 : 0; a.do_even = q.both(p.last) || !q.odd() ? 1 : 0;
   // single tile: the halo rule is applied while loading; with the arctic patch only where the reference has its halo
   // update, in front of an odd substep (a lone even substep reads the margins the launch before it published)
-  a.fold_halo = c->tiling.multi() ? 0 : (h.nreg == 2 ? (do_odd ? 1 : 0) : 1);
-  a.write_margin = (h.nreg == 2 && (!c->tiling.multi() || c->barotp_arctic_fused)) ? 1 : 0;
-  a.rim_on = 0; a.rim_w = a.rim_e = nullptr; a.rim_has_w = a.rim_has_e = 0; a.rim_per = 0;
+  a.fold_halo = c->tiling.multi() ? 0 : (h.nreg == 2 ? a.do_odd : 1);
+  a.write_margin = h.nreg == 2 ? 1 : 0;
   if (rim && rim->from_west) {
     a.rim_on = 1; a.rim_w = rim->from_west; a.rim_e = rim->from_east;
     a.rim_has_w = rim->has_w; a.rim_has_e = rim->has_e; a.rim_per = rim->per;
+    if (rim->send_west && h.jj >= 2 * HB && h.ii >= 2 * HB) { a.pack_on = 1; a.pack_w = rim->send_west; a.pack_e = rim->send_east; }
   }
-  a.pack_on = 0; a.pack_w = a.pack_e = nullptr;
-  if (rim && rim->from_west && rim->send_west && h.jj >= 2 * HB && h.ii >= 2 * HB) {
-    a.pack_on = 1; a.pack_w = rim->send_west; a.pack_e = rim->send_east;
-  }
-  a.prof = c->bt_prof;
-  a.lll0 = a.last = 0; a.woa = a.wob = a.wna = a.wnb = 0.; a.flags = nullptr; a.abort_word = nullptr; a.epoch_base = 0;
-  const BtShape sh = bt_shape(c);
-  const int nbx = (h.ii + sh.ti - 1) / sh.ti, nby = (h.jj + sh.tj - 1) / sh.tj;
+  const BtShape sh = bt_pair_shape(c);
+  const int nbx = bt_ntiles(h.ii, sh.ti), nby = bt_ntiles(h.jj, sh.tj);
   a.nbx = nbx;
   if (rim) rim->prepacked = a.pack_on;      // the launch below leaves the next exchange's send strips packed
-  if (tsel == 0) {
-    a.tsel = 0;
-    return bt_launch_pair(c, sh, dim3(nbx, nby), c->stream, a);
-  }
+  if (tsel == 0) return bt_launch(c, sh, BT_K_PAIR, dim3(nbx, nby), c->stream, a);
   // edge tile columns on the exchange stream (their output is what gets packed), the rest on the main stream
   a.tsel = 1;
-  if (int rc = bt_launch_pair(c, sh, dim3(nbx > 1 ? 2 : 1, nby), c->xstream, a)) return rc;
+  if (int rc = bt_launch(c, sh, BT_K_PAIR, dim3(nbx > 1 ? 2 : 1, nby), c->xstream, a)) return rc;
   if (nbx > 2) {
     a.tsel = 2;
-    if (int rc = bt_launch_pair(c, sh, dim3(nbx - 2, nby), c->stream, a)) return rc;
+    if (int rc = bt_launch(c, sh, BT_K_PAIR, dim3(nbx - 2, nby), c->stream, a)) return rc;
   }
   return 0;
 }
-
-// RCCL tiles along i, closed in j: the E/W strips a pair produces come from the two outer columns of
-// LDS tiles only, so those run first on the exchange stream, followed by pack / ncclSend+Recv / unpack,
-// while the columns in between compute on the main stream (the reference's "exchange, then compute"
-// order, phy/mod_barotp.F90:395-397, with the exchange moved to where its input is ready).  With a
-// periodic j the N/S phase of the exchange would read rows the inner tiles are still writing.
-// MEASURED (channel, RCCL self-send, one MI355X): bit-identical, but barotp 4.87 ms instead of 3.26 ms.
-// The pair kernel is latency-bound (15 of its 20 us are the coefficient load), so two half-size
-// launches each still take ~20 us, and the cross-stream fork/join events add ~10 us per pair: there is
-// no throughput-bound interior to hide the exchange behind.  Kept as an option (barotp_overlap=1),
-// off by default.
-int bt_overlap_usable(blomgpu_ctx *c) {
-  const DevView &h = c->h;
-  if (!c->tiling.rccl || !c->xstream || !c->barotp_overlap) return 0;
-  if (h.nreg > 2 || h.nreg == 2) return 0;
-  if (c->tiling.npy != 1) return 0;
-  const BtShape sh = bt_shape(c);
-  return (h.ii + sh.ti - 1) / sh.ti >= 3 ? 1 : 0;
-}
-
-// Can the persistent form be used, and with which tile shape?  Every tile must be resident (one workgroup per CU) and a
-// tile's rim must come from its direct neighbours only (also across the periodic seam; with the arctic patch from the
-// mirror tiles of the last tile row too).  Shapes in the order of preference: 26 x 16 and 26 x 15 stay below 768 threads
-// (168 VGPRs: no spills); 40 x 16 / 40 x 15 serve domains that need more than 256 of those (the tnx1v4 dimensions).
-// {0, 0}: not usable -- one launch per substep pair then.
-struct BtPersistShape { int ti, tj; };
-static const BtPersistShape kPersistShapes[4] = {{26, 16}, {26, 15}, {40, 16}, {40, 15}};
-template <int TI, int TJ>
-static int bt_persist_blocks_per_cu() {
-  int nb = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bt_steps<true, TI, TJ>, bt_threads(TI, TJ), 0) != hipSuccess) nb = 0;
-  return nb;
-}
-static BtShape bt_phase_shape(blomgpu_ctx *c) {
-  const DevView &h = c->h;
-  const BtShape none{0, 0};
-  if (c->tiling.multi()) return none;
-  if (c->num_cus <= 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return none;
-    c->num_cus = prop.multiProcessorCount;
-  }
-  for (int x = 0; x < 4; x++) {
-    const int ti = kPersistShapes[x].ti, tj = kPersistShapes[x].tj;
-    if (c->barotp_tile && c->barotp_tile != 100 * ti + tj) continue;
-    const int nbx = (h.ii + ti - 1) / ti, nby = (h.jj + tj - 1) / tj;
-    if (nbx * nby > c->num_cus) continue;
-    if (h.ii - (nbx - 1) * ti < HB || h.jj - (nby - 1) * tj < HB) continue;
-    // arctic patch: the fold reads the rows jj-1-HB..jj, which must lie in the last tile row; at least two tile columns,
-    // the last one wider than the sampling step with which the kernel finds its mirror tiles
-    if (h.nreg == 2 && (h.jj - (nby - 1) * tj < 2 * HB || nbx < 2 || h.ii - (nbx - 1) * ti < (ti + 2 * HB + 3) / 3 + 1 || !c->barotp_arctic_persist)) continue;
-    // the tiles wait for each other inside the launch: every one of them must be resident.  Ask the runtime how many
-    // workgroups of this kernel a CU takes (registers, LDS) instead of assuming one.
-    if (c->bt_blocks_per_cu[x] < 0)
-      c->bt_blocks_per_cu[x] = x == 0 ? bt_persist_blocks_per_cu<26, 16>() : x == 1 ? bt_persist_blocks_per_cu<26, 15>()
-                               : x == 2 ? bt_persist_blocks_per_cu<40, 16>() : bt_persist_blocks_per_cu<40, 15>();
-    if (c->bt_blocks_per_cu[x] < 1) continue;
-    return BtShape{ti, tj};
-  }
-  return none;
-}
-bool bt_phase_usable(blomgpu_ctx *c) { return bt_phase_shape(c).ti != 0; }
 
 // The abort word and the completion counts of the persistent forms, zeroed for the first launch of a barotp call.  The forms
 // differ in their tile counts (jj = 261: 17 tile rows of 16 in the pair form, 18 of 15 in the blocked one) and an option can
@@ -1063,156 +1124,173 @@ static int bt_flags_restart(blomgpu_ctx *c, int ntiles) {
   c->bt_restart = false;
   return 0;
 }
-
-// one launch for the substeps lll0..last of a phase; `src` as in bt_pair_launch; returns the buffer set
-// that holds the state afterwards in *src_out and the level indices in *ml_out, *nl_out
-int bt_phase_launch(blomgpu_ctx *c, int m, int n, int ml, int nl, double woa, double wob, double wna, double wnb, int lll0,
-                    int last, int src, int *src_out, int *ml_out, int *nl_out) {
-  const DevView &h = c->h;
-  const BtShape psh = bt_phase_shape(c);
-  if (!psh.ti) return ctx_fail(c, "barotp: the persistent form is not usable on this domain");
-  const int nbx = (h.ii + psh.ti - 1) / psh.ti, nby = (h.jj + psh.tj - 1) / psh.tj;
-  int niter = 0;
-  for (int lll = lll0; lll <= last; niter++) lll += (lll % 2 == 1 && lll + 1 <= last) ? 2 : 1;
-  // the completion counters start at 0 with the first launch of every barotp call (st_barotp sets bt_restart): the
-  // launches of a step then carry the same epochs every step, which lets blomgpu_step replay them as a graph
+// what a persistent launch of ntiles tiles and niter iterations needs: the completion counts, its epochs, the abort word.  The counters
+// start at 0 with the first launch of every barotp call (st_barotp_on sets bt_restart): the launches of a step then carry the same
+// epochs every step, which lets blomgpu_step replay them as a graph
+static int bt_persist_args(blomgpu_ctx *c, PairArgs &a, int ntiles, int niter) {
   if (!c->bt_flags || c->bt_restart)
-    if (int rc = bt_flags_restart(c, nbx * nby)) return rc;
-  PairArgs a;
-  a.m = m; a.n = n; a.ml = ml; a.nl = nl;
-  for (int x = 0; x < 2; x++) { a.wo[x] = a.wm[x] = a.wn[x] = 0.; }
-  a.do_odd = a.do_even = 0; a.src = src;
-  a.fold_halo = 1;
-  a.prof = c->bt_prof;
-  a.lll0 = lll0; a.last = last; a.woa = woa; a.wob = wob; a.wna = wna; a.wnb = wnb;
+    if (int rc = bt_flags_restart(c, ntiles)) return rc;
   a.flags = c->bt_flags + 16;
-  // arctic patch: the launch covers whole odd+even pairs only (st_barotp_on); its last iteration also publishes the margins
-  // beyond the edges of the domain, which a following lone even substep and the epilogue read without a halo update
-  a.tsel = 0; a.nbx = nbx; a.write_margin = h.nreg == 2 ? 1 : 0;
-  a.pack_on = 0; a.pack_w = a.pack_e = nullptr;
-  a.rim_on = 0; a.rim_w = a.rim_e = nullptr; a.rim_has_w = a.rim_has_e = 0; a.rim_per = 0;
   a.epoch_base = c->bt_epoch;
   c->bt_epoch += (unsigned)niter;
   if (int rc = ctx_err_words(c)) return rc;
   a.abort_word = (unsigned *)(c->err_dev + 2);
-  TimeScope tk(c, "k_bt_steps");
-  if (psh.ti == 26 && psh.tj == 16) hipLaunchKernelGGL((k_bt_steps<true, 26, 16>), dim3(nbx, nby), dim3(bt_threads(26, 16)), 0, c->stream, c->d, a);
-  else if (psh.ti == 26) hipLaunchKernelGGL((k_bt_steps<true, 26, 15>), dim3(nbx, nby), dim3(bt_threads(26, 15)), 0, c->stream, c->d, a);
-  else if (psh.tj == 16) hipLaunchKernelGGL((k_bt_steps<true, 40, 16>), dim3(nbx, nby), dim3(bt_threads(40, 16)), 0, c->stream, c->d, a);
-  else hipLaunchKernelGGL((k_bt_steps<true, 40, 15>), dim3(nbx, nby), dim3(bt_threads(40, 15)), 0, c->stream, c->d, a);
-  // replay the iteration bookkeeping of the kernel
-  for (int lll = lll0; lll <= last;) {
-    const bool odd = lll % 2 == 1, both = odd && lll + 1 <= last;
-    src ^= 1;
-    if (!both) { const int t = ml; ml = nl; nl = t; }
-    lll += both ? 2 : 1;
-  }
-  *src_out = src; *ml_out = ml; *nl_out = nl;
   return 0;
 }
 
-// The temporally blocked form (k_bt_steps4): shape 26 x 16 or 26 x 15, no arctic patch, one process; the last tile row and
-// column at least as wide as the high rim (a tile's rim comes from its direct neighbours only).  persistent: all tiles
-// resident.  {0, 0}: not usable.
-static BtShape bt_block_shape(blomgpu_ctx *c, bool persistent) {
+// One persistent launch (k_bt_steps<true>) for the substeps from the cursor to `last` of phase p: coefficients stay on chip, tiles
+// hand each other their edge values through memory.  Leaves the cursor behind `last`.
+static int bt_phase_launch(blomgpu_ctx *c, int m, int n, const BtPhase &p, int last, BtCursor &q) {
   const DevView &h = c->h;
-  const BtShape none{0, 0};
-  if (c->tiling.multi() || h.nreg == 2) return none;
-  if (persistent && c->num_cus <= 0) {
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return none;
-    c->num_cus = prop.multiProcessorCount;
-  }
-  for (int x = 0; x < 2; x++) {
-    const int ti = kPersistShapes[x].ti, tj = kPersistShapes[x].tj;
-    if (c->barotp_tile && c->barotp_tile != 100 * ti + tj) continue;
-    const int nbx = (h.ii + ti - 1) / ti, nby = (h.jj + tj - 1) / tj;
-    if (h.ii - (nbx - 1) * ti < BT4_RH || h.jj - (nby - 1) * tj < BT4_RH) continue;
-    if (persistent) {
-      if (nbx * nby > c->num_cus) continue;
-      if (c->bt4_blocks_per_cu[x] < 0) {
-        int nb = 0;
-        hipError_t e = x == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bt_steps4<26, 16>, BT4_NT, 0)
-                              : hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k_bt_steps4<26, 15>, BT4_NT, 0);
-        c->bt4_blocks_per_cu[x] = e == hipSuccess ? nb : 0;
+  const BtShape sh = bt_phase_shape(c);
+  if (!sh.ti) return ctx_fail(c, "barotp: the persistent form is not usable on this domain");
+  const int nbx = bt_ntiles(h.ii, sh.ti), nby = bt_ntiles(h.jj, sh.tj);
+  auto a = bt_args(c, m, n, q);
+  a.lll0 = q.lll; a.last = last; a.woa = p.woa; a.wob = p.wob; a.wna = p.wna; a.wnb = p.wnb;
+  // arctic patch: the launch covers whole odd+even pairs only (bt_run_phases_arctic); its last iteration also publishes the margins
+  // beyond the edges of the domain, which a following lone even substep and the epilogue read without a halo update
+  a.nbx = nbx; a.write_margin = h.nreg == 2 ? 1 : 0;
+  int niter = 0;
+  for (; q.lll <= last; niter++) q.advance(last);       // the kernel's iterations: the cursor is where the launch leaves the state
+  if (int rc = bt_persist_args(c, a, nbx * nby, niter)) return rc;
+  TimeScope tk(c, "k_bt_steps");
+  return bt_launch(c, sh, BT_K_PERSIST, dim3(nbx, nby), c->stream, a);
+}
+
+// ---- one driver per form: the five phases of a barotp call -------------------------------------------------------------------------------
+// RCCL tiles along i, closed in j: the E/W strips a pair produces come from the two outer columns of
+// LDS tiles only, so those run first on the exchange stream, followed by pack / ncclSend+Recv / unpack,
+// while the columns in between compute on the main stream (the reference's "exchange, then compute"
+// order, phy/mod_barotp.F90:395-397, with the exchange moved to where its input is ready).  With a
+// periodic j the N/S phase of the exchange would read rows the inner tiles are still writing.
+// MEASURED (channel, RCCL self-send, one MI355X): bit-identical, but barotp 4.87 ms instead of 3.26 ms.
+// The pair kernel is latency-bound (15 of its 20 us are the coefficient load), so two half-size
+// launches each still take ~20 us, and the cross-stream fork/join events add ~10 us per pair: there is
+// no throughput-bound interior to hide the exchange behind.  Kept as an option (barotp_overlap=1),
+// off by default.
+static bool bt_overlap_usable(blomgpu_ctx *c) {
+  const DevView &h = c->h;
+  if (bt_form(c) != BT_PAIRS || !c->tiling.rccl || !c->xstream || !c->barotp_overlap) return false;
+  if (h.nreg >= 2 || c->tiling.npy != 1) return false;
+  return bt_ntiles(h.ii, bt_pair_shape(c).ti) >= 3;
+}
+
+// Fused odd+even substep pairs per LDS tile, one launch each; single substeps only where a pair would straddle a phase
+// boundary (epilogue + sum reset sit in between)
+int bt_run_pairs(blomgpu_ctx *c, int m, int n, const BtPhase *ph) {
+  const DevView &h = c->h;
+  const bool arctic = h.nreg == 2, multi = c->tiling.multi(), ovl = bt_overlap_usable(c);
+  // single tile: the pair kernel applies the halo rule while loading (with the arctic patch xctilr's seam rule, before odd substeps);
+  // otherwise exchange first.  RCCL tiles along i: the received strips stay in the transport's buffers and the kernel loads its
+  // E/W rim from there (c->barotp_rimbuf), saving the unpack launch of every exchange
+  const bool rimbuf = c->tiling.rccl && c->barotp_rimbuf && c->tiling.npy == 1 && !ovl && !arctic && !c->tiling.tab;
+  BtCursor q;
+  for (int nb = 1; nb <= 5; nb++) {
+    const BtPhase &p = ph[nb - 1];
+    bt_zero_sums(c);
+    bool halo_done = false;
+    RcclLanded landed;          // .prepacked carries over from launch to launch within the phase
+    while (q.lll <= p.last) {
+      if ((arctic ? q.odd() && multi : multi) && !halo_done) {
+        if (int rc = bt_pair_halo(c, q.set, rimbuf ? &landed : nullptr)) return rc;
       }
-      if (c->bt4_blocks_per_cu[x] < 1) continue;
+      if (ovl) {
+        // fork: outer tile columns + exchange of the new state on xstream, inner columns on stream; join
+        HIPCHK(c, hipEventRecord(c->ev_fork, c->stream));
+        HIPCHK(c, hipStreamWaitEvent(c->xstream, c->ev_fork, 0));
+        if (int rc = bt_pair_launch(c, m, n, p, q, 1, nullptr)) return rc;
+        q.advance(p.last);
+        c->halo_stream = c->xstream;
+        const int rc = bt_pair_halo(c, q.set);
+        c->halo_stream = nullptr;
+        if (rc) return rc;
+        HIPCHK(c, hipEventRecord(c->ev_join, c->xstream));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+        halo_done = true;
+      } else {
+        if (int rc = bt_pair_launch(c, m, n, p, q, 0, rimbuf ? &landed : nullptr)) return rc;
+        q.advance(p.last);
+      }
     }
-    return BtShape{ti, tj};
+    if (int rc = bt_end_phase(c, nb, m, n, q, !halo_done && !arctic)) return rc;
   }
-  return none;
+  return 0;
 }
-// 1: the persistent blocked form serves this context, 2: the blocked form with one launch per iteration, 0: neither
-int bt_block_mode(blomgpu_ctx *c) {
-  if (!c->barotp_block || !c->barotp_fused) return 0;
-  if (c->barotp_block == 1) return c->barotp_persist && bt_block_shape(c, true).ti ? 1 : 0;
-  return bt_block_shape(c, false).ti ? 2 : 0;
+
+// One persistent launch per phase
+int bt_run_phases(blomgpu_ctx *c, int m, int n, const BtPhase *ph) {
+  BtCursor q;
+  for (int nb = 1; nb <= 5; nb++) {
+    bt_zero_sums(c);
+    if (int rc = bt_phase_launch(c, m, n, ph[nb - 1], ph[nb - 1].last, q)) return rc;
+    if (int rc = bt_end_phase(c, nb, m, n, q, true)) return rc;
+  }
+  return 0;
 }
-// 100 * ti + tj of the tile shape that serves this context's next barotp call (blomgpu_get_real "barotp_shape"): the blocked
-// form's where bt_block_mode selects it, otherwise the shape of the pair forms (with barotp_fused = 0, one kernel per equation,
-// no tile kernel runs and the value is the shape the fused form would take)
-int bt_shape_code(blomgpu_ctx *c) {
-  const int mode = bt_block_mode(c);
-  const BtShape sh = mode ? bt_block_shape(c, mode == 1) : bt_shape(c);
-  return 100 * sh.ti + sh.tj;
+
+// Arctic patch, single tile: the halo update -- which also rewrites the seam row -- belongs in front of odd substeps only, so the
+// persistent launch takes the whole odd+even pairs of the phase (its tiles re-read rim and seam at the top of every pair), and a lone
+// even substep at the start (it reads the published margins) or a lone odd one at the end of a phase (it folds while loading) is a
+// launch of the pair form
+int bt_run_phases_arctic(blomgpu_ctx *c, int m, int n, const BtPhase *ph) {
+  BtCursor q;
+  for (int nb = 1; nb <= 5; nb++) {
+    const BtPhase &p = ph[nb - 1];
+    bt_zero_sums(c);
+    if (!q.odd()) {
+      if (int rc = bt_pair_launch(c, m, n, p, q, 0, nullptr)) return rc;
+      q.advance(p.last);
+    }
+    const int npair = (p.last - q.lll + 1) / 2;
+    if (npair > 0)
+      if (int rc = bt_phase_launch(c, m, n, p, q.lll + 2 * npair - 1, q)) return rc;
+    if (q.lll <= p.last) {
+      if (int rc = bt_pair_launch(c, m, n, p, q, 0, nullptr)) return rc;
+      q.advance(p.last);
+    }
+    if (int rc = bt_end_phase(c, nb, m, n, q, false)) return rc;
+  }
+  return 0;
 }
-// the substeps of all five phases, four per iteration; mode as bt_block_mode returns it; ph_last / ph_w: PairArgs
-int bt_block_launch(blomgpu_ctx *c, int mode, int m, int n, int ml, int nl, const int *ph_last, const double (*ph_w)[4], int src,
-                    int *src_out, int *ml_out, int *nl_out) {
+
+// k_bt_steps4 walks the substeps of all five phases, four per hand-off, zeroing each phase's flux sums and doing its epilogue itself:
+// ONE persistent launch, or one launch per four substeps
+int bt_run_blocked(blomgpu_ctx *c, BtForm form, int m, int n, const BtPhase *ph) {
   const DevView &h = c->h;
-  const BtShape sh = bt_block_shape(c, mode == 1);
+  const bool persistent = form == BT_BLOCKED_PERSISTENT;
+  const BtShape sh = bt_block_shape(c, persistent);
   if (!sh.ti) return ctx_fail(c, "barotp: the blocked form is not usable on this domain");
-  const int nbx = (h.ii + sh.ti - 1) / sh.ti, nby = (h.jj + sh.tj - 1) / sh.tj;
-  const int lll0 = 1, last = ph_last[4];
-  const int niter = (last - lll0 + 1 + 3) / 4;
-  PairArgs a;
-  a.m = m; a.n = n;
-  for (int x = 0; x < 2; x++) { a.wo[x] = a.wm[x] = a.wn[x] = 0.; }
-  a.do_odd = a.do_even = 0; a.fold_halo = 1; a.prof = nullptr;
-  a.woa = a.wob = a.wna = a.wnb = 0.;
+  const int nbx = bt_ntiles(h.ii, sh.ti), nby = bt_ntiles(h.jj, sh.tj), last = ph[4].last;
+  BtCursor q;
+  auto a = bt_args(c, m, n, q);
   for (int x = 0; x < 5; x++) {
-    a.ph_last[x] = ph_last[x];
-    for (int y = 0; y < 4; y++) a.ph_w[x][y] = ph_w[x][y];
+    a.ph_last[x] = ph[x].last;
+    a.ph_w[x][0] = ph[x].woa; a.ph_w[x][1] = ph[x].wob; a.ph_w[x][2] = ph[x].wna; a.ph_w[x][3] = ph[x].wnb;
   }
-  a.tsel = 0; a.nbx = nbx; a.write_margin = 0;
-  a.pack_on = 0; a.pack_w = a.pack_e = nullptr;
-  a.rim_on = 0; a.rim_w = a.rim_e = nullptr; a.rim_has_w = a.rim_has_e = 0; a.rim_per = 0;
-  a.flags = nullptr; a.abort_word = nullptr; a.epoch_base = 0;
-  auto launch = [&]() {
-    if (sh.tj == 16) hipLaunchKernelGGL((k_bt_steps4<26, 16>), dim3(nbx, nby), dim3(BT4_NT), 0, c->stream, c->d, a);
-    else hipLaunchKernelGGL((k_bt_steps4<26, 15>), dim3(nbx, nby), dim3(BT4_NT), 0, c->stream, c->d, a);
-  };
-  if (mode == 1) {
-    if (!c->bt_flags || c->bt_restart)
-      if (int rc = bt_flags_restart(c, nbx * nby)) return rc;
-    a.flags = c->bt_flags + 16;
-    a.epoch_base = c->bt_epoch;
-    c->bt_epoch += (unsigned)niter;
-    if (int rc = ctx_err_words(c)) return rc;
-    a.abort_word = (unsigned *)(c->err_dev + 2);
-    a.ml = ml; a.nl = nl; a.src = src; a.lll0 = lll0; a.last = last;
+  a.nbx = nbx;
+  if (persistent) {
+    if (int rc = bt_persist_args(c, a, nbx * nby, (last - q.lll + 1 + 3) / 4)) return rc;
+    a.lll0 = q.lll; a.last = last;
     TimeScope tk(c, "k_bt_steps");
-    launch();
-    HIPCHK(c, hipGetLastError());
-    src ^= niter & 1;
-    if ((last - lll0 + 1) & 1) { const int t = ml; ml = nl; nl = t; }
+    if (int rc = bt_launch(c, sh, BT_K_BLOCK, dim3(nbx, nby), c->stream, a)) return rc;
   } else {
     TimeScope tk(c, "k_bt_steps");
-    for (int lll = lll0; lll <= last; lll += 4) {
-      const int e = lll + 3 < last ? lll + 3 : last;
-      a.ml = ml; a.nl = nl; a.src = src; a.lll0 = lll; a.last = e;
-      launch();
-      src ^= 1;
-      if ((e - lll + 1) & 1) { const int t = ml; ml = nl; nl = t; }
+    while (q.lll <= last) {
+      const int e = q.lll + 3 < last ? q.lll + 3 : last;
+      a.ml = q.ml; a.nl = q.nl; a.src = q.set; a.lll0 = q.lll; a.last = e;
+      if (int rc = bt_launch(c, sh, BT_K_BLOCK, dim3(nbx, nby), c->stream, a)) return rc;
+      q.step(e - q.lll + 1);
     }
-    HIPCHK(c, hipGetLastError());
   }
-  *src_out = src; *ml_out = ml; *nl_out = nl;
+  HIPCHK(c, hipGetLastError());
   return 0;
 }
 
-// did any tile of the persistent launches give up waiting?  (checked once per barotp call)
-int bt_phase_check(blomgpu_ctx *c) {
+// did any tile of the persistent launches give up waiting?  (checked once per barotp call that ran `form`; behind the blocked forms
+// where the persistent pair form could serve the context too)
+int bt_phase_check(blomgpu_ctx *c, BtForm form) {
+  const bool blocked = form == BT_BLOCKED_PERSISTENT || form == BT_BLOCKED_PER_LAUNCH;
+  if (!(form == BT_PHASE || form == BT_PHASE_ARCTIC || (blocked && c->barotp_persist && bt_phase_usable(c)))) return 0;
   if (c->seq.defer_checks) return 0;
   return ctx_check_errors(c);
 }
