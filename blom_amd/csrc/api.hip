@@ -298,6 +298,14 @@ static const Opt g_stepend_opts[] = {
 static const Opt g_budget_opts[] = {
   CI(budget_step),
 };
+// blomgpu_dia_reduce's section kernel (stage_diaout.hip), likewise unlisted: the entries of a section a pass takes and the levels a
+// chunk stages, so that a small grid can cross both boundaries
+static const Opt g_diaout_opts[] = {
+  {"diaout_entries", O_INT, IN_C(diaout_entries), KEEP_GRAPHS, [](double &v) -> const char * {
+     return v < 1 || v > 256 ? "blomgpu_set_int: diaout_entries is 1..256" : nullptr; }},
+  {"diaout_levels", O_INT, IN_C(diaout_levels), KEEP_GRAPHS, [](double &v) -> const char * {
+     return v < 1 || v > 8 ? "blomgpu_set_int: diaout_levels is 1..8" : nullptr; }},
+};
 #undef IN_P
 #undef IN_C
 #undef PR
@@ -317,6 +325,8 @@ static const Opt *find_opt(std::string_view name, unsigned kinds) {      // kind
   for (const Opt &o : g_stepend_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   for (const Opt &o : g_budget_opts)
+    if (name == o.name && (kinds >> o.kind & 1)) return &o;
+  for (const Opt &o : g_diaout_opts)
     if (name == o.name && (kinds >> o.kind & 1)) return &o;
   return nullptr;
 }
@@ -477,6 +487,7 @@ int blomgpu_destroy(blomgpu_ctx *c) {
   if (c->bt_flags) (void)hipFree(c->bt_flags);
   ale_free(c);
   dia_free(c);
+  diaout_free(c);
   cesm_free(c);
   ben02_free(c);
   stepend_free(c);
@@ -738,6 +749,17 @@ int blomgpu_dia_name_full(int index, char *buf, int cap, int *kind, int *grid) {
 int blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid) { return dia_name_ext(index, buf, cap, kind, grid); }
 int blomgpu_dia_set_sigdia(blomgpu_ctx *c, const double *sigdia, int n) { return dia_set_sigdia(c, sigdia, n); }
 int blomgpu_dia_get_sigdia(blomgpu_ctx *c, double *out, int cap, int *n) { return dia_get_sigdia(c, out, cap, n); }
+// what diaout_iogrp forms from the accumulators at output time (stage_diaout.hip)
+int blomgpu_dia_name_msc(int index, char *buf, int cap, int *kind, int *grid) { return diaout_name_msc(index, buf, cap, kind, grid); }
+int blomgpu_dia_set_mertra(blomgpu_ctx *c, int lmax, const double *mtlat, const int *nind, const int *pts, const int *oflg, int ocn_nreg,
+                           int mer_nreg, const int *nflg, const int *regflg, const double *minlat, const double *maxlat) {
+  return c ? diaout_set_mertra(c, lmax, mtlat, nind, pts, oflg, ocn_nreg, mer_nreg, nflg, regflg, minlat, maxlat) : 1;
+}
+int blomgpu_dia_set_sections(blomgpu_ctx *c, int sec_num, const int *nsi, const int *pts, int equat_sec) {
+  return c ? diaout_set_sections(c, sec_num, nsi, pts, equat_sec) : 1;
+}
+int blomgpu_dia_reduce(blomgpu_ctx *c) { return c ? diaout_reduce(c) : 1; }
+int blomgpu_dia_msc_get(blomgpu_ctx *c, const char *name, double *out, int cap, int *dims) { return c ? diaout_msc_get(c, name, out, cap, dims) : 1; }
 // sfcstr, phy/mod_sfcstr.F90:33-62: the surface stress of the idealised experiments is set at initialisation
 // (or absent), so the stage is empty for them; the coupled/reanalysis branches live in modules that are
 // not part of this path.

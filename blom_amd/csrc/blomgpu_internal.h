@@ -298,6 +298,7 @@ struct RcclComm;             // one process per GPU, neighbour ncclSend/ncclRecv
 struct BtGlobal;             // RCCL tiles: the barotropic solve replicated on every rank (comm_rccl.hip)
 struct DiaState;             // the selected time-mean diagnostics and their accumulators (stage_diaacc.hip)
 struct BudgetState;          // mod_budget's records, on the device and on the host (stage_budget.hip)
+struct DiaOutState;          // the section and region tables of diamer / diasec and the results of the last reduce (stage_diaout.hip)
 // The general tile table of xcspmd (phy/mod_xc.F90:1332-1720), kept for ragged layouts only: tile rows cut differently,
 // tiles shrunk to their sea points, all-land tiles eliminated (ii = 0).  Tensor-product layouts never carry one.
 struct TileTable {
@@ -562,6 +563,8 @@ struct blomgpu_ctx {
   double *fwb_buf = nullptr;                   // fwbbal's year end: [0..1] totei, totpr, then the row sums of both
   unsigned long long *chk_dev = nullptr;       // chkvar's words: [0] the error word, [1] the key of the first hit in the serial reference's order
   int dia_alarm = -1;                          // blomgpu_dia_alarm: alarm_phy(1) as the host declared it, 0 | 1; -1: undeclared
+  DiaOutState *diaout = nullptr;               // blomgpu_dia_set_mertra / _set_sections' tables and blomgpu_dia_reduce's results (stage_diaout.hip)
+  int diaout_entries = 256, diaout_levels = 8; // k_diaout_sections: section entries per pass (1..256), levels per chunk (1..8)
 };
 // alternative device views (see blomgpu_ctx::overlap): MOM_A = momtum's work space + its pu, pv (k_mom_pupv, the viscous
 // march); MOM_B = momtum's work space + its p (k_mom_pscan, k_mom_drag, the Coriolis march); MOM_C = momtum's work space
@@ -655,8 +658,9 @@ static inline double *ctx_real_ptr(const blomgpu_ctx *c, int id) {
   return c->ben02_planes ? c->ben02_planes + (size_t)(id - FID_BEN02) * c->h.nplane : nullptr;
 }
 static inline int ctx_real_nlev(const blomgpu_ctx *c, int id) { return id < FID_BEN02 ? c->nlev_real[id] : id >= FID_STEPEND ? kStepEndLevels[id - FID_STEPEND] : 1; }
-// halo.hip: xcsum of nb planes at once, the sums left on the device in out[0..nb-1]; mask[q] == nullptr: ips
-int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int *const *masks, double *rows, double *out);
+// halo.hip: xcsum of nb planes at once, the sums left on the device in out[0..nb-1]; mask[q] == nullptr: ips; count: the launches go into
+// the forcing family's launch count (cesm_launches), which is thermf's statistic -- another caller passes false
+int st_xcsum_batch(blomgpu_ctx *, int nb, const double *const *planes, const int *const *masks, double *rows, double *out, bool count = true);
 int st_niw_ke_tendency(blomgpu_ctx *, int m, int mm);                           // stage_difest.hip
 int st_difest_isobml_pre(blomgpu_ctx *, int m, int n, int mm, int nn);
 int st_difest_isobml(blomgpu_ctx *, int m, int n, int mm, int nn);               // stage_difest_iso.hip: the whole routine
@@ -730,6 +734,23 @@ int dia_step_check(blomgpu_ctx *);           // a selection that reads z / dz in
 bool dia_active(const blomgpu_ctx *);
 void dia_count(blomgpu_ctx *);
 void dia_free(blomgpu_ctx *);
+unsigned dia_msc_mask(const blomgpu_ctx *);  // the selected msc names, bit = row of stage_diaout.hip's table
+bool dia_finalized(const blomgpu_ctx *);     // blomgpu_dia_finalize has run since the accumulators were initialised
+const double *dia_edges_dev(const blomgpu_ctx *, int *ddm);   // the ddm + 1 edges of the depth levels on the device; ddm 0: no level row selected
+int dia_levels_kind(const blomgpu_ctx *);    // the level table in force: 35 (:111-128), 70 (LEVITUS2X) or 0 (the caller's own)
+const double *dia_plane_dev(const blomgpu_ctx *, const char *name);   // first plane of a selected accumulator on the device, or nullptr
+// stage_diaout.hip: what diaout_iogrp forms from the accumulators at output time (phy/mod_dia.F90:2366-2588): diamer, diasec, the global
+// sums and means.  The msc names have no accumulator of their own: dia_select asks for their sources.
+int diaout_msc_index(const char *name);      // row of an msc name, or -1
+void diaout_msc_sources(int row, std::vector<std::string> *names);   // appends the accumulators the name is formed from
+int diaout_name_msc(int index, char *buf, int cap, int *kind, int *grid);
+int diaout_set_mertra(blomgpu_ctx *, int lmax, const double *mtlat, const int *nind, const int *pts, const int *oflg, int ocn_nreg,
+                      int mer_nreg, const int *nflg, const int *regflg, const double *minlat, const double *maxlat);
+int diaout_set_sections(blomgpu_ctx *, int sec_num, const int *nsi, const int *pts, int equat_sec);
+int diaout_reduce(blomgpu_ctx *);
+int diaout_msc_get(blomgpu_ctx *, const char *name, double *out, int cap, int *dims);
+void diaout_invalidate(blomgpu_ctx *);       // a new selection or a reset: the results of the last reduce are no longer handed out
+void diaout_free(blomgpu_ctx *);
 int st_mom_pupv(blomgpu_ctx *, int off, int lo, int hi);                          // stage_momtum.hip
 int st_convec_velocity(blomgpu_ctx *, int nn);                                    // stage_convec.hip
 int launch_dpudpv(blomgpu_ctx *, int off, int flags);                                        // stage_simple.hip

@@ -1286,7 +1286,7 @@ int st_xcsum_dev(blomgpu_ctx *c, const double *a, int itype, int slot, double **
 
 // nb planes at once: two launches per XCS_NB = 32 planes on a single tile (counted in cesm_launches).  On tile groups and over RCCL the one-plane paths above, once per
 // plane (they know the ip mask only: a mask of the caller's own is refused there).  rows: nb * jtdm doubles of the caller's.
-int st_xcsum_batch(blomgpu_ctx *c, int nb, const double *const *planes, const int *const *masks, double *rows, double *out) {
+int st_xcsum_batch(blomgpu_ctx *c, int nb, const double *const *planes, const int *const *masks, double *rows, double *out, bool count) {
   const DevView &h = c->h;
   if (c->tiling.multi()) {
     for (int q = 0; q < nb; q++) {
@@ -1309,7 +1309,7 @@ int st_xcsum_batch(blomgpu_ctx *c, int nb, const double *const *planes, const in
     }
     hipLaunchKernelGGL(k_xcsum_rows_batch, dim3(h.jj, n), dim3(64), 0, c->stream, c->d, B, rows + (size_t)q0 * h.jj);
     hipLaunchKernelGGL(k_xcsum_total_batch, dim3(n), dim3(256), sizeof(double) * (size_t)h.jj, c->stream, rows + (size_t)q0 * h.jj, h.jj, out + q0);
-    c->cesm_launches += 2;
+    if (count) c->cesm_launches += 2;
   }
   HIPCHK(c, hipGetLastError());
   return 0;

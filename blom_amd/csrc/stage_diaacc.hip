@@ -170,6 +170,8 @@ struct DiaState {
   int ncls = 0;                 // selected density-class slots; their kk class densities lie behind the edges
   bool vfl = false;             // diavfl's group is selected: wflx wflx2 wflxlvl wflx2lvl uflx vflx uflxlvl vflxlvl uflxold vflxold
   bool col = false, ml82 = false, pv = false;   // a row of k_diacol is selected; one of mldl82 mldl82mn mldl82mx mldl82sq; avdsg dpvor
+  unsigned msc = 0;             // the selected msc names (stage_diaout.hip: bit = its row there); they have no slot, their sources have
+  bool finalized = false;       // blomgpu_dia_finalize has run since the last initialisation: the level rows hold fill values
   double *sigdia() const { return edges() + (ddm ? ddm + 1 : 0); }
   size_t np = 0;
   int slot_of(int row) const {
@@ -865,6 +867,7 @@ static int dia_init(blomgpu_ctx *c, DiaState *S) {
     if (nl > maxlev) maxlev = nl;
   }
   S->nacc = 0;
+  S->finalized = false;
   if (!T.n) return 0;
   ctx_sync_view(c);
   hipLaunchKernelGGL(k_dia_init, plane_grid(c->h, maxlev), dim3(256), 0, c->stream, c->d, S->acc, T);
@@ -937,13 +940,22 @@ int dia_select(blomgpu_ctx *c, const char *names) {
   const std::string all(names);
   size_t pos = 0;
   bool any = false;
+  unsigned msc = 0;
+  std::vector<std::string> nms;
   while (pos < all.size()) {
     while (pos < all.size() && (all[pos] == ' ' || all[pos] == ',' || all[pos] == '\t' || all[pos] == '\n')) pos++;
     size_t end = pos;
     while (end < all.size() && !(all[end] == ' ' || all[end] == ',' || all[end] == '\t' || all[end] == '\n')) end++;
     if (end == pos) break;
-    const std::string nm = all.substr(pos, end - pos);
+    const std::string tok = all.substr(pos, end - pos);
     pos = end;
+    // an msc name (diaout_iogrp's reductions, stage_diaout.hip) selects its sources as diaini does (:557, :559, :598-670)
+    const int mi = diaout_msc_index(tok.c_str());
+    if (mi >= 0) msc |= 1u << mi;
+    if (mi >= 0) diaout_msc_sources(mi, &nms);
+    else nms.push_back(tok);
+  }
+  for (const std::string &nm : nms) {
     const int r = find_row(nm);
     if (r < 0) return ctx_fail(c, "blomgpu_dia_select: unknown accumulator " + nm);
     if (g_rows[r].op == OP_OLD)
@@ -991,6 +1003,7 @@ int dia_select(blomgpu_ctx *c, const char *names) {
   if (any) {
     S = new DiaState;
     S->vfl = vfl;
+    S->msc = msc;
     int n2d = 0, nly = 0, nlv = 0;
     for (int r = 0; r < NROW; r++)
       if (want[r] && g_rows[r].lyr == 2) nlv++;
@@ -1034,11 +1047,33 @@ int dia_select(blomgpu_ctx *c, const char *names) {
   }
   dia_free(c);                       // the previous selection goes only now that the new one stands
   c->dia = S;
+  diaout_invalidate(c);
   ctx_drop_graphs(c);
   return 0;
 }
 
-int dia_reset(blomgpu_ctx *c) { return c->dia ? dia_init(c, c->dia) : 0; }       // inifld, :5864
+int dia_reset(blomgpu_ctx *c) {                                                  // inifld, :5864
+  diaout_invalidate(c);
+  return c->dia ? dia_init(c, c->dia) : 0;
+}
+
+// what stage_diaout.hip reads of a selection: the msc names, the count, whether finalize has run, the depth levels on the device,
+// and the first plane of a selected accumulator
+unsigned dia_msc_mask(const blomgpu_ctx *c) { return c->dia ? c->dia->msc : 0u; }
+bool dia_finalized(const blomgpu_ctx *c) { return c->dia && c->dia->finalized; }
+const double *dia_edges_dev(const blomgpu_ctx *c, int *ddm) {
+  *ddm = c->dia ? c->dia->ddm : 0;
+  return *ddm ? c->dia->edges() : nullptr;
+}
+int dia_levels_kind(const blomgpu_ctx *c) {       // 35: the table of :111-128, 70: LEVITUS2X, 0: a table of the caller's
+  const std::vector<double> &e = c->dia_edges;
+  if (e.empty() || (e.size() == 36 && !memcmp(e.data(), g_edges35, sizeof(g_edges35)))) return 35;
+  return e.size() == 71 && !memcmp(e.data(), g_edges70, sizeof(g_edges70)) ? 70 : 0;
+}
+const double *dia_plane_dev(const blomgpu_ctx *c, const char *name) {
+  const int r = find_row(name), s = r >= 0 && c->dia ? c->dia->slot_of(r) : -1;
+  return s < 0 ? nullptr : c->dia->acc + (size_t)c->dia->plane0[s] * c->dia->np;
+}
 
 // alarm_phy(1) (phy/mod_dia.F90: diaout_alarms) as the host declares it.  Under cntiso_hybrid / plevel it decides where templvl salnlvl
 // uvellvl vvellvl take their sample: inside ale_regrid_remap while it is 0 (phy/mod_ale_regrid_remap.F90:1524-1531), in ale_remap_diazlv
@@ -1116,6 +1151,7 @@ int dia_finalize(blomgpu_ctx *c) {
     if (g_rows[S->rows[s]].lyr == 2 && g_rows[S->rows[s]].op != OP_OLD) { M.d[M.n][0] = S->plane0[s]; M.d[M.n][1] = g_rows[S->rows[s]].grid; M.n++; }   // (wflxlvl, wflx2lvl on p: :2676-2677)
   if (M.n) hipLaunchKernelGGL(k_dia_msklvl, plane_grid(c->h, S->ddm), dim3(256), 0, c->stream, c->d, S->acc, S->edges(), M);
   HIPCHK(c, hipGetLastError());
+  S->finalized = true;               // blomgpu_dia_reduce is refused from here until a reset or a new selection
   return 0;
 }
 

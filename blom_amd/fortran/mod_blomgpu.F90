@@ -193,6 +193,35 @@ module mod_blomgpu
       integer(c_int), value :: cap
       integer(c_int), intent(out) :: n
     end function
+    ! diaout_iogrp's reductions (phy/mod_dia.F90:2366-2588: diamer, diasec, the global sums)
+    integer(c_int) function blomgpu_dia_name_msc(index, buf, cap, kind, grid) bind(C, name='blomgpu_dia_name_msc')
+      import :: c_int, c_char
+      integer(c_int), value :: index, cap
+      character(kind=c_char), intent(out) :: buf(*)
+      integer(c_int), intent(out) :: kind, grid
+    end function
+    integer(c_int) function blomgpu_dia_set_mertra(c, lmax, mtlat, nind, pts, oflg, ocn_nreg, mer_nreg, nflg, regflg, minlat, maxlat) &
+         bind(C, name='blomgpu_dia_set_mertra')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, mtlat, nind, pts, oflg, nflg, regflg, minlat, maxlat
+      integer(c_int), value :: lmax, ocn_nreg, mer_nreg
+    end function
+    integer(c_int) function blomgpu_dia_set_sections(c, sec_num, nsi, pts, equat_sec) bind(C, name='blomgpu_dia_set_sections')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c, nsi, pts
+      integer(c_int), value :: sec_num, equat_sec
+    end function
+    integer(c_int) function blomgpu_dia_reduce(c) bind(C, name='blomgpu_dia_reduce')
+      import :: c_ptr, c_int
+      type(c_ptr), value :: c
+    end function
+    integer(c_int) function blomgpu_dia_msc_get(c, name, out, cap, dims) bind(C, name='blomgpu_dia_msc_get')
+      import :: c_ptr, c_int, c_char
+      type(c_ptr), value :: c, out
+      character(kind=c_char), intent(in) :: name(*)
+      integer(c_int), value :: cap
+      integer(c_int), intent(out) :: dims(3)
+    end function
     integer(c_int) function blomgpu_field_info(c, name, nlev, isint) bind(C, name='blomgpu_field_info')
       import :: c_ptr, c_int, c_char
       type(c_ptr), value :: c
@@ -339,6 +368,7 @@ module mod_blomgpu
   public :: iniswa, updswa, fwbbal, chkvar
   public :: gpu_dia_set_levels, gpu_dia_default_levels, gpu_dia_levitus2x, gpu_dia_get_levels
   public :: gpu_dia_set_sigdia, gpu_dia_clear_sigdia, gpu_dia_get_sigdia
+  public :: gpu_dia_set_mertra, gpu_dia_set_sections, gpu_dia_reduce, gpu_dia_msc
 
   interface gpu_set
     module procedure gpu_set_real, gpu_set_int, gpu_set_str
@@ -849,6 +879,34 @@ contains
     call gpu_check(blomgpu_dia_nacc(ctx, v), 'gpu_dia_nacc')
     gpu_dia_nacc = v
   end function
+  ! diaout_iogrp's reductions (phy/mod_dia.F90:2366-2588).  The tables diamer reads from mer_orfile and mer_mifile (:4026-4108) and
+  ! diasec from sec_sifile (:3838-3866) are the host's: pts(4,n) = (i, j, uflg, vflg) per point, oflg(itdm,jtdm), regflg(20,mer_nreg)
+  ! (Fortran order: the C arrays' transposes).  gpu_dia_reduce goes where diaout_iogrp has diamer and diasec: behind the last step of
+  ! the window (and ale_remap_diazlv), in front of gpu_dia_finalize; gpu_dia_msc hands one result out with its extents (:4113-4119).
+  subroutine gpu_dia_set_mertra(lmax, mtlat, nind, pts, oflg, ocn_nreg, mer_nreg, nflg, regflg, minlat, maxlat)
+    integer, intent(in) :: lmax, ocn_nreg, mer_nreg
+    real(8), intent(in), target :: mtlat(lmax), minlat(mer_nreg), maxlat(mer_nreg)
+    integer(c_int), intent(in), target :: nind(lmax), pts(4,*), oflg(*), nflg(mer_nreg), regflg(20,mer_nreg)
+    call gpu_check(blomgpu_dia_set_mertra(ctx, int(lmax, c_int), c_loc(mtlat), c_loc(nind), c_loc(pts), c_loc(oflg), int(ocn_nreg, c_int), &
+         int(mer_nreg, c_int), c_loc(nflg), c_loc(regflg), c_loc(minlat), c_loc(maxlat)), 'gpu_dia_set_mertra')
+  end subroutine
+  subroutine gpu_dia_set_sections(sec_num, nsi, pts, equat_sec)
+    integer, intent(in) :: sec_num, equat_sec
+    integer(c_int), intent(in), target :: nsi(sec_num), pts(4,*)
+    call gpu_check(blomgpu_dia_set_sections(ctx, int(sec_num, c_int), c_loc(nsi), c_loc(pts), int(equat_sec, c_int)), 'gpu_dia_set_sections')
+  end subroutine
+  subroutine gpu_dia_reduce()
+    call gpu_check(blomgpu_dia_reduce(ctx), 'gpu_dia_reduce')
+  end subroutine
+  subroutine gpu_dia_msc(name, a, cap, dims)
+    character(len=*), intent(in) :: name
+    integer, intent(in) :: cap
+    real(8), intent(out), target :: a(cap)
+    integer, intent(out) :: dims(3)
+    integer(c_int) :: d(3)
+    call gpu_check(blomgpu_dia_msc_get(ctx, cz(name), c_loc(a), int(cap, c_int), d), 'gpu_dia_msc')
+    dims = d
+  end subroutine
   subroutine cmnfld2(m,n,mm,nn,k1m,k1n)         ! phy/mod_cmnfld_routines.F90:1158 (halo updates, bfsqf, neutral slopes)
     integer, intent(in) :: m,n,mm,nn,k1m,k1n
     call stage6('cmnfld2',m,n,mm,nn,k1m,k1n)

@@ -39,6 +39,7 @@ class BlomGpu:
         self.lib = load_library()
         self.idm, self.jdm, self.kdm, self.ntr, self.nreg = idm, jdm, kdm, ntr, nreg
         self.ni, self.nj = idm + 8, jdm + 8
+        self.itdm, self.jtdm = itdm or idm, jtdm or jdm
         d = blomgpu_dims(idm, jdm, kdm, 4, itdm or idm, jtdm or jdm, i0, j0, nreg, ntr, device)
         self.ctx = C.c_void_p()
         rc = self.lib.blomgpu_create(C.byref(d), C.byref(self.ctx))
@@ -390,6 +391,62 @@ class BlomGpu:
             rows.append((buf.value.decode(), kind.value, "puv"[grid.value]))
             k += 1
         return rows
+
+    def dia_names_msc(self):
+        """the rows of dia_names_ext() in their order, then the 23 msc names that dia_reduce forms from the accumulators at output
+        time (kind 5) -- blomgpu_dia_name_msc"""
+        out, k = [], 0
+        buf, kind, grid = C.create_string_buffer(32), C.c_int(0), C.c_int(0)
+        while self.lib.blomgpu_dia_name_msc(k, buf, 32, C.byref(kind), C.byref(grid)) == 0:
+            out.append((buf.value.decode(), kind.value, "puv"[grid.value]))
+            k += 1
+        return out
+
+    def dia_set_mertra(self, mtlat=None, nind=None, pts=None, oflg=None, ocn_nreg=0, nflg=None, regflg=None, minlat=None, maxlat=None):
+        """diamer's sections and regions (phy/mod_dia.F90:4026-4108): mtlat (lmax,), nind (lmax,), pts (sum nind, 4) = (i, j, uflg,
+        vflg) 1-based global, oflg (jtdm, itdm), regflg (mer_nreg, 20) with nflg (mer_nreg,) and the latitude bounds; no argument
+        clears the table -- blomgpu_dia_set_mertra"""
+        if mtlat is None:
+            self._chk(self.lib.blomgpu_dia_set_mertra(self.ctx, 0, None, None, None, None, 0, 0, None, None, None, None))
+            return
+        f8 = lambda a: np.ascontiguousarray(a, dtype=np.float64)
+        i4 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        mtlat, minlat, maxlat = f8(mtlat), f8(minlat), f8(maxlat)
+        nind, pts, oflg, nflg, regflg = i4(nind), i4(pts).reshape(-1, 4), i4(oflg), i4(nflg), i4(regflg)
+        if nind.size != mtlat.size or pts.shape[0] != int(nind.sum()) or regflg.shape != (nflg.size, 20) or minlat.size != nflg.size or maxlat.size != nflg.size:
+            raise ValueError("dia_set_mertra: the tables' extents do not agree")
+        if oflg.shape != (self.jtdm, self.itdm):
+            raise ValueError(f"dia_set_mertra: oflg has shape {oflg.shape}, the global domain is (jtdm, itdm) = {(self.jtdm, self.itdm)}")
+        self._chk(self.lib.blomgpu_dia_set_mertra(self.ctx, C.c_int(mtlat.size), p(mtlat), p(nind), p(pts), p(oflg), C.c_int(int(ocn_nreg)),
+                                                  C.c_int(nflg.size), p(nflg), p(regflg), p(minlat), p(maxlat)))
+
+    def dia_set_sections(self, nsi=None, pts=None, equat_sec=-1):
+        """diasec's sections (phy/mod_dia.F90:3838-3866): nsi (sec_num,), pts (sum nsi, 4) = (i, j, usi, vsi), equat_sec the 1-based
+        section of the upper-350 m sums or -1; no argument clears the table -- blomgpu_dia_set_sections"""
+        if nsi is None:
+            self._chk(self.lib.blomgpu_dia_set_sections(self.ctx, 0, None, None, -1))
+            return
+        nsi, pts = np.ascontiguousarray(nsi, dtype=np.int32), np.ascontiguousarray(pts, dtype=np.int32).reshape(-1, 4)
+        if pts.shape[0] != int(nsi.sum()):
+            raise ValueError("dia_set_sections: the tables' extents do not agree")
+        self._chk(self.lib.blomgpu_dia_set_sections(self.ctx, C.c_int(nsi.size), nsi.ctypes.data_as(C.c_void_p), pts.ctypes.data_as(C.c_void_p),
+                                                    C.c_int(int(equat_sec))))
+
+    def dia_reduce(self):
+        """diamer, diasec and the global sums for the selected msc names, in front of dia_finalize -- blomgpu_dia_reduce"""
+        self._chk(self.lib.blomgpu_dia_reduce(self.ctx))
+
+    def dia_msc(self, name):
+        """one result of the last dia_reduce in the reference's shape: (mer_nreg, kdm | ddm, lmax), (mer_nreg, lmax), (sec_num,) or
+        (1,) -- blomgpu_dia_msc_get"""
+        dims = (C.c_int * 3)()
+        self._chk(self.lib.blomgpu_dia_msc_get(self.ctx, name.encode(), None, 0, dims))       # cap = 0: the shape alone
+        n = dims[0] * dims[1] * dims[2]
+        a = np.empty(n)
+        self._chk(self.lib.blomgpu_dia_msc_get(self.ctx, name.encode(), a.ctypes.data_as(C.c_void_p), n, dims))
+        ndim = 3 if name.startswith("mm") else 2 if name[:2] in ("mh", "ms") else 1      # stream functions, transports, the others
+        return a.reshape([dims[k] for k in range(ndim)])
 
     def dia_select(self, names):
         """replace the selection (a blank-separated string or a list of names; empty: none) -- blomgpu_dia_select"""

@@ -417,6 +417,60 @@ int  blomgpu_dia_name_ext(int index, char *buf, int cap, int *kind, int *grid);
 int  blomgpu_dia_alarm(blomgpu_ctx *, int alarm);
 int  blomgpu_ale_remap_diazlv(blomgpu_ctx *, int m, int n, int mm, int nn, int k1m, int k1n);
 
+/* What diaout_iogrp forms from the accumulators at output time (phy/mod_dia.F90:2366-2588), on the device
+ * (blom_amd/csrc/stage_diaout.hip): diamer (:4004-4629), diasec (:3814-4001), the global sums and means (:2427-2588).  One output group,
+ * a context that holds the whole domain.
+ *
+ * The 23 "msc" names have no accumulator of their own; blomgpu_dia_select takes them and selects their sources as diaini does (:557,
+ *   :559, :598-670):
+ *     "mmflxl mmftdl mmfsml"       overturning stream function in density space   umfll vmfll | umfltdl vmfltdl | umflsml vmflsml
+ *                                  (class names: they need a sigdia table)
+ *     "mmflxd mmftdd mmfsmd"       the same in depth space                         uflxlvl vflxlvl | umfltdlvl vmfltdlvl | umflsmlvl vmflsmlvl
+ *     "mhflx mhftd mhfsm mhfld"    meridional heat transports                      utflx vtflx | utfltd vtfltd | utflsm vtflsm | utflld vtflld
+ *     "msflx msftd msfsm msfld"    meridional salt transports                      the same on s
+ *     "masstr heattr salttr"       transports through named sections               uflxlvl vflxlvl | utflxlvl vtflxlvl | usflxlvl vsflxlvl
+ *     "massgs salnga tempga"       global mass, mean salinity and temperature      dp (+ saln | temp)
+ *     "volgs"  "sssga sstga"       global volume; mean surface S and T             dz;  sss | sst
+ * blomgpu_dia_name_msc: the 133 rows of blomgpu_dia_name_ext in their order, then these 23 with kind 5.  The earlier enumerators do
+ *   not list them.
+ * blomgpu_dia_set_mertra: what diamer reads from mer_orfile and mer_mifile (:4026-4108), as the caller's tables: lmax sections with
+ *   latitude mtlat[l] and nind[l] points each, pts[sum nind][4] = (i, j, uflg, vflg) with i, j 1-based in the global domain; the ocean
+ *   region flags oflg[jtdm][itdm]; ocn_nreg; mer_nreg meridional regions with nflg[m] flags regflg[m][20] (regflg[m][0] == 0: all ocean
+ *   regions, :4242) and latitude bounds minlat[m], maxlat[m].  A point whose oflg <= 0 is dropped (:4070).  Refused with a message: an
+ *   index outside 1..itdm | 1..jtdm (:4076-4086), oflg > ocn_nreg, a region flag outside 0..ocn_nreg (0 as the first flag only),
+ *   lmax > itdm+jtdm and a section that keeps more than itdm+jtdm points (ldm, sdm :163-164), ocn_nreg or mer_nreg outside 1..32.
+ *   NULL tables with lmax == 0 clear the table.
+ * blomgpu_dia_set_sections: what diasec reads from sec_sifile (:3838-3866): sec_num sections of nsi[s] points, pts[sum nsi][4] =
+ *   (i, j, usi, vsi); equat_sec the 1-based section that takes the upper-350 m sums (:3849), -1 for none.  With equat_sec >= 1 the
+ *   depth levels must be the 35-level table (k350 = 12, w350 = 1., :112-113) or LEVITUS2X (25, .5, :131-132): a table of
+ *   blomgpu_dia_set_levels is refused, here and again at blomgpu_dia_reduce.  NULL tables with sec_num == 0 clear the table.
+ *   Both tables are copied to the device once, may be set at any time, and are read by blomgpu_dia_reduce only.
+ * blomgpu_dia_reduce: runs what the selection asks for on the context's stream, the results into a small device buffer; the host is
+ *   not made to wait.  Where diaout_iogrp has these computations: after the last blomgpu_step of the window (and after
+ *   blomgpu_ale_remap_diazlv where that applies), before blomgpu_dia_finalize -- which writes fill values into the level rows, so
+ *   from finalize until blomgpu_dia_reset or a new selection a reduce is refused.  Also refused, each with its reason: nacc == 0,
+ *   an msc name whose table has not been set, no msc name selected, sssga | sstga with "area" <= 0, a context that is a tile of a group
+ *   or an RCCL rank.  It reads accumulators only: twice gives the same bytes, no accumulator and no model field changes.
+ *   The bits are the reference's: r = (.5*spcifh | .5*g2kg | .5)/((grav*baclin)*real(nacc)); the running sums of :4188-4212, :4340-4371,
+ *   :4492-4559, :3903-3953 at the wet u | v points and 0. elsewhere; the section sums serial in the table's order, mflx_or(l,o) =
+ *   (mflx_or(l,o) + real(uflg)*ucum) + real(vflg)*vcum, one per ocean region; the region sums of :4235-4256; nf90_fill_double where
+ *   mtlat lies outside the region's bounds, for the eight transports where the region has no point (:4254), in depth space below
+ *   kmax(l,m) (:4449-4467); the global numbers with xcsum's order, salnga and tempga divided by the unscaled massgs.
+ *   Options (blomgpu_set_int; blomgpu_option_name does not list them): "diaout_entries" (1..256, default 256) section points per
+ *   pass and "diaout_levels" (1..8, default 8) levels per chunk of the section kernel; the results do not depend on them.
+ * blomgpu_dia_msc_get: the result of one selected name from the last reduce into out[cap], its shape into dims[3] -- the reference's
+ *   (:4113-4119): [mer_nreg][kdm | ddm][lmax] for the stream functions, [mer_nreg][lmax][1] for the transports, [sec_num][1][1] for the
+ *   section transports, [1][1][1] for the global names.  cap == 0 asks for the shape alone (out may be NULL).  Refused before a
+ *   reduce, for a name that is not selected, and with a cap that is neither 0 nor enough (dims is filled all the same).
+ * Not built: the barotropic stream function btmstr (:2376-2424), tiles and RCCL ranks, several output groups. */
+int  blomgpu_dia_name_msc(int index, char *buf, int cap, int *kind, int *grid);
+int  blomgpu_dia_set_mertra(blomgpu_ctx *, int lmax, const double *mtlat, const int *nind, const int *pts /* [sum nind][4] */,
+                            const int *oflg /* [jtdm][itdm] */, int ocn_nreg, int mer_nreg, const int *nflg,
+                            const int *regflg /* [mer_nreg][20] */, const double *minlat, const double *maxlat);
+int  blomgpu_dia_set_sections(blomgpu_ctx *, int sec_num, const int *nsi, const int *pts /* [sum nsi][4] */, int equat_sec);
+int  blomgpu_dia_reduce(blomgpu_ctx *);
+int  blomgpu_dia_msc_get(blomgpu_ctx *, const char *name, double *out, int cap, int *dims /* [3] */);
+
 /* The end of blom_step (phy/mod_blom_step.F90:96-252).  Everything here is off until an option declares it; an undeclared context steps
  * as before.  The options are set like every other (blomgpu_set_int / _real / _str); blomgpu_option_name does not list them.
  *
